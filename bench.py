@@ -51,7 +51,13 @@ def parse():
     ap.add_argument("--launch-check", action="store_true",
                     help="only bring the ranks up, check the world size against --gpus, print {n_gpus, ranks} and exit "
                          "(no GPU work: with LNR_DIST_BACKEND=gloo this runs on a CPU-only box; tests/test_host.py)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what their last step handed back to the caller - density parameters, keyframe "
+                         "poses, occupancy grid, loss terms - as DIR/<name>.npy (train mode), to compare two builds output for output")
+    args = ap.parse_args()
+    if args.dump_outputs is not None and (args.mode != "train" or args.steps < 1):
+        ap.error("--dump-outputs needs --mode train and --steps >= 1")
+    return args
 
 
 def spawn_ranks(args):
@@ -528,6 +534,44 @@ def api_parity_leg(args, device_index, iters, warmup):
                     "reference.  The headline value is the fused-loss mode of the same window."}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, opt, window, world, rank):
+    """--dump-outputs: what the last timed step handed back to the caller of the mapping loop, as out_dir/<name>.npy, in full
+    (33.7 MB for the default network):
+      sigma_params    float32 [n_params]       density network parameters after the step (MLP weights, then the hash tables)
+      poses           float32 [K, 6]           every keyframe's lidar pose (translation, axis-angle); sharded: each from its owner rank
+      occupancy_grid  float32 [1, 1, V, V, V]  occupancy grid logits
+      loss_terms      float64 [5]              the step's {total, depth, los, opacity, sum of eps}; sharded: summed over the ranks
+    Inputs are seeded (synthetic scans, torch.manual_seed in make_bench_optimizer / per rank), so two runs with the same arguments
+    start from the same state.  Collective in a sharded run (every rank calls it); rank 0 writes."""
+    import numpy as np
+    import torch.distributed as dist
+    dev = torch.device("cuda", torch.cuda.current_device())
+    poses = torch.stack([kf.get_lidar_pose().get_pose_tensor().detach().float().cpu() for kf in window]).to(dev)
+    loss = opt.last_stats["loss_terms"][-1, :5].to(dev, torch.float64)
+    if world > 1:
+        from loner_amd.mapping.sharding import shard_window
+        owned = torch.zeros(len(window), 1, device=dev)
+        owned[shard_window(len(window), world, rank)] = 1.0
+        poses = poses * owned                      # a rank's own keyframes only: the sum over the ranks is each keyframe's owner's pose
+        dist.all_reduce(poses)
+        dist.all_reduce(loss)
+    if rank != 0:
+        return
+    arrays = {"sigma_params": opt._model.nerf_model._model_sigma.params.detach().float(),
+              "poses": poses, "occupancy_grid": opt._occupancy_grid_model.occupancy_grid.detach().float(), "loss_terms": loss}
+    arrays = {k: v.cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    print(f"bench.py: wrote {', '.join(f'{k}{list(a.shape)}' for k, a in arrays.items())} ({total / 1e6:.1f} MB) to {out_dir}",
+          file=sys.stderr, flush=True)
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -653,6 +697,8 @@ def main():
 
     kprof = ops.profile_read()                     # kernels inside lnr_density_forward / _backward, HIP events in the library
     ops.profile_enable(False)
+    if args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, opt, my_window, world, rank)      # (before anything below trains the map further)
     if rank != 0:
         if world > 1:
             dist.destroy_process_group()

@@ -24,6 +24,19 @@ def cube_exit_distance(origins: torch.Tensor, dirs: torch.Tensor) -> torch.Tenso
     return per_axis.min(dim=1, keepdim=True).values
 
 
+def rotate(rot: torch.Tensor, local: torch.Tensor) -> torch.Tensor:
+    """rot [3,3] @ local [3,n], rounded as the reference's `R @ local` was when the fixtures were captured: torch hands the product to
+    MKL, whose AVX512 sgemm forms the k = 0 product and adds the other two with fused multiply-adds, in k order.  MKL's path depends on
+    the host CPU (on AMD processors it takes a plain multiply-then-add path whatever MKL_CBWR says; 37 % of the elements differ in the
+    last bit, 40 % of G8's rays then sample differently), so the oracle rounds this product itself.  A float32 product is exact in
+    float64, so one float64 add rounded to float32 is the fused multiply-add (up to a double rounding when the float64 sum falls
+    exactly halfway between two float32 values).  Differentiable."""
+    acc = rot[:, 0:1] * local[0:1]
+    for k in (1, 2):
+        acc = (rot[:, k:k + 1].double() * local[k:k + 1].double() + acc.double()).float()
+    return acc
+
+
 def lidar_ray_records(directions: torch.Tensor, distances: torch.Tensor, index: torch.Tensor,
                       transform: torch.Tensor, ray_range, scale, shift,
                       keep_all: bool = False):
@@ -35,7 +48,7 @@ def lidar_ray_records(directions: torch.Tensor, distances: torch.Tensor, index: 
     local = directions[:, index]
     origin = (transform[:3, 3] + shift) / scale
     origins = origin.tile(index.shape[0], 1)
-    world = (transform[:3, :3] @ local).T
+    world = rotate(transform[:3, :3], local).T
     unit = world / torch.linalg.vector_norm(world, dim=1, keepdim=True)
     ones = torch.ones_like(origins[:, :1])
     near = ray_range[0] / scale * ones

@@ -198,13 +198,13 @@ def test_optimizer_first_iterations_match_reference_state_by_state(golden, k):
     assert e["pose"] < 2e-6 and e["grid"] < 1e-5, e
 
 
-def test_optimizer_schedule_default_config_properties():
+def test_optimizer_schedule_default_config_properties(tmp_path):
     """Default network (16-level hash grid, 64-wide MLP), 2 keyframes, in-kernel RNG: the schedule runs, the
     anchored keyframe does not move, the free one does, the loss goes down, nothing is NaN."""
     from loner_amd.common.settings import default_optimizer_settings
     from loner_amd.mapping.optimizer import Optimizer
     from loner_amd.utils import synthetic as SY
-    s = default_optimizer_settings()
+    s = default_optimizer_settings(log_directory=str(tmp_path))          # (timing.csv: a fresh file of this run's, not a shared one)
     s["num_samples"]["sky"] = 0
     s["keyframe_schedule"][0]["iteration_schedule"][0]["num_iterations"] = 60
     s["keyframe_schedule"][1]["iteration_schedule"][1]["num_iterations"] = 20
