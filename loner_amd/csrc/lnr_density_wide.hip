@@ -597,30 +597,24 @@ wide_dx_kernel(const float* __restrict__ WT, int n_kt, const float* __restrict__
 // peak: VERDICT r5 weak #10).  Per chunk of 131 072 samples (rocprofv3, profiles/r06_wide_networks.txt; fp32 MFMA -> f16 MFMA): weight
 // gradient of a hidden matrix 212 -> 180 us, of the first layer 111 -> 67 us, first-layer back-propagation 74 -> 63 us, hidden
 // back-propagation 246 -> 292 us (kept on the fp32 pipe): 15.9 -> ~14.5 ms - these kernels were never matrix-bound, their planes
-// cross L2 -> L1 four times (weight gradient: 1.07 GB per chunk and matrix at ~6 TB/s) or leave as 64-byte row segments.  Here dZ is converted to fp16 where it is consumed, scaled by an exact power of two per 32-sample tile -
-// 2^-e, e = the exponent of the tile's largest |d_sigma|: every dZ column is d_sigma[m] times O(1) factors, so the scaled values sit
-// around 1 whatever the loss magnitude, and what underflows fp16 lies 2^-14 below its tile's maximum - and the f16 MFMA results are
-// un-scaled in fp32 (the same scheme as the fused 128-wide kernels, lnr_f16_bwd_kernel.h, per tile instead of per workgroup step).
-// A tile whose d_sigma are all zero contributes nothing and is skipped.
+// cross L2 -> L1 four times (weight gradient: 1.07 GB per chunk and matrix at ~6 TB/s) or leave as 64-byte row segments.  Here dZ is converted to fp16 where it is consumed, scaled by an exact power of two per
+// wave operand - 2^-e, e = the exponent of the largest |dZ| the wave rounds (its 16 rows x 32 samples in the weight gradient, its 256 rows
+// x 32 samples in the first-layer back-propagation): the scaled values lie below 2 whatever the loss magnitude, the weights or the
+// activation, and what underflows fp16 lies 2^-14 below the operand's maximum - and the f16 MFMA results are un-scaled in fp32.  (The
+// scale used to come from the tile's largest |d_sigma|: hidden dZ that outgrew d_sigma by 2^15 - large output weights, Exponential - passed
+// 65504, and dZ far below it - saturated units, small output weights - fell into subnormals.)  An all-zero operand contributes nothing and
+// is skipped.
 
-// 2^-e for the 32 samples [ml0, ml0 + 32) of the chunk (lanes (c, g): every lane calls it; the result is wave-uniform); 0: all-zero tile.
-// In two halves so that the load can be issued a tile ahead of its use (wide_dw_h_kernel: one exposed L2 round trip per tile otherwise).
-__device__ __forceinline__ float wide_tile_dsigma(const float* __restrict__ d_sigma, const WideSamples& smp, int64_t ml0, int64_t M, int lane) {
-    const int64_t ml = ml0 + (lane & 31);
-    return ml < M ? __builtin_fabsf(d_sigma[smp.lo + ml]) : 0.0f;
-}
-__device__ __forceinline__ float wide_tile_scale_of(float v, float* inv) {
+// 2^-e for a wave's dZ operand, v = the lane's largest |dZ| (every lane calls it; the result is wave-uniform); 0: an all-zero operand
+__device__ __forceinline__ float wide_wave_scale_of(float v, float* inv) {
     v = fmaxf(v, __shfl_xor(v, 1, 64)); v = fmaxf(v, __shfl_xor(v, 2, 64)); v = fmaxf(v, __shfl_xor(v, 4, 64));
-    v = fmaxf(v, __shfl_xor(v, 8, 64)); v = fmaxf(v, __shfl_xor(v, 16, 64));
+    v = fmaxf(v, __shfl_xor(v, 8, 64)); v = fmaxf(v, __shfl_xor(v, 16, 64)); v = fmaxf(v, __shfl_xor(v, 32, 64));
     v = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(v)));
-    if (!(v > 0.0f) || !(v < 3.0e38f)) { *inv = 0.0f; return 0.0f; }        // nothing to propagate (or a non-finite d_sigma: left to the fp32 checks upstream)
+    if (!(v > 0.0f) || !(v < 3.0e38f)) { *inv = 0.0f; return 0.0f; }        // nothing to propagate (or a non-finite dZ: left to the fp32 checks upstream)
     uint32_t be = (__float_as_uint(v) >> 23) & 0xFFu;
     be = be < 2u ? 2u : (be > 252u ? 252u : be);
     *inv = __uint_as_float(be << 23);                                        // 2^e
     return __uint_as_float((254u - be) << 23);                               // 2^-e
-}
-__device__ __forceinline__ float wide_tile_scale(const float* __restrict__ d_sigma, const WideSamples& smp, int64_t ml0, int64_t M, int lane, float* inv) {
-    return wide_tile_scale_of(wide_tile_dsigma(d_sigma, smp, ml0, M, lane), inv);
 }
 
 // dZ_prev = act'(Z_prev) . (W^T dZ) for a hidden matrix (TO_FEAT: the d_feature planes of the first layer) on v_mfma_f32_16x16x32_f16:
@@ -629,7 +623,7 @@ __device__ __forceinline__ float wide_tile_scale(const float* __restrict__ d_sig
 template <bool TO_FEAT>
 __global__ void __launch_bounds__(256)
 wide_dx_h_kernel(const float* __restrict__ WT, int n_rt, const float* __restrict__ dz, int64_t chp, int act, WideSamples smp,
-                 const float* __restrict__ d_sigma, const float* __restrict__ z_prev, float* __restrict__ out, int64_t out_stride, int enc_dim) {
+                 const float* __restrict__ z_prev, float* __restrict__ out, int64_t out_stride, int enc_dim) {
     __shared__ __attribute__((aligned(16))) f16 w_h[2][LNR_WIDE_H * WIDE_LDS_HROW];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c = lane & 15, g = lane >> 4;
@@ -648,8 +642,15 @@ wide_dx_h_kernel(const float* __restrict__ WT, int n_rt, const float* __restrict
             ml[t] = (2 * (active ? pair : n_pairs - 1) + t) * 16 + c;
             if (ml[t] >= M) ml[t] = M - 1;                        // (finite operands for padding columns; their results are not stored)
         }
-        float inv_sc;
-        const float sc = wide_tile_scale(d_sigma, smp, (active ? pair : n_pairs - 1) * 32, M, lane, &inv_sc);
+        float inv_sc, vmax = 0.0f;                                // the wave's largest |dZ| over its 256 rows x 32 samples (live samples)
+        for (int kb = 0; kb < n_kb; ++kb)
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const bool live = (2 * (active ? pair : n_pairs - 1) + t) * 16 + c < M;
+#pragma unroll
+                for (int r = 0; r < 8; ++r) vmax = fmaxf(vmax, live ? __builtin_fabsf(dz[(size_t)(32 * kb + 8 * g + r) * chp + ml[t]]) : 0.0f);
+            }
+        const float sc = wide_wave_scale_of(vmax, &inv_sc);
         f32x4 Z[2][16];
 #pragma unroll
         for (int t = 0; t < 2; ++t)
@@ -770,7 +771,7 @@ wide_dx_h_kernel(const float* __restrict__ WT, int n_rt, const float* __restrict
 template <int IN>
 __global__ void __launch_bounds__(256)
 wide_dw_h_kernel(const float* __restrict__ dz, int64_t chp, const float* __restrict__ in, int64_t in_stride, int enc_dim, int K, int act,
-                 WideSamples smp, const float* __restrict__ d_sigma, float* __restrict__ partial, int64_t n_mlp, int64_t layer_off) {
+                 WideSamples smp, float* __restrict__ partial, int64_t n_mlp, int64_t layer_off) {
     constexpr int ROW = 40;                                       // halves per staged column: 32 samples + 8 (80-byte rows: conflict-free 16-byte reads)
     __shared__ __attribute__((aligned(16))) f16 b_s[2][64 * ROW];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -811,10 +812,8 @@ wide_dw_h_kernel(const float* __restrict__ dz, int64_t chp, const float* __restr
         for (int ct = 0; ct < NCT; ++ct) acc[ct] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
         const float4 zero4 = float4{0.0f, 0.0f, 0.0f, 0.0f};
         float4 a0 = zero4, a1 = zero4, n0 = zero4, n1 = zero4, r0 = zero4, r1 = zero4;
-        float ds_c = 0.0f, ds_n = 0.0f;                           // the lane's |d_sigma| of the tile in hand / the next one (for the tile's scale)
         int64_t tile = split;
         if (tile < n_t32) {
-            ds_c = wide_tile_dsigma(d_sigma, smp, tile * 32, M, lane);
             if (s_load) { r0 = *reinterpret_cast<const float4*>(s_src + tile * 32); r1 = *reinterpret_cast<const float4*>(s_src + tile * 32 + 4); }
             a0 = *reinterpret_cast<const float4*>(dz_row + tile * 32); a1 = *reinterpret_cast<const float4*>(dz_row + tile * 32 + 4);
             stage(0, tile, r0, r1);
@@ -824,11 +823,15 @@ wide_dw_h_kernel(const float* __restrict__ dz, int64_t chp, const float* __restr
             const int64_t nt = tile + LNR_WIDE_SPLITS < n_t32 ? tile + LNR_WIDE_SPLITS : tile;
             if (s_load) { r0 = *reinterpret_cast<const float4*>(s_src + nt * 32); r1 = *reinterpret_cast<const float4*>(s_src + nt * 32 + 4); }
             n0 = *reinterpret_cast<const float4*>(dz_row + nt * 32); n1 = *reinterpret_cast<const float4*>(dz_row + nt * 32 + 4);
-            ds_n = wide_tile_dsigma(d_sigma, smp, nt * 32, M, lane);
+            const int64_t m0 = tile * 32 + 8 * g;
+            float vmax = 0.0f;                                    // the lane's largest |dZ| of the operand in hand (live samples)
+            vmax = fmaxf(fmaxf(m0 < M ? __builtin_fabsf(a0.x) : 0.0f, m0 + 1 < M ? __builtin_fabsf(a0.y) : 0.0f),
+                         fmaxf(m0 + 2 < M ? __builtin_fabsf(a0.z) : 0.0f, m0 + 3 < M ? __builtin_fabsf(a0.w) : 0.0f));
+            vmax = fmaxf(vmax, fmaxf(fmaxf(m0 + 4 < M ? __builtin_fabsf(a1.x) : 0.0f, m0 + 5 < M ? __builtin_fabsf(a1.y) : 0.0f),
+                                     fmaxf(m0 + 6 < M ? __builtin_fabsf(a1.z) : 0.0f, m0 + 7 < M ? __builtin_fabsf(a1.w) : 0.0f)));
             float inv_sc;
-            const float sc = wide_tile_scale_of(ds_c, &inv_sc);
-            if (sc != 0.0f) {                                     // (wave-uniform, and the same for the four waves: no barrier inside)
-                const int64_t m0 = tile * 32 + 8 * g;
+            const float sc = wide_wave_scale_of(vmax, &inv_sc);
+            if (sc != 0.0f) {                                     // (wave-uniform: no barrier inside)
                 auto dzv = [&](float v, int i) { return m0 + i < M ? v * sc : 0.0f; };
                 const f16x8 a = frag_from_dwords(pack_h2(dzv(a0.x, 0), dzv(a0.y, 1)), pack_h2(dzv(a0.z, 2), dzv(a0.w, 3)),
                                                  pack_h2(dzv(a1.x, 4), dzv(a1.y, 5)), pack_h2(dzv(a1.z, 6), dzv(a1.w, 7)));
@@ -842,7 +845,7 @@ wide_dw_h_kernel(const float* __restrict__ dz, int64_t chp, const float* __restr
                 }
             }
             stage((it + 1) & 1, nt, r0, r1);
-            a0 = n0; a1 = n1; ds_c = ds_n;
+            a0 = n0; a1 = n1;
             __syncthreads();
         }
         float* out = partial + (size_t)(1 + split) * n_mlp + layer_off;
@@ -951,8 +954,8 @@ static int wide_backward(const WideCtx& c, const float* d_sigma, float* dfeat, f
             const int64_t layer_off = l == 0 ? 0 : (int64_t)c.H * c.K1 + (int64_t)(l - 1) * c.H * c.H;
             const dim3 grid_w((unsigned)(4 * ((K + 63) / 64) * LNR_WIDE_SPLITS));
             if (!want_dw) {}                                       // frozen parameters (tracking phase): the input gradient only
-            else if (HALF && LNR_WIDE_F16_BWD && l > 0) hipLaunchKernelGGL((wide_dw_h_kernel<WIDE_IN_Z>), grid_w, block, 0, c.st, dz, c.chp, c.z(l - 1), c.chp, c.H, K, c.act, s, d_sigma, slabs, n_mlp, layer_off);
-            else if (HALF && LNR_WIDE_F16_BWD) hipLaunchKernelGGL((wide_dw_h_kernel<WIDE_IN_PAIR>), grid_w, block, 0, c.st, dz, c.chp, c.feat, c.m_pad, c.spec->enc_dim, K, c.act, s, d_sigma, slabs, n_mlp, layer_off);
+            else if (HALF && LNR_WIDE_F16_BWD && l > 0) hipLaunchKernelGGL((wide_dw_h_kernel<WIDE_IN_Z>), grid_w, block, 0, c.st, dz, c.chp, c.z(l - 1), c.chp, c.H, K, c.act, s, slabs, n_mlp, layer_off);
+            else if (HALF && LNR_WIDE_F16_BWD) hipLaunchKernelGGL((wide_dw_h_kernel<WIDE_IN_PAIR>), grid_w, block, 0, c.st, dz, c.chp, c.feat, c.m_pad, c.spec->enc_dim, K, c.act, s, slabs, n_mlp, layer_off);
             else if (l > 0) hipLaunchKernelGGL((wide_dw_kernel<HALF, WIDE_IN_Z>), grid_w, block, 0, c.st, dz, c.chp, c.z(l - 1), c.chp, c.H, K, c.act, s, slabs, n_mlp, layer_off);
             else if (HALF) hipLaunchKernelGGL((wide_dw_kernel<HALF, WIDE_IN_PAIR>), grid_w, block, 0, c.st, dz, c.chp, c.feat, c.m_pad, c.spec->enc_dim, K, c.act, s, slabs, n_mlp, layer_off);
             else hipLaunchKernelGGL((wide_dw_kernel<HALF, WIDE_IN_FEAT>), grid_w, block, 0, c.st, dz, c.chp, c.feat, c.m_pad, c.spec->enc_dim, K, c.act, s, slabs, n_mlp, layer_off);
@@ -960,7 +963,7 @@ static int wide_backward(const WideCtx& c, const float* d_sigma, float* dfeat, f
             if (want_dw) hipLaunchKernelGGL(wide_fold_kernel, dim3((unsigned)((count + 255) / 256)), block, 0, c.st, slabs, n_mlp, layer_off, count);
             if (l > 0) {
                 if (HALF && LNR_WIDE_F16_BWD && LNR_WIDE_F16_DX_HIDDEN)
-                    hipLaunchKernelGGL((wide_dx_h_kernel<false>), grid_p, block, 0, c.st, wt + (size_t)(l - 1) * c.H * c.H, c.H / 16, dz, c.chp, c.act, s, d_sigma,
+                    hipLaunchKernelGGL((wide_dx_h_kernel<false>), grid_p, block, 0, c.st, wt + (size_t)(l - 1) * c.H * c.H, c.H / 16, dz, c.chp, c.act, s,
                                        c.z(l - 1), dz_other, c.chp, 0);
                 else
                     hipLaunchKernelGGL((wide_dx_kernel<HALF, false>), grid_p, block, 0, c.st, wt + (size_t)(l - 1) * c.H * c.H, c.H / 16, dz, c.chp, c.act, s,
@@ -968,7 +971,7 @@ static int wide_backward(const WideCtx& c, const float* d_sigma, float* dfeat, f
                 float* t = dz; dz = dz_other; dz_other = t;
             } else if (want_dfeat) {
                 if (HALF && LNR_WIDE_F16_BWD)
-                    hipLaunchKernelGGL((wide_dx_h_kernel<true>), grid_p, block, 0, c.st, wt_first, K / 16, dz, c.chp, c.act, s, d_sigma, (const float*)nullptr, dfeat,
+                    hipLaunchKernelGGL((wide_dx_h_kernel<true>), grid_p, block, 0, c.st, wt_first, K / 16, dz, c.chp, c.act, s, (const float*)nullptr, dfeat,
                                        c.m_pad, c.spec->enc_dim);
                 else
                     hipLaunchKernelGGL((wide_dx_kernel<HALF, true>), grid_p, block, 0, c.st, wt_first, K / 16, dz, c.chp, c.act, s, (const float*)nullptr, dfeat,

@@ -1,12 +1,13 @@
 // General fp16-mode backward of the density MLP (any supported width / depth / activation): weight gradients of every layer, the
 // output row's gradient and the feature gradient (d_feature planes) in ONE launch.  Host dispatch: lnr_density_f16_bwd.hip.
-// Semantics = oracle/network.py with precision="fp16": dZ is scaled by an exact power of two before its fp16 conversion so that no
-// gradient underflows whatever the loss magnitude, and un-scaled in fp32; products accumulate in fp32.  The oracle scales every
-// 32-sample tile by the power of two of its largest |d_sigma|; this kernel keeps ONE unit 2^e for the workgroup - the exponent of the
-// largest |d_sigma| of a step's 128 samples, kept while that maximum stays within [2^-4, 2) of it - and rescales the fp32
-// accumulators by the exact power of two whenever the unit moves.  The weight-gradient MFMAs then accumulate straight into their
-// registers (a per-wave scale meant a separate product, four v_accvgpr_read and two v_pk_fma per MFMA, 1000 VALU instructions a
-// step); values differ from the oracle's only where an element lies 2^-20 below its tile's maximum (fp16 subnormals).
+// Semantics = oracle/network.py with precision="fp16": dZ is scaled by an exact power of two before its fp16 conversion so that it
+// neither overflows nor underflows whatever the loss magnitude, the weights or the activation, and un-scaled in fp32; products
+// accumulate in fp32.  Every hidden layer j keeps ONE unit 2^U_j for the workgroup: the exponent of the largest |dZ_j| of a step's 128
+// samples, taken from the fp32 dZ_j of all four waves before it is rounded (one LDS exchange per layer), kept while that maximum stays
+// within [2^-4, 2) of it.  The fp32 accumulators of the weight gradient that dZ_j feeds are rescaled by the exact power of two whenever
+// the unit moves, so the weight-gradient MFMAs accumulate straight into their registers (a per-wave scale meant a separate product, four
+// v_accvgpr_read and two v_pk_fma per MFMA, 1000 VALU instructions a step).  Values differ from the oracle's only where an element lies
+// 2^-14 (at most 2^-18) below its layer's step maximum (fp16 subnormals).  d_sigma itself only sets the fp32 domain dZ is formed in.
 //
 // Shapes are compile time (HT row tiles, NH hidden layers, KT first-layer K blocks), the weights sit in LDS in the forward kernel's
 // layout (lnr_f16_fwd_kernel.h: first-layer rows zero-padded to KT blocks, hidden rows K-permuted, 256-byte rows XOR-swizzled, the
@@ -38,8 +39,9 @@ struct BwdLds {
     static constexpr int TILE = 32 * 16;                                    // halves of one [32 samples][16 columns] image tile
     static constexpr int IMG_X = HT * TILE, IMG_WAVE = (HT + NT) * TILE;    // per wave: dZ tiles, then the layer-input tiles
     static constexpr int OFF_IMG = W::N_W + 2 * W::H;                       // halves: behind the weights and the fp32 bias
-    static constexpr int OFF_SC = OFF_IMG + 4 * IMG_WAVE;                   // 2 x 4 floats (the waves' |d_sigma| maxima, this step / next), then dWo partials [4][H]
-    static constexpr size_t BYTES = (size_t)OFF_SC * sizeof(f16) + 8 * sizeof(float) + 4 * (size_t)W::H * sizeof(float);
+    static constexpr int OFF_SC = OFF_IMG + 4 * IMG_WAVE;                   // 2 x 4 floats (the waves' |d_sigma| maxima, this step / next), then dWo partials [4][H],
+    static constexpr size_t BYTES = (size_t)OFF_SC * sizeof(f16) + 8 * sizeof(float) + 4 * (size_t)W::H * sizeof(float) +   // then the waves' |dZ|
+                                    4 * F16_NH_MAX * sizeof(float);                                                          // maxima per layer
 };
 
 // K = 32 fragment (8 halves per lane) from two transposing reads: p = the lane's address in the first [4][16] block, the second
@@ -96,6 +98,7 @@ mlp_backward_f16_gen_kernel(const LnrNetSpec spec, const float* __restrict__ par
     f16* img = img_all + wave * B::IMG_WAVE;                                // own images: dZ tiles [HT], input tiles [NT]
     float* mx_s = reinterpret_cast<float*>(Ws + B::OFF_SC);
     float* dwo_s = mx_s + 8;
+    float* lmx_s = dwo_s + 4 * H;                                           // [layer][wave] largest |dZ| of the step (fp32, before rounding)
     __syncthreads();
 
     const int64_t M = live_samples(n_points, n_rays_dev, n_rays, n_samples);
@@ -239,10 +242,10 @@ mlp_backward_f16_gen_kernel(const LnrNetSpec spec, const float* __restrict__ par
     // ---- one forward layer with the row pipeline of fwd_layer, keeping what the backward needs.
     // LASTH = false: Aout = the activations as the next layer's B operands, Dout = the activation's derivative in the same packing
     //                (not for ReLU: the gate is read off the activations).
-    // LASTH = true:  dzp = dZ of this layer (scaled domain) = ds sc_dn wo act'(Z), and dwo += ds act(Z).
+    // LASTH = true:  dzf = dZ of this layer in fp32 (d_sigma domain) = ds sc_dn wo act'(Z), and dwo += ds act(Z).
     auto fwd_keep = [&](auto last_tag, auto bias_tag, auto kb_tag, auto s_tag, const f16* Wl, const int (&koff)[F16_KB_MAX],
                         const u32x4 (&Bin)[F16_KB_MAX][2], u32x4 (&Aout)[F16_KB_MAX][2], uint32_t (&Dout)[F16_KB_MAX][2][4],
-                        uint32_t (&dzp)[HT][2][2], const float (&dsd)[2], const float (&ds)[2]) {
+                        float (&dzf)[HT][2][4], const float (&dsd)[2], const float (&ds)[2]) {
         constexpr bool LASTH = decltype(last_tag)::value, BIAS = decltype(bias_tag)::value;
         constexpr int KB = decltype(kb_tag)::value, S = decltype(s_tag)::value;
         typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
@@ -259,14 +262,11 @@ mlp_backward_f16_gen_kernel(const LnrNetSpec spec, const float* __restrict__ par
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 if constexpr (LASTH) {
-                    float dz[4];
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         dwo[jt][r] = __builtin_fmaf(ds[t], fwd_act<ACT>(z[t][r], act), dwo[jt][r]);
-                        dz[r] = (dsd[t] * (float)wv[r]) * gact_d<ACT>(z[t][r], act);
+                        dzf[jt][t][r] = (dsd[t] * (float)wv[r]) * gact_d<ACT>(z[t][r], act);      // (rounded once its layer's unit is known)
                     }
-                    dzp[jt][t][0] = pack_h2(dz[0], dz[1]);
-                    dzp[jt][t][1] = pack_h2(dz[2], dz[3]);
                 } else {
                     if constexpr (RELU) {
                         Aout[jt >> 1][t][2 * (jt & 1)] = relu_pack_h2(z[t][0], z[t][1]);
@@ -411,8 +411,44 @@ mlp_backward_f16_gen_kernel(const LnrNetSpec spec, const float* __restrict__ par
 
     u32x4 x[F16_KB_MAX][2], xn[F16_KB_MAX][2];
     float ds[2], dsn[2];
-    uint32_t e_unit = 127u;                                                 // biased exponent of the unit dZ is expressed in (workgroup-uniform)
-    bool have_unit = false;
+    uint32_t e_unit = 127u;                                                 // biased exponent of the step's d_sigma domain (workgroup-uniform)
+    uint32_t u_lay[NH];                                                     // biased exponent of layer j's unit: dZ_j and the gradient it feeds
+    bool have_lay[NH];
+#pragma unroll
+    for (int j = 0; j < NH; ++j) { u_lay[j] = 127u; have_lay[j] = false; }
+    // layer j's unit from the four waves' maxima (lmx_s, written before the last barrier) of |dZ_j| in the domain of biased exponent
+    // d_exp; rescales the accumulators dZ_j feeds when the unit moves.  -> the factor from that domain to the unit (exact power of two)
+    auto layer_unit = [&](auto j_tag, uint32_t d_exp) -> float {
+        constexpr int J = decltype(j_tag)::value;
+        const float* mb = lmx_s + 4 * J;
+        const float m = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(fmaxf(fmaxf(mb[0], mb[1]), fmaxf(mb[2], mb[3])))));
+        if (m > 0.0f) {
+            int be = (int)d_exp + (int)((__float_as_uint(m) >> 23) & 0xFFu) - 127;     // biased exponent of the maximum itself
+            be = be < 1 ? 1 : (be > 253 ? 253 : be);
+            const int eu = (int)u_lay[J];
+            if (!have_lay[J] || be > eu || be + 4 < eu) {
+                if (have_lay[J]) {
+                    if (be + 96 < eu) be = eu - 96;                         // the accumulators grow by 2^(eu - be): bounded
+                    const int sh = eu - be;                                 // exact: a power of two (0 when nothing of the old sum would survive)
+                    const float f = sh < -126 ? 0.0f : __uint_as_float((uint32_t)(127 + sh) << 23);
+#pragma unroll
+                    for (int i = 0; i < NO; ++i) {
+                        if constexpr (J == 0) {
+#pragma unroll
+                            for (int k = 0; k < 2 * KT; ++k) acc0[i][k] *= f;
+                            accb[i] *= f;
+                        } else {
+#pragma unroll
+                            for (int k = 0; k < HT; ++k) acch[J > 0 ? J - 1 : 0][i][k] *= f;
+                        }
+                    }
+                }
+                u_lay[J] = (uint32_t)be;
+                have_lay[J] = true;
+            }
+        }
+        return __builtin_ldexpf(1.0f, (int)d_exp - (int)u_lay[J]);
+    };
     if (n_steps > 0) {
         load_step(0, x, ds);
         const float mx0 = wave_max(fmaxf(fabsf(ds[0]), fabsf(ds[1])));
@@ -426,33 +462,15 @@ mlp_backward_f16_gen_kernel(const LnrNetSpec spec, const float* __restrict__ par
         // The lane addresses of the W^T fragments and the image stores (dozens of distinct values of c and g) are cheap to recompute;
         // hoisted out of this loop as invariants they were spilled to scratch and re-read every step (85 scratch loads a step).
         asm volatile("" : "+v"(c), "+v"(g));
-        // the unit: exponent of the step's largest |d_sigma| (its maximum then lies in [1, 2)), kept while that stays within [2^-4, 2)
+        // the d_sigma domain: exponent of the step's largest |d_sigma| (its maximum then lies in [1, 2)) - keeps the fp32 dZ of the last
+        // hidden layer in range whatever the loss magnitude; what is rounded is scaled by the layers' own units
         const float* mxb = mx_s + 4 * (int)(step & 1);
         const float mxg = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(fmaxf(fmaxf(mxb[0], mxb[1]), fmaxf(mxb[2], mxb[3])))));
-        uint32_t be = (__float_as_uint(mxg) >> 23) & 0xFFu;
-        be = be < 1u ? 1u : (be > 253u ? 253u : be);
-        if (mxg > 0.0f && (!have_unit || be > e_unit || be + 4u < e_unit)) {
-            if (have_unit) {
-                if (be + 96u < e_unit) be = e_unit - 96u;                   // the accumulators grow by 2^(e_unit - be): bounded
-                const int sh = (int)e_unit - (int)be;                       // exact: a power of two (0 when nothing of the old sum would survive)
-                const float f = sh < -126 ? 0.0f : __uint_as_float((uint32_t)(127 + sh) << 23);
-#pragma unroll
-                for (int i = 0; i < NO; ++i) {
-#pragma unroll
-                    for (int k = 0; k < 2 * KT; ++k) acc0[i][k] *= f;
-                    accb[i] *= f;
-                    if constexpr (NHID > 0) {
-#pragma unroll
-                        for (int l = 0; l < NHID; ++l)
-#pragma unroll
-                            for (int k = 0; k < HT; ++k) acch[l][i][k] *= f;
-                    }
-                }
-            }
-            e_unit = be;
-            have_unit = true;
+        if (mxg > 0.0f) {
+            const uint32_t be = (__float_as_uint(mxg) >> 23) & 0xFFu;
+            e_unit = be < 1u ? 1u : (be > 253u ? 253u : be);
         }
-        const float sc_dn = __uint_as_float((254u - e_unit) << 23), sc_up = __uint_as_float(e_unit << 23);
+        const float sc_dn = __uint_as_float((254u - e_unit) << 23);
         const float dsd[2] = {ds[0] * sc_dn, ds[1] * sc_dn};
         PHASE(1);
 
@@ -460,18 +478,42 @@ mlp_backward_f16_gen_kernel(const LnrNetSpec spec, const float* __restrict__ par
         u32x4 A[NHID > 0 ? NHID : 1][F16_KB_MAX][2];
         uint32_t Dv[(!RELU && NHID > 0) ? NHID : 1][F16_KB_MAX][2][4];
         uint32_t dzp[HT][2][2];
+        float dzf[HT][2][4];
         using T = std::true_type; using F = std::false_type;
         using KT_ = std::integral_constant<int, KT>; using KH_ = std::integral_constant<int, (NH > 1 ? KBH : 1)>;
         using S0_ = std::integral_constant<int, L::S0>; using SH_ = std::integral_constant<int, L::SH>;
         if constexpr (NH == 1) {
-            fwd_keep(T{}, T{}, KT_{}, S0_{}, Ws, koff0, x, A[0], Dv[0], dzp, dsd, ds);
+            fwd_keep(T{}, T{}, KT_{}, S0_{}, Ws, koff0, x, A[0], Dv[0], dzf, dsd, ds);
         } else {
-            fwd_keep(F{}, T{}, KT_{}, S0_{}, Ws, koff0, x, A[0], Dv[0], dzp, dsd, ds);
+            fwd_keep(F{}, T{}, KT_{}, S0_{}, Ws, koff0, x, A[0], Dv[0], dzf, dsd, ds);
             PHASE(2);
 #pragma unroll
             for (int l = 1; l < NH - 1; ++l)
-                fwd_keep(F{}, F{}, KH_{}, SH_{}, Ws + L::OFF_H + (l - 1) * H * L::SH, koffh, A[l - 1], A[l], Dv[RELU ? 0 : l], dzp, dsd, ds);
-            fwd_keep(T{}, F{}, KH_{}, SH_{}, Ws + L::OFF_H + (NH - 2) * H * L::SH, koffh, A[NH - 2], A[0], Dv[0], dzp, dsd, ds);
+                fwd_keep(F{}, F{}, KH_{}, SH_{}, Ws + L::OFF_H + (l - 1) * H * L::SH, koffh, A[l - 1], A[l], Dv[RELU ? 0 : l], dzf, dsd, ds);
+            fwd_keep(T{}, F{}, KH_{}, SH_{}, Ws + L::OFF_H + (NH - 2) * H * L::SH, koffh, A[NH - 2], A[0], Dv[0], dzf, dsd, ds);
+        }
+        // the last hidden layer's unit from the fp32 dZ of all four waves, then its rounding
+        {
+            float m = 0.0f;
+#pragma unroll
+            for (int jt = 0; jt < HT; ++jt)
+#pragma unroll
+                for (int t = 0; t < 2; ++t)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) m = fmaxf(m, __builtin_fabsf(dzf[jt][t][r]));
+            m = wave_max(m);
+            if (lane == 0) lmx_s[4 * (NH - 1) + wave] = m;
+        }
+        __syncthreads();
+        {
+            const float f = layer_unit(std::integral_constant<int, NH - 1>{}, e_unit);
+#pragma unroll
+            for (int jt = 0; jt < HT; ++jt)
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    dzp[jt][t][0] = pack_h2(dzf[jt][t][0] * f, dzf[jt][t][1] * f);
+                    dzp[jt][t][1] = pack_h2(dzf[jt][t][2] * f, dzf[jt][t][3] * f);
+                }
         }
 
         PHASE(3);
@@ -483,8 +525,9 @@ mlp_backward_f16_gen_kernel(const LnrNetSpec spec, const float* __restrict__ par
                 write_dz_image(dzp);
                 write_x_image_hidden(A[l - 1]);
                 PHASE(4);
-                // dA_{l-1} = W_l^T dZ_l (scaled domain), gated by layer l-1's derivative -> dZ_{l-1}
-                uint32_t dzn[HT][2][2];
+                // dA_{l-1} = W_l^T dZ_l (layer l's unit), gated by layer l-1's derivative -> dZ_{l-1} in fp32, rounded once its unit is known
+                float dznf[HT][2][4];
+                float mq = 0.0f;
                 f16x8 wt[2][KBH];                                          // W^T fragments of row tile it + 1 in flight behind the products of it
 #pragma unroll
                 for (int kb = 0; kb < KBH; ++kb) wt[0][kb] = wt_frag_hidden(Wl, 0, kb);
@@ -503,17 +546,22 @@ mlp_backward_f16_gen_kernel(const LnrNetSpec spec, const float* __restrict__ par
                     }
 #pragma unroll
                     for (int t = 0; t < 2; ++t) {
-                        if constexpr (RELU) {
-                            dzn[it][t][0] = relu_gate(pack_h2(Dq[t][0], Dq[t][1]), A[l - 1][it >> 1][t][2 * (it & 1)]);
-                            dzn[it][t][1] = relu_gate(pack_h2(Dq[t][2], Dq[t][3]), A[l - 1][it >> 1][t][2 * (it & 1) + 1]);
+                        if constexpr (RELU) {                               // the gate: the packed activation is non-zero
+                            const uint32_t a01 = A[l - 1][it >> 1][t][2 * (it & 1)], a23 = A[l - 1][it >> 1][t][2 * (it & 1) + 1];
+                            dznf[it][t][0] = (a01 & 0xFFFFu) ? Dq[t][0] : 0.0f; dznf[it][t][1] = (a01 >> 16) ? Dq[t][1] : 0.0f;
+                            dznf[it][t][2] = (a23 & 0xFFFFu) ? Dq[t][2] : 0.0f; dznf[it][t][3] = (a23 >> 16) ? Dq[t][3] : 0.0f;
                         } else {
                             typedef _Float16 h2 __attribute__((ext_vector_type(2)));
                             const h2 d01 = __builtin_bit_cast(h2, Dv[l - 1][it >> 1][t][2 * (it & 1)]), d23 = __builtin_bit_cast(h2, Dv[l - 1][it >> 1][t][2 * (it & 1) + 1]);
-                            dzn[it][t][0] = pack_h2(Dq[t][0] * (float)d01[0], Dq[t][1] * (float)d01[1]);
-                            dzn[it][t][1] = pack_h2(Dq[t][2] * (float)d23[0], Dq[t][3] * (float)d23[1]);
+                            dznf[it][t][0] = Dq[t][0] * (float)d01[0]; dznf[it][t][1] = Dq[t][1] * (float)d01[1];
+                            dznf[it][t][2] = Dq[t][2] * (float)d23[0]; dznf[it][t][3] = Dq[t][3] * (float)d23[1];
                         }
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) mq = fmaxf(mq, __builtin_fabsf(dznf[it][t][r]));
                     }
                 }
+                mq = wave_max(mq);
+                if (lane == 0) lmx_s[4 * (l - 1) + wave] = mq;              // (read behind the barrier below)
                 PHASE(5);
                 __syncthreads();
                 PHASE(6);
@@ -521,13 +569,19 @@ mlp_backward_f16_gen_kernel(const LnrNetSpec spec, const float* __restrict__ par
                 PHASE(7);
                 __syncthreads();                                           // the images are rewritten by the next layer
                 PHASE(8);
+                const float f = l == 1 ? layer_unit(std::integral_constant<int, 0>{}, u_lay[l])             // (l - 1 as a compile-time index)
+                                       : layer_unit(std::integral_constant<int, NH >= 3 ? 1 : 0>{}, u_lay[l]);
 #pragma unroll
                 for (int jt = 0; jt < HT; ++jt)
 #pragma unroll
-                    for (int t = 0; t < 2; ++t) { dzp[jt][t][0] = dzn[jt][t][0]; dzp[jt][t][1] = dzn[jt][t][1]; }
+                    for (int t = 0; t < 2; ++t) {
+                        dzp[jt][t][0] = pack_h2(dznf[jt][t][0] * f, dznf[jt][t][1] * f);
+                        dzp[jt][t][1] = pack_h2(dznf[jt][t][2] * f, dznf[jt][t][3] * f);
+                    }
             }
         }
         // ---- first layer: its weight gradient and the feature gradient (un-scaled, to the d_feature planes)
+        const float up0 = __uint_as_float(u_lay[0] << 23);                 // layer 0's unit
         write_dz_image(dzp);
         // The features are not kept across the hidden layers (32 registers at the point of highest pressure): they are read again
         // here (L2) for the input image, together with the next step's operands (a static number of loads: the last step re-reads itself)
@@ -611,7 +665,7 @@ mlp_backward_f16_gen_kernel(const LnrNetSpec spec, const float* __restrict__ par
                     }
                     const int64_t m = tile * 32 + 16 * t + c;
                     const float mine = g == 0 ? tot[0] : (g == 1 ? tot[1] : tot[2]);
-                    if (have_tile && m < M && g < 3) d_pts[3 * m + g] = 0.5f * sc_up * mine;          // x = (xyz + 1) / 2
+                    if (have_tile && m < M && g < 3) d_pts[3 * m + g] = 0.5f * up0 * mine;            // x = (xyz + 1) / 2
                 }
             }
         } else
@@ -631,7 +685,7 @@ mlp_backward_f16_gen_kernel(const LnrNetSpec spec, const float* __restrict__ par
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             const int k = 16 * it + 4 * g + r;
-                            if (k < 2 * enc_pairs) st32<float>(dfeat, (uint32_t)k * plane_bytes + (uint32_t)m * 4u, sc_up * Dq[t][r]);
+                            if (k < 2 * enc_pairs) st32<float>(dfeat, (uint32_t)k * plane_bytes + (uint32_t)m * 4u, up0 * Dq[t][r]);
                         }
                     }
                 }
@@ -675,7 +729,7 @@ mlp_backward_f16_gen_kernel(const LnrNetSpec spec, const float* __restrict__ par
     // Written straight from the accumulator layout - 4-byte stores at a row stride per lane, for the fused first layer at scattered
     // feature positions too - the 120 KB slab of the 128 x 2 network took 25 - 30 us per workgroup (profiles/r06_fp16_mlp_phases.txt).
     const int n_mlp = spec.n_mlp_params, in_dim = spec.in_dim;
-    const float unit = __uint_as_float(e_unit << 23);
+    const float unit = __uint_as_float(u_lay[0] << 23);                      // first layer: dZ_0's unit; hidden matrix l: dZ_l's
     float* slab = slabs + (size_t)blockIdx.x * n_mlp;
     float* stg = reinterpret_cast<float*>(img);
     static_assert((size_t)B::IMG_WAVE * sizeof(f16) >= 16u * 32u * KT * sizeof(float) && (size_t)B::IMG_WAVE * sizeof(f16) >= 16u * H * sizeof(float), "a row tile fits the wave's image area");
@@ -705,7 +759,7 @@ mlp_backward_f16_gen_kernel(const LnrNetSpec spec, const float* __restrict__ par
 #pragma unroll
                     for (int kt = 0; kt < HT; ++kt)
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) stg[(4 * g + r) * H + 16 * kt + c] = unit * acch[l][i][kt][r];
+                        for (int r = 0; r < 4; ++r) stg[(4 * g + r) * H + 16 * kt + c] = __uint_as_float(u_lay[l + 1] << 23) * acch[l][i][kt][r];
                     float* dst = slab + H * in_dim + l * H * H + 16 * jt * H;
 #pragma unroll
                     for (int j = 0; j < 16 * H / 64; ++j) dst[64 * j + lane] = stg[64 * j + lane];

@@ -270,3 +270,41 @@ def test_squareplus_and_softplus_carry_tiny_cuda_nn_k_act():
     assert torch.allclose(sq, 0.5 * (y + torch.sqrt(y * y + 4.0)) / 10.0, atol=1e-12)
     assert torch.allclose(torch.autograd.grad(sq.sum(), x)[0], 0.5 * (1.0 + y / torch.sqrt(y * y + 4.0)), atol=1e-12)
     assert abs(float(NW._activate(torch.zeros(1), "Squareplus")) - 0.1) < 1e-7 and abs(float(NW._activate(torch.zeros(1), "Softplus")) - 0.0693147) < 1e-6
+
+
+def test_density_route_helper_restates_the_dispatch():
+    """tests/support.py density_route against launch plans worked out by hand from plan_launch / lnr_wide_class / lnr_f16_supported
+    (LDS bytes in the comments): if the dispatch changes, this and the route assertions of test_gpu_activations.py say so."""
+    from tests.support import ACTIVATION_NAMES, ACTIVATION_ROUTES, density_route, route_of
+    F = lambda nf: dict(otype="Frequency", n_frequencies=nf)
+    Hg = lambda levels, f=2: dict(otype="HashGrid", n_levels=levels, n_features_per_level=f, log2_hashmap_size=12, base_resolution=8)
+    N = lambda H, nh, act="Tanh", prec="fp32": dict(activation=act, n_neurons=H, n_hidden_layers=nh, precision=prec)
+    # the default shape class: bf16x3 (fp32), fp32 chains, the fp16 register kernels; not with another activation
+    assert density_route(Hg(16), N(64, 1, "ReLU"), 1000) == dict(route="bf3")
+    assert density_route(Hg(16), N(64, 1, "ReLU", "fp32_chain"), 1000) == dict(route="fast32")
+    assert density_route(Hg(16), N(64, 1, "ReLU", "fp16"), 1000) == dict(route="f16_fast")
+    assert density_route(Hg(16), N(64, 1, "Tanh"), 1000) == dict(route="regs", w_lds=1)
+    # register-accumulating backward: 64 x 1 all weights in LDS (20 480 + 35 840 B); 128 x 2: scratch 81 920 + hidden 75 776 B; 128 x 3: none
+    assert density_route(F(8), N(64, 1), 1000) == dict(route="regs", w_lds=1)
+    assert density_route(F(8), N(128, 2), 1000) == dict(route="regs", w_lds=2)
+    assert density_route(F(8), N(128, 3), 1000) == dict(route="regs", w_lds=0)
+    assert density_route(F(8), N(128, 3), 1000, backward=False) == dict(route="lds", w_lds=0, waves=4, dw64=0)   # 169 984 B of weights
+    # LDS-accumulating tiers: 64 x 2 over 144 inputs: (1, 4, 1) = 237 568 B ... (1, 2, 0) = 147 456 B; 128 x 1 over 144: weights from L2
+    assert density_route(F(24), N(64, 2), 1000) == dict(route="lds", w_lds=1, waves=2, dw64=0)
+    assert density_route(F(24), N(128, 1), 1000) == dict(route="lds", w_lds=0, waves=4, dw64=0)
+    assert density_route(F(4), N(16, 1), 1000) == dict(route="lds", w_lds=1, waves=4, dw64=1)
+    # 256 neurons: one hidden layer fused (fp32 registers, fp16 general kernels), two or three layer by layer
+    assert density_route(F(6), N(256, 1), 1000) == dict(route="regs", w_lds=1)
+    assert density_route(F(6), N(256, 1, prec="fp16"), 1000) == dict(route="f16_freq", obj=2)
+    assert density_route(F(6), N(256, 3, prec="fp16"), 1000) == dict(route="wide")
+    # fp16: fused frequency kernels up to 12 frequencies, pair planes above; odd feature counts are refused
+    assert density_route(F(12), N(64, 2, "Sine", "fp16"), 1000) == dict(route="f16_freq", obj=None)
+    assert density_route(F(16), N(16, 1, "Softplus", "fp16"), 1000) == dict(route="f16_gen", obj=1)
+    assert density_route(Hg(4), N(128, 3, prec="fp16"), 1000) == dict(route="f16_gen", obj=2)
+    assert density_route(Hg(10, 1), N(16, 1, prec="fp16"), 1000) == dict(route="unsupported")
+    assert density_route(F(24), N(128, 2, prec="fp16"), 1000) == dict(route="unsupported")       # 144 inputs into a 128-wide network
+    # the route table of the activation matrix lands where it says, for every activation but where the compile-time kernels take over
+    for name, (_, _, want) in ACTIVATION_ROUTES.items():
+        for act in ACTIVATION_NAMES:
+            expect = dict(want, obj=None) if ("obj" in want and act in ("ReLU", "Sine")) else want
+            assert route_of(name, act, 2000) == expect, (name, act)
