@@ -377,6 +377,50 @@ int lnr_render_backward(const float* sigma, const float* z, const float* rays, i
 int lnr_points_grad_to_rays(const float* d_pts /*[n,S,3]*/, const float* z, int32_t n_rays,
                             const int32_t* n_rays_dev, int32_t n_samples, float* d_rays, void* stream);
 
+/* ---- meshing (analysis/mesher.py:103-225) ---------------------------------------------------------- */
+/* The lattice of Mesher.get_grid_uniform: n[a] nodes per axis (x, y, z), the np.linspace axes as doubles on the device, the fp32
+ * bounds of the reference's bound check (a 0-dim fp64 tensor does not promote fp32 points: the bound is rounded to fp32 and compared
+ * in fp32) and, for the bucket search, the first node and 1 / spacing of each axis (a guess only: the bucket is then corrected
+ * against the axis values themselves). */
+typedef struct LnrMeshGrid {
+    int32_t n[3];
+    float lo[3], hi[3];
+    double first[3], inv_step[3];
+    const double* axis[3];
+} LnrMeshGrid;
+
+/* Compositing (the arithmetic and noise draws of lnr_render_forward: the same weights, depth and variance bit for bit) fused with the reference's weight volume (mesher.py:143-180),
+ * without writing weights, depths or points.  A ray counts when depth < depth_max (the rendered depth in world-cube units against
+ * ray_range[1] - 0.25 in metres: the reference's comparison, kept) and, with use_var != 0, variance < var_max.  Each of its samples
+ * with w > 0 is placed at o + d z (fp32 multiply, then fp32 add), kept when lo <= p <= hi on every axis (fp32), bucketed per axis as
+ * torch.bucketize against the fp64 axis (smallest i with (double) p <= axis[i]) and lands at flat index x_b nz + y_b nx nz + z_b (the
+ * reference's [y][x][z] order; indices >= nx ny nz are dropped, smaller ones - also those of bucket n on an axis - are kept).
+ * volume [ny*nx*nz] fp32 receives the max of the weights (integer max on the bit patterns: weights are >= 0); the caller zeroes it.
+ * counters (nullable, uint64 [2]) += {samples that reached the volume, atomics issued}. */
+int lnr_render_mesh_accumulate(const float* sigma, const float* z, const float* rays, int32_t n_rays, const int32_t* n_rays_dev,
+                               int32_t n_samples, const float* noise, float noise_std, uint64_t seed, const LnrMeshGrid* grid,
+                               float depth_max, int32_t use_var, float var_max, float* volume, uint64_t* counters, void* stream);
+
+/* Marching cubes over volume [nx][ny][nz] fp32 (all >= 2, nx ny nz < 2^31).  A node is inside when v > level.  A vertex lies on
+ * every lattice edge whose ends differ, owned by the edge's lower node, at t = (level - va) / (vb - va) from it (va at the lower
+ * node); its coordinate along the edge is ((float) index + t) * spacing + origin, the others (float) index * spacing + origin, each
+ * operation rounded on its own in fp32.  Vertex ids follow node order, then axis (x, y, z); triangles follow cell order (a cell is
+ * named by its lower node), then the case table's order.  The case table (256 x LNR_MC_TABLE_WIDTH int8, edge ids, -1 after the
+ * last triangle; edge e = 4 a + q lies along axis a from the q-th corner with bit a clear, corners numbered x + 2 y + 4 z) is
+ * generated from one rule: on a face with its two inside corners diagonal they are separated.  Triangles face lower values.
+ * Two calls: the count pass (per-block vertex and triangle counts, then their exclusive scan; totals_dev uint64 [2] = {V, F}),
+ * then, with the totals read back, the emit pass: verts [V,3] fp32, tris [F,3] int32 (V < 2^30).  lnr_mc_workspace: bytes of the
+ * workspace both calls share. */
+#define LNR_MC_TABLE_WIDTH 16
+size_t lnr_mc_workspace(int32_t nx, int32_t ny, int32_t nz);
+int lnr_mc_count(const float* volume, int32_t nx, int32_t ny, int32_t nz, float level, void* workspace, size_t workspace_bytes,
+                 uint64_t* totals_dev, void* stream);
+int lnr_mc_emit(const float* volume, int32_t nx, int32_t ny, int32_t nz, float level, const float* spacing /*host [3]*/,
+                const float* origin /*host [3]*/, void* workspace, size_t workspace_bytes, int64_t n_verts, int64_t n_tris,
+                float* verts, int32_t* tris, void* stream);
+/* host only: the case table, out [256 * LNR_MC_TABLE_WIDTH] */
+int lnr_mc_case_table(int8_t* out);
+
 /* ---- loss ------------------------------------------------------------------------------------------ */
 /* get_weights_gt (losses.py:29-51); eps_ray [n] per-ray or NULL -> eps_scalar. */
 int lnr_weights_gt(const float* s /*[n,S] metres*/, const float* g /*[n] metres*/, const float* eps_ray,

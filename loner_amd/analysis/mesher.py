@@ -1,0 +1,174 @@
+"""Mesh of a trained map (the reference's analysis/mesher.py:29-225), on HIP.
+
+Mesher.get_mesh renders every `skip_step`-th keyframe pose with a full synthetic LiDAR scan, max-accumulates the rendered weights
+of all samples into a lattice over `marching_cubes_bound` (Model.mesh_accumulate: one kernel composites and accumulates, nothing
+per sample reaches memory), and runs marching cubes on the device (ops.marching_cubes).  Differences from the reference, by intent:
+  * the volume holds the true max of the weights that fall into a voxel; the reference's `results[idx] = torch.max(results[idx], w)`
+    (mesher.py:180) keeps the LAST writer among samples of one chunk that share a voxel;
+  * marching cubes is this project's (include/loner_hip.h, "meshing"), not scikit-image's Lewiner tables: the vertices lie on the same
+    lattice edges at the same interpolated positions, the triangulation of a cell can differ;
+  * the result is a small TriangleMesh (vertices, triangles, vertex normals, .ply output), not an open3d object.
+The reference's quirks are kept: a ray counts when its rendered depth in world-cube units is below ray_range[1] - 0.25 in metres
+(mesher.py:144), the bound check compares in fp32 and the bucketing in fp64, and bucket indices that alias into the next row stay.
+"""
+import numpy as np
+import torch
+
+from .. import ops
+from ..common.pose import Pose
+from ..common.ray_utils import LidarRayDirections
+from ..common.sensors import LidarScan
+
+
+def build_lidar_scan(lidar_intrinsics, device=0):
+    """A full synthetic scan: unit directions over vertical_fov x 360 deg at the given resolutions (mesher.py:29-50)."""
+    vert_fov = lidar_intrinsics["vertical_fov"]
+    vert_res = lidar_intrinsics["vertical_resolution"]
+    hor_res = lidar_intrinsics["horizontal_resolution"]
+    phi = torch.arange(vert_fov[0], vert_fov[1], vert_res).deg2rad()
+    theta = torch.arange(0, 360, hor_res).deg2rad()
+    phi_grid, theta_grid = torch.meshgrid(phi, theta, indexing="ij")
+    phi_grid = torch.pi / 2 - phi_grid.reshape(-1, 1)
+    theta_grid = theta_grid.reshape(-1, 1)
+    x = torch.cos(theta_grid) * torch.sin(phi_grid)
+    y = torch.sin(theta_grid) * torch.sin(phi_grid)
+    z = torch.cos(phi_grid)
+    xyz = torch.hstack((x, y, z))
+    return LidarScan(xyz.T, torch.ones_like(x).flatten(), torch.zeros_like(x).flatten()).to(device)
+
+
+class TriangleMesh:
+    """vertices float64 [V,3] (world frame, metres), triangles int32 [F,3]; what the reference's script uses of open3d's mesh."""
+
+    def __init__(self, vertices, triangles):
+        self.vertices = np.ascontiguousarray(vertices, dtype=np.float64)
+        self.triangles = np.ascontiguousarray(triangles, dtype=np.int32)
+        self.vertex_normals = np.zeros((0, 3), dtype=np.float64)
+
+    def has_vertex_normals(self):
+        return self.vertex_normals.shape[0] == self.vertices.shape[0] and self.vertices.shape[0] > 0
+
+    def compute_vertex_normals(self):
+        """Area-weighted sum of the adjacent triangles' normals, normalised (triangles face lower weights: out of the surface)."""
+        v, t = self.vertices, self.triangles.astype(np.int64)
+        fn = np.cross(v[t[:, 1]] - v[t[:, 0]], v[t[:, 2]] - v[t[:, 0]])
+        n = np.zeros_like(v)
+        for k in range(3):
+            np.add.at(n, t[:, k], fn)
+        norm = np.linalg.norm(n, axis=1, keepdims=True)
+        self.vertex_normals = n / np.where(norm > 0, norm, 1.0)
+        return self
+
+    def write_ply(self, path, binary=True):
+        """PLY with float64 x y z (+ nx ny nz when computed) and int32 vertex_indices lists."""
+        normals = self.has_vertex_normals()
+        props = ["x", "y", "z"] + (["nx", "ny", "nz"] if normals else [])
+        fmt = "binary_little_endian" if binary else "ascii"
+        head = [f"ply", f"format {fmt} 1.0", f"element vertex {self.vertices.shape[0]}"] + [f"property double {p}" for p in props] + \
+            [f"element face {self.triangles.shape[0]}", "property list uchar int vertex_indices", "end_header"]
+        vdata = np.hstack([self.vertices, self.vertex_normals]) if normals else self.vertices
+        with open(path, "wb") as f:
+            f.write(("\n".join(head) + "\n").encode("ascii"))
+            if binary:
+                f.write(np.ascontiguousarray(vdata, dtype="<f8").tobytes())
+                faces = np.zeros(self.triangles.shape[0], dtype=[("n", "u1"), ("i", "<i4", (3,))])
+                faces["n"] = 3
+                faces["i"] = self.triangles
+                f.write(faces.tobytes())
+            else:
+                for row in vdata:
+                    f.write((" ".join(repr(float(x)) for x in row) + "\n").encode("ascii"))
+                for tri in self.triangles:
+                    f.write(f"3 {tri[0]} {tri[1]} {tri[2]}\n".encode("ascii"))
+
+    @staticmethod
+    def read_ply(path):
+        """Reads what write_ply writes (both formats)."""
+        with open(path, "rb") as f:
+            lines = []
+            while True:
+                line = f.readline().decode("ascii").strip()
+                lines.append(line)
+                if line == "end_header":
+                    break
+            nv = int(next(l for l in lines if l.startswith("element vertex")).split()[-1])
+            nf = int(next(l for l in lines if l.startswith("element face")).split()[-1])
+            ncol = sum(1 for l in lines if l.startswith("property double"))
+            if "format binary_little_endian 1.0" in lines:
+                vdata = np.frombuffer(f.read(nv * ncol * 8), dtype="<f8").reshape(nv, ncol)
+                faces = np.frombuffer(f.read(nf * 13), dtype=[("n", "u1"), ("i", "<i4", (3,))])
+                tris = faces["i"].copy()
+            else:
+                rows = f.read().decode("ascii").split("\n")
+                vdata = np.array([[float(x) for x in r.split()] for r in rows[:nv]], dtype=np.float64).reshape(nv, ncol)
+                tris = np.array([[int(x) for x in r.split()[1:4]] for r in rows[nv:nv + nf]], dtype=np.int32).reshape(nf, 3)
+        mesh = TriangleMesh(vdata[:, :3], tris)
+        if ncol == 6:
+            mesh.vertex_normals = vdata[:, 3:6].copy()
+        return mesh
+
+
+class Mesher(object):
+    def __init__(self, model, ckpt, world_cube, ray_range, resolution=0.2, marching_cubes_bound=[[-40, 20], [0, 20], [-3, 15]],
+                 level_set=0, points_batch_size=5000000, lidar_vertical_fov=[-22.5, 22.5]):
+        self.marching_cubes_bound = np.array(marching_cubes_bound)
+        self.world_cube_shift = world_cube.shift.cpu().numpy()
+        self.world_cube_scale_factor = world_cube.scale_factor.cpu().numpy()
+        self.world_cube = world_cube
+        self.model = model
+        self.ckpt = ckpt
+        self.resolution = resolution
+        self.points_batch_size = points_batch_size          # (kept for the signature: the lattice is never materialised as points)
+        self.level_set = level_set
+        self.ray_range = ray_range
+        self.lidar_vertical_fov = lidar_vertical_fov
+
+    def _bound(self):
+        """the lattice's bound in world-cube units, float64 [3,2] (mesher.py:141)"""
+        return (np.array(self.marching_cubes_bound) + np.expand_dims(self.world_cube_shift, 1)) / self.world_cube_scale_factor
+
+    def get_grid_uniform(self, resolution):
+        """{"xyz": [x, y, z]}: the lattice axes of mesher.py:60-90 (np.linspace over the bound in world-cube units).  The reference also
+        returns every lattice point ("grid_points", 1.2 GB at 0.1 m); nothing here needs them."""
+        bound = self._bound()
+        length = self.marching_cubes_bound[:, 1] - self.marching_cubes_bound[:, 0]
+        num = (length / resolution).astype(int)
+        x = np.linspace(bound[0][0], bound[0][1], num[0])
+        y = np.linspace(bound[1][0], bound[1][1], num[1])
+        z = np.linspace(bound[2][0], bound[2][1], num[2])
+        return {"xyz": [x, y, z]}
+
+    def get_volume(self, device, ray_sampler, skip_step=15, var_threshold=None, counters=None):
+        """-> (volume [nx, ny, nz] fp32 on `device`, axes): the reference's `volume` (mesher.py:182-184)."""
+        device = torch.device(device) if not isinstance(device, int) else torch.device("cuda", device)
+        grid = self.get_grid_uniform(self.resolution)
+        lattice = ops.MeshLattice(grid["xyz"], self._bound(), device)
+        nx, ny, nz = lattice.shape
+        results = torch.zeros(ny * nx * nz, device=device, dtype=torch.float32)
+        scan = build_lidar_scan({"vertical_fov": self.lidar_vertical_fov, "vertical_resolution": 0.25, "horizontal_resolution": 0.25},
+                                device)
+        ray_directions = LidarRayDirections(scan)
+        depth_max = float(self.ray_range[1]) - 0.25
+        all_rays = torch.arange(len(ray_directions))
+        for pose_state in self.ckpt["poses"][::skip_step]:
+            lidar_pose = Pose(pose_tensor=pose_state["lidar_pose"]).to(device)
+            # every ray of the scan at once: the reference's 512-ray chunks (fetch_chunk_rays) concatenated
+            rays = ray_directions.build_lidar_rays(all_rays, self.ray_range, self.world_cube, lidar_pose.get_transformation_matrix())[0]
+            self.model.mesh_accumulate(rays, ray_sampler, lattice, results, depth_max, var_threshold, counters=counters)
+        volume = results.view(ny, nx, nz).permute(1, 0, 2).contiguous()
+        return volume, grid["xyz"]
+
+    def get_mesh(self, device, ray_sampler, skip_step=15, var_threshold=None):
+        """TriangleMesh in world coordinates (metres), or None when no surface crosses level_set (mesher.py:103-225)."""
+        with torch.no_grad():
+            volume, xyz = self.get_volume(device, ray_sampler, skip_step, var_threshold)
+            spacing = (xyz[0][2] - xyz[0][1], xyz[1][2] - xyz[1][1], xyz[2][2] - xyz[2][1])
+            verts, faces = ops.marching_cubes(volume, float(self.level_set), spacing=spacing)
+            if faces.shape[0] == 0:
+                print('marching_cubes error. Possibly no surface extracted from the level set.')
+                return None
+            # convert back to world coordinates (mesher.py:214-219), in float64 as numpy does it there
+            vertices = verts.cpu().numpy() + np.array([xyz[0][0], xyz[1][0], xyz[2][0]])
+            vertices *= self.world_cube_scale_factor
+            vertices -= self.world_cube_shift
+            return TriangleMesh(vertices, faces.cpu().numpy())

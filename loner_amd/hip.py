@@ -56,6 +56,13 @@ class LossConfig(C.Structure):
                 ("fixed_eps", C.c_float)]
 
 
+class MeshGrid(C.Structure):
+    _fields_ = [("n", C.c_int32 * 3), ("lo", C.c_float * 3), ("hi", C.c_float * 3), ("first", C.c_double * 3),
+                ("inv_step", C.c_double * 3), ("axis", C.c_void_p * 3)]
+
+
+MC_TABLE_WIDTH = 16          # LNR_MC_TABLE_WIDTH
+
 P = C.c_void_p
 _SIGNATURES = {
     "lnr_last_error": (C.c_char_p, []),
@@ -90,6 +97,13 @@ _SIGNATURES = {
     "lnr_render_backward": (C.c_int, [P, P, P, C.c_int32, P, C.c_int32, P, C.c_float, C.c_uint64, P, P, P, P, P, P, P]),
     "lnr_render_ftb_gather": (C.c_int, [P, P, C.c_int32, P, P, C.c_int32, C.c_int32, C.c_int32, P, P, P, P]),
     "lnr_render_ftb_composite": (C.c_int, [P, P, P, C.c_int32, P, P, C.c_int32, C.c_int32, C.c_int32, P, C.c_float, C.c_uint64, P, P, P, P, P, C.c_int32, P]),
+    "lnr_render_mesh_accumulate": (C.c_int, [P, P, P, C.c_int32, P, C.c_int32, P, C.c_float, C.c_uint64, C.POINTER(MeshGrid),
+                                             C.c_float, C.c_int32, C.c_float, P, P, P]),
+    "lnr_mc_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "lnr_mc_count": (C.c_int, [P, C.c_int32, C.c_int32, C.c_int32, C.c_float, P, C.c_size_t, P, P]),
+    "lnr_mc_emit": (C.c_int, [P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), P, C.c_size_t,
+                              C.c_int64, C.c_int64, P, P, P]),
+    "lnr_mc_case_table": (C.c_int, [P]),
     "lnr_points_grad_to_rays": (C.c_int, [P, P, C.c_int32, P, C.c_int32, P, P]),
     "lnr_weights_gt": (C.c_int, [P, P, P, C.c_float, C.c_int32, C.c_int32, C.c_int32, P, P]),
     "lnr_logits_grad": (C.c_int, [P, P, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, P, P]),

@@ -134,6 +134,79 @@ class Model(nn.Module):
         return {k: (v[0] if len(v) == 1 else torch.cat(v, 0)) for k, v in out.items() if v}
 
     @torch.no_grad()
+    def mesh_accumulate(self, rays, ray_sampler, lattice, volume, depth_max, var_threshold=None, counters=None):
+        """The mesher's weight volume (analysis/mesher.py:137-180) for a batch of rays rendered as forward(testing=False) renders them
+        (N_samples_train, perturb): every sample's weight is max-accumulated into `volume` (ops.mesh_accumulate) in the kernel that
+        composites it - no [N,S] weights, depths or points.  Batching, the sampler-ahead stream, the `draws` parity hook and the order
+        in which seeds are asked of torch's generator are _render_no_grad's, so the same generator state gives the same samples and
+        weights as forward(testing=False).  The loop below restates _render_no_grad's and must change with it: the bit-identity test of
+        tests/test_gpu_mesh.py (forward-fed restatement against this method, one launch and several) fails when the two drift apart."""
+        n_samples, perturb = self._sample_counts(False)
+        rays = rays.detach().float().contiguous()
+        n = rays.shape[0]
+        if n == 0:
+            return volume
+        net = self.nerf_model._model_sigma
+        noise_std = float(self.cfg.render.raw_noise_std)
+        draws = getattr(ray_sampler, "_draws", None)
+        occ = hasattr(ray_sampler, "update_occ_grid")
+        pre = None
+        if draws is not None:
+            u1, u2, nz = [], [], []
+            for lo in range(0, n, self.cfg.render.chunk):
+                m = min(self.cfg.render.chunk, n - lo)
+                if perturb > 0:
+                    u1.append(draws.jitter(m, n_samples // 2 if occ else n_samples))
+                if occ:
+                    u2.append(draws.pdf(m, n_samples // 2))
+                if noise_std > 0:
+                    nz.append(draws.noise(m, n_samples) * noise_std)
+            cat = lambda xs: torch.cat(xs).to(rays.device) if xs else None
+            pre = (cat(u1), cat(u2), cat(nz))
+        step = max(64, self._POINTS_PER_LAUNCH // int(n_samples))
+        ahead = pre is None and rays.is_cuda and n > step
+        if ahead:
+            main = torch.cuda.current_stream(rays.device)
+            streams = self.__dict__.setdefault("_sampler_streams", {})
+            side = streams.get(rays.device)
+            if side is None:
+                side = streams[rays.device] = torch.cuda.Stream(rays.device)
+            side.wait_stream(main)
+
+            def sample_ahead(lo):
+                r_ = rays[lo:lo + step]
+                with torch.cuda.stream(side):
+                    z_ = ray_sampler.get_samples(r_, n_samples, perturb)
+                    ev_ = torch.cuda.Event()
+                    ev_.record(side)
+                return r_, z_, ev_
+            coming = sample_ahead(0)
+        for lo in range(0, n, step):
+            r = rays[lo:lo + step]
+            kw = {}
+            noise = None
+            if pre is not None:
+                if pre[0] is not None:
+                    kw["u_jitter"] = pre[0][lo:lo + step]
+                if pre[1] is not None:
+                    kw["u_pdf"] = pre[1][lo:lo + step]
+                noise = pre[2][lo:lo + step] if pre[2] is not None else None
+            if ahead:
+                r, z, ev = coming
+                seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if noise_std > 0 else 0
+                coming = sample_ahead(lo + step) if lo + step < n else None
+                main.wait_event(ev)
+                z.record_stream(main)
+            else:
+                z = ray_sampler.get_samples(r, n_samples, perturb, **kw)
+                seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if (noise is None and noise_std > 0) else 0
+            sigma = ops.density_forward(net.spec, net.params.detach(), rays=r, z=z, forward_only=True)
+            ops.mesh_accumulate(sigma, z, r, lattice, volume, depth_max, var_threshold, noise=noise, noise_std=noise_std, seed=seed,
+                                counters=counters)
+        self.nerf_model.warn_if_clipped(rays.device)
+        return volume
+
+    @torch.no_grad()
     def render_depth(self, rays, ray_sampler, scale_factor=None, testing=True, front_to_back=None):
         """Rendered depth per ray and nothing else (what compute_l1_depth, renderer_lidar and the meshing consumers read from the
         result dictionary: analysis/compute_l1_depth.py:56-58): the lean form of forward(testing=True, camera=False).

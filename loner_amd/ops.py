@@ -417,6 +417,81 @@ def render_forward(sigma, z, rays, noise=None, noise_std=0.0, seed=0, n_rays_dev
     return depth, weights, opacity, variance
 
 
+class MeshLattice:
+    """The mesher's lattice on a device (include/loner_hip.h: LnrMeshGrid): the three np.linspace axes (fp64, kept alive here) and
+    the bound of the reference's fp32 bound check.  axes: three 1-D float64 arrays; bound: [[lo, hi]] x 3 (float64, world-cube units)."""
+
+    def __init__(self, axes, bound, device):
+        import numpy as np
+        self.axes = [torch.as_tensor(np.asarray(a, dtype=np.float64)).to(device).contiguous() for a in axes]
+        self.shape = tuple(int(a.numel()) for a in self.axes)            # (nx, ny, nz)
+        g = hip.MeshGrid()
+        for i, a in enumerate(axes):
+            a = np.asarray(a, dtype=np.float64)
+            g.n[i] = a.shape[0]
+            g.lo[i] = float(np.float32(bound[i][0]))                     # the 0-dim fp64 bound meets fp32 points: compared in fp32
+            g.hi[i] = float(np.float32(bound[i][1]))
+            g.first[i] = float(a[0])
+            g.inv_step[i] = float(1.0 / (a[1] - a[0])) if a.shape[0] > 1 and a[1] != a[0] else 0.0
+            g.axis[i] = self.axes[i].data_ptr()
+        self.grid = g
+
+    @property
+    def n_nodes(self):
+        return self.shape[0] * self.shape[1] * self.shape[2]
+
+
+def mesh_accumulate(sigma, z, rays, lattice: MeshLattice, volume, depth_max, var_max=None, noise=None, noise_std=0.0, seed=0,
+                    n_rays_dev=None, counters=None):
+    """Renders the rays (lnr_render_forward's arithmetic) and max-accumulates every sample's weight into volume [ny*nx*nz] fp32 (the
+    reference's [y][x][z] order, include/loner_hip.h: lnr_render_mesh_accumulate).  counters: optional int64 [2] += {samples that
+    reached the volume, atomics issued}."""
+    require_device(sigma, z, rays, volume, noise, counters)
+    sigma, z, rays = _f32c(sigma), _f32c(z), _f32c(rays)
+    assert volume.dtype == torch.float32 and volume.is_contiguous() and volume.numel() == lattice.n_nodes
+    assert counters is None or (counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() == 2)
+    n, s = z.shape
+    check(load().lnr_render_mesh_accumulate(_ptr(sigma), _ptr(z), _ptr(rays), n, _ptr(n_rays_dev), s, _ptr(_f32c(noise)), float(noise_std),
+                                            int(seed), C.byref(lattice.grid), float(depth_max), 0 if var_max is None else 1,
+                                            0.0 if var_max is None else float(var_max), _ptr(volume), _ptr(counters), _stream()),
+          "lnr_render_mesh_accumulate")
+    return volume
+
+
+def mc_case_table():
+    """The marching-cubes case table as numpy int8 [256, MC_TABLE_WIDTH] (host: no device needed)."""
+    import numpy as np
+    out = np.empty((256, hip.MC_TABLE_WIDTH), dtype=np.int8)
+    check(load().lnr_mc_case_table(out.ctypes.data_as(C.c_void_p)), "lnr_mc_case_table")
+    return out
+
+
+def marching_cubes(volume, level=0.0, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0)):
+    """Marching cubes of a device volume [nx, ny, nz] at `level` (inside: v > level) -> (verts [V,3] fp32, faces [F,3] int32) on the
+    device; both empty when nothing crosses the level.  Vertex i lies at index * spacing + origin (include/loner_hip.h: lnr_mc_*).
+    One device -> host read of the two totals sizes the outputs."""
+    require_device(volume)
+    vol = _f32c(volume)
+    assert vol.dim() == 3, "marching_cubes: a 3-D volume [nx, ny, nz]"
+    nx, ny, nz = (int(x) for x in vol.shape)
+    dev = vol.device
+    lib = load()
+    ws_bytes = lib.lnr_mc_workspace(nx, ny, nz)
+    ws = torch.empty(max(int(ws_bytes), 1), device=dev, dtype=torch.uint8)
+    totals = torch.empty(2, device=dev, dtype=torch.int64)
+    check(lib.lnr_mc_count(_ptr(vol), nx, ny, nz, float(level), _ptr(ws), int(ws_bytes), _ptr(totals), _stream()), "lnr_mc_count")
+    n_verts, n_tris = (int(x) for x in totals.cpu())
+    if n_verts >= 1 << 30:                          # lnr_mc_emit's limit: refused before the outputs are allocated
+        raise RuntimeError(f"marching_cubes: {n_verts} vertices, the limit is 2^30 - 1")
+    verts = torch.empty(n_verts, 3, device=dev, dtype=torch.float32)
+    faces = torch.empty(n_tris, 3, device=dev, dtype=torch.int32)
+    sp = (C.c_float * 3)(*[float(x) for x in spacing])
+    org = (C.c_float * 3)(*[float(x) for x in origin])
+    check(lib.lnr_mc_emit(_ptr(vol), nx, ny, nz, float(level), sp, org, _ptr(ws), int(ws_bytes), n_verts, n_tris, _ptr(verts), _ptr(faces),
+                          _stream()), "lnr_mc_emit")
+    return verts, faces
+
+
 def render_backward(sigma, z, rays, g_depth, g_weights, g_opacity, g_variance, noise=None, noise_std=0.0, seed=0,
                     n_rays_dev=None):
     require_device(sigma, z, rays)
