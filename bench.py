@@ -12,6 +12,11 @@ step every 10th iteration, synthetic 64x1024 scans of an analytic scene (loner_a
 With N > 1 the SAME 8-keyframe window is sharded over the ranks (keyframe i -> rank i mod N) with an
 RCCL all-reduce of the density gradient per step ("strong" scaling).
 
+A plain run sets up, warms up, times the steps (with the sampled per-kernel events of that region), writes --dump-outputs and
+prints the line.  --full adds what the headline does not need, each outside the timed region: the L1 depth of the trained map,
+an extended run, the other dtype, the north-star network, API-parity mode, the render leg, and (unless --no-cpu-baseline) the CPU
+and torch-ROCm baselines with the matched-quality legs.
+
 Prints ONE JSON line on rank 0 (see README / DESIGN.md for the fields).
 """
 import argparse
@@ -38,15 +43,18 @@ def parse():
                     help="arithmetic of the density network: f32 (default, stricter than the reference; the MLP's products as three-term "
                          "bf16 splits on the bf16 matrix pipe), f16 (the reference's storage types: fp16 features and weights on MFMA, fp32 "
                          "accumulation) or f32_chain (fp32 with exact fma chains on v_mfma_f32_16x16x4_f32: the pre-round-5 kernels, for A/B runs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg outside the headline (train mode, one GPU): L1 depth of the trained map, extended run, other "
+                         "dtype, north-star network, API-parity mode, render leg, CPU / torch-ROCm baselines and matched-quality legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the baselines and the matched-quality legs")
     ap.add_argument("--quick", action="store_true",
-                    help="development: only the timed region and its kernel table (no other-dtype leg, no north-star network leg, no render leg, "
-                         "no extended run, no baselines) - for A/B runs of a kernel")
+                    help="no effect: a run without --full is already only the timed region and its kernel table (kept so that older "
+                         "command lines still parse)")
     ap.add_argument("--profile-every", type=int, default=-1,
                     help="HIP-event timing of the kernels on every N-th iteration of the timed region (0: none - then no roofline / kernels_ms; "
                          "default: every 4th, every 10th from 100 steps on - about ten sampled iterations)")
     ap.add_argument("--mode", choices=["train", "render"], default="train",
-                    help="train (default): the mapping iteration, with the inference leg as a `render` block in the line; "
+                    help="train (default): the mapping iteration (with --full, the inference leg as a `render` block in the line); "
                          "render: only the inference leg (Model.forward(testing=True) over a whole scan), for profiling")
     ap.add_argument("--launch-check", action="store_true",
                     help="only bring the ranks up, check the world size against --gpus, print {n_gpus, ranks} and exit "
@@ -705,7 +713,7 @@ def main():
         return
 
     # quality half of the metric ("at matched L1 depth"): render held-out rays of the first keyframe with the trained
-    # map (Model.forward(testing=True), 2048 samples) and compare with the analytic ranges.  Outside the timed region.
+    # map (Model.forward(testing=True), 2048 samples) and compare with the analytic ranges.  Outside the timed region, --full only.
     from loner_amd.analysis.l1_depth import compute_l1_depth
     from loner_amd.common.ray_utils import LidarRayDirections
 
@@ -715,14 +723,14 @@ def main():
                                     o._ray_sampler, o._world_cube, o._ray_range, o._device, max_rays=max_rays)
         except Exception as e:      # never let the quality probe break the benchmark line
             return f"failed: {e}"
-    l1_depth = l1_of(opt, my_window[0], 4096)
+    l1_depth = l1_of(opt, my_window[0], 4096) if args.full else None
 
     # A longer look at the same loop, OUTSIDE the official timed region (which is whatever --steps asked for; the driver uses 20 steps =
     # ~45 ms, where run-to-run spread is the size of a typical kernel gain): 200 further iterations of the same optimiser, timed the same
     # way, no per-kernel events.  The iteration gets cheaper as the map forms (dead samples produce no gradient records), so this is a
     # companion figure, not a replacement for ms_per_step.
     extended = None
-    if world == 1 and not args.quick:
+    if world == 1 and args.full:
         torch.cuda.synchronize()
         t_e = time.perf_counter()
         opt._do_iterate_optimizer(my_window, [None], optimizer_settings=phase(200))
@@ -733,7 +741,7 @@ def main():
 
     # the other arithmetic mode of the density network, same workload, same step counts (outside the headline's timed region)
     other = None
-    if world == 1 and not args.quick:
+    if world == 1 and args.full:
         try:
             od = "f16" if args.dtype == "f32" else "f32"
             o2, w2 = make_optimizer(od), build_window(args.keyframes)
@@ -754,19 +762,19 @@ def main():
             other = {"error": str(e)}
 
     ns_net = None
-    if world == 1 and not args.quick:
+    if world == 1 and args.full:
         try:
             ns_net = north_star_network_leg(args.keyframes * args.rays, args.samples, "cuda")
         except Exception as e:
             ns_net = {"error": str(e)}
     api_mode = None
-    if world == 1 and not args.quick:
+    if world == 1 and args.full:
         try:
             api_mode = api_parity_leg(args, local, iters=min(max(args.steps, 1), 20), warmup=3)
         except Exception as e:
             api_mode = {"error": str(e)}
     render = None
-    if world == 1 and not args.quick:
+    if world == 1 and args.full:
         try:
             render = render_leg(opt, my_window[0], scans=2, dtype=args.dtype)
         except Exception as e:
@@ -877,8 +885,8 @@ def main():
             "timed_region": "inputs resident in HBM (scans uploaded once per keyframe before the loop); no host sync inside the loop",
         },
     }
-    print(json.dumps({k: v for k, v in line.items() if k != "cpu_baseline"}), file=sys.stderr, flush=True)   # progress copy
-    if world == 1 and not args.no_cpu_baseline and not args.quick:
+    if world == 1 and args.full and not args.no_cpu_baseline:
+        print(json.dumps(line), file=sys.stderr, flush=True)          # progress copy: the legs below take minutes
         # baseline legs on the SAME workload, each bounded; then the HIP path's L1 after the same number of iterations as the CPU leg
         # BASELINE.md section 3 planned os.cpu_count() threads; torch's CPU ops on [4096,512] tensors do not scale that far on a 256-core
         # host, so the thread count is MEASURED: one iteration each at 16 / 64 / all cores, the fastest count runs the bounded sample

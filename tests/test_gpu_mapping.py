@@ -1075,6 +1075,29 @@ def test_training_with_the_in_kernel_generator_reaches_the_oracles_l1_distributi
     assert abs(h.mean() - o.mean()) < max(pooled, 0.03 * o.mean()), (h.mean(), o.mean(), pooled)
 
 
+def test_plain_bench_run_reports_the_timed_steps_and_runs_no_other_leg():
+    """`python bench.py --gpus 1` without --full: the headline fields and the timed region's kernel table, and none of the legs that
+    --full adds (they run for minutes outside the timed region)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "8", "--warmup", "2"], env=env,
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["metric"] == "training rays/sec" and line["unit"] == "rays/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f32" and line["steps"] == 8 and line["value"] > 0 and line["ms_per_step"] > 0 and line["kernels_ms"]
+    for k in ("l1_depth_m", "extended_run", "other_dtype", "north_star_network", "api_parity_mode", "render"):
+        assert line[k] is None, k
+    for k in ("cpu_baseline", "torch_rocm_baseline", "matched_quality"):
+        assert k not in line, k
+
+
 @pytest.mark.parametrize("pipeline", [True, False])
 def test_overwrite_gradient_mode_changes_nothing(pipeline):
     """LNR_BWD_OVERWRITE_GRAD: the training loop lets the table-gradient reduce and the weight-gradient fold STORE the gradient (no read
