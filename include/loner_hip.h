@@ -421,6 +421,57 @@ int lnr_mc_emit(const float* volume, int32_t nx, int32_t ny, int32_t nz, float l
 /* host only: the case table, out [256 * LNR_MC_TABLE_WIDTH] */
 int lnr_mc_case_table(int8_t* out);
 
+/* ---- point clouds (analysis/renderer_lidar.py:71-91, :296-349; analysis/evaluate_lidar_map.py:16-98) ----------------------- */
+/* Points are fp64 [n,3] (x y z per point), n <= 2^31 - 4096 per call (LNR_ERR_INVALID_ARG beyond).  Every fp64 expression rounds
+ * operation by operation (no fma), divides and square roots are IEEE.  Calls that sort take a caller-owned workspace of
+ * lnr_cloud_workspace(n) bytes (about 36 n: keys, indices and scan space for n points; 0 = n out of range). */
+size_t lnr_cloud_workspace(int64_t n_points);
+
+/* Scan points of one rendered pose (renderer_lidar.py:83-91).  Ray i (i < n_rays) was rendered with depth[i] and variance[i]
+ * (Model.forward(testing=True, return_variance=True)) along scan direction ray_index[i] (directions: the scan's [3, n_directions]
+ * fp32 sensor-frame directions).  With d = fp32(depth * scale) and v = fp32(variance * scale) it is kept when v < var_max and
+ * d < depth_max (fp32 compares: NaN is dropped); its point is fp32(dir_a * d) per axis, widened to fp64.  points [n_rays,3]
+ * receives the kept points in ray order, n_points_dev (int32 [1]) their count; the count stays on the device. */
+int lnr_lidar_scan_points(const float* depth, const float* variance, const int64_t* ray_index, int64_t n_rays,
+                          const float* directions, int64_t n_directions, float scale, float var_max, float depth_max,
+                          void* workspace, size_t workspace_bytes, double* points, int32_t* n_points_dev, void* stream);
+
+/* open3d's legacy PointCloud::VoxelDownSample (as called by renderer_lidar.py:342,348 and evaluate_lidar_map.py:20-21), with a
+ * defined order.  n_points_dev (nullable): the live count (<= n_points) is read on the device.  voxel_size finite and > 0.
+ * lo = min - 0.5 v and hi = max + 0.5 v per axis; v * INT_MAX < max_a(hi_a - lo_a) is open3d's "voxel_size is too small".  A point's
+ * voxel is floor((p_a - lo_a) / v) per axis; the key packs the three indices with ceil(log2(voxels on the axis)) bits each (x highest,
+ * z lowest), at most 64 bits in all.  Each occupied voxel gives one point, the fp64 sum of its points in input order divided by
+ * (double) count; out [n_points,3] receives them in ascending (i_x, i_y, i_z) order.
+ * info_dev int64 [8], written by the call: {status, points out, non-finite input points, key bits, edge (fp64 bits), voxels on x, y, z};
+ * status bit 1: non-finite input (nothing is written), 2: voxel_size too small, 4: key wider than 64 bits.  One host read of info_dev
+ * gives the outcome and the output count. */
+int lnr_voxel_down_sample(const double* points, int64_t n_points, const int32_t* n_points_dev, double voxel_size,
+                          void* workspace, size_t workspace_bytes, double* out, int64_t* info_dev, void* stream);
+
+/* open3d's PointCloud::Transform with an affine T (renderer_lidar.py:304,341): transform host [12] fp64, the top three rows of T
+ * (row-major); dst_i = ((T_i0 x + T_i1 y) + T_i2 z) + T_i3 for each row i.  dst may equal src (in place) or be the tail of a merged
+ * cloud (the append of merge_o3d_pc, renderer_lidar.py:61-67). */
+int lnr_cloud_append_transformed(const double* src, int64_t n_points, const double* transform, double* dst, void* stream);
+
+/* The search structure of compute_point_cloud_distance (evaluate_lidar_map.py:59-60: open3d's KDTreeFlann over the target cloud):
+ * a grid of cubic cells over the targets, origin at their minimum, the targets sorted by cell.  cell_edge <= 0: the default
+ * edge cbrt(e_x e_y e_z / n) with every extent e_a raised to at least 2^-10 of the largest (1 when all targets coincide).  The edge
+ * is doubled until the key fits 63 bits; the distances do not depend on it.  grid: lnr_nn_grid_bytes(n) bytes, kept by the caller
+ * for any number of lnr_nn_distance calls.  info_dev int64 [8] as lnr_voxel_down_sample's ({status, occupied cells, non-finite
+ * targets, key bits, edge, cells on x, y, z}); status bit 1: a non-finite target (the grid is unusable). */
+size_t lnr_nn_grid_bytes(int64_t n_targets);
+int lnr_nn_grid_build(const double* targets, int64_t n_targets, double cell_edge, void* workspace, size_t workspace_bytes,
+                      void* grid, size_t grid_bytes, int64_t* info_dev, void* stream);
+
+/* PointCloud::ComputePointCloudDistance: for every query the distance to its nearest target, exactly.  d2 = (dx*dx + dy*dy) + dz*dz
+ * (d = q - t per axis), minimised over all targets; distance = sqrt(d2) (correctly rounded); sq_distance (nullable) receives d2.  With
+ * no target every distance is 0 (open3d: SearchKNN finds nothing).  A query visits Chebyshev shells of cells around its own and stops
+ * once its best d2 lies below a rounding-safe lower bound on every unvisited cell; queries still open after 5 shells take an exact
+ * pass over all targets.  A non-finite query gets NaN.  workspace: lnr_cloud_workspace(n_queries) bytes.
+ * counters_dev int64 [4], written by the call: {queries that took the exact pass, non-finite queries, shells visited, 0}. */
+int lnr_nn_distance(const void* grid, int64_t n_targets, const double* queries, int64_t n_queries, double* distance,
+                    double* sq_distance, void* workspace, size_t workspace_bytes, int64_t* counters_dev, void* stream);
+
 /* ---- loss ------------------------------------------------------------------------------------------ */
 /* get_weights_gt (losses.py:29-51); eps_ray [n] per-ray or NULL -> eps_scalar. */
 int lnr_weights_gt(const float* s /*[n,S] metres*/, const float* g /*[n] metres*/, const float* eps_ray,

@@ -1,0 +1,268 @@
+"""Rendered LiDAR maps and their accuracy / completion / F-score (the reference's analysis/renderer_lidar.py and
+analysis/evaluate_lidar_map.py::compare_point_clouds), on HIP and without open3d.
+
+LidarMapRenderer renders a dense synthetic scan from keyframe poses through Model.forward(testing=True, return_variance=True),
+keeps the confident rays (ops.lidar_scan_points), voxel-down-samples each scan in the sensor frame, moves it to the world frame
+while appending it to the merged cloud (ops.cloud_transform) and down-samples the merged cloud once more (renderer_lidar.py:71-91,
+:296-349).  compare_point_clouds down-samples both clouds and takes exact nearest-neighbour distances both ways on the device
+(ops.NNGrid) before deriving the reference's statistics (evaluate_lidar_map.py:58-80).  Differences from the reference, by intent:
+  * no ICP refinement of the alignment (evaluate_lidar_map.py:23-53) and no est_align.pcd / gt_align.pcd in the working directory;
+  * voxel_down_sample returns its voxels in ascending (i_x, i_y, i_z) order; open3d's order is its hash map's;
+  * a ray the cube test drops gives no point (the reference would fail to assign a shorter chunk into its fixed slice);
+  * an empty cloud after down-sampling raises ValueError (the reference divides by zero), and the statistics are returned.
+"""
+import os
+
+import numpy as np
+import torch
+
+from .. import ops
+from ..common.pose import Pose
+from ..common.ray_utils import device_scan, mapping_device
+from .mesher import build_lidar_scan
+
+
+def _device(device):
+    if device is None:
+        return mapping_device()
+    return torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+
+
+class PointCloud:
+    """fp64 points [n,3] on the HIP device; the part of open3d's PointCloud the evaluation uses."""
+
+    def __init__(self, points=None, device=None):
+        pts = torch.zeros(0, 3, dtype=torch.float64) if points is None else points
+        pts = pts if torch.is_tensor(pts) else torch.from_numpy(np.asarray(pts, dtype=np.float64))
+        if pts.dim() != 2 or pts.shape[1] != 3:
+            raise ValueError(f"PointCloud: points [n,3], got {tuple(pts.shape)}")
+        dev = pts.device if device is None and pts.is_cuda else _device(device)
+        self.points = pts.to(device=dev, dtype=torch.float64).contiguous()
+
+    def __len__(self):
+        return int(self.points.shape[0])
+
+    def numpy(self):
+        return self.points.cpu().numpy()
+
+    def voxel_down_sample(self, voxel_size):
+        """A new cloud: one point per occupied voxel, the mean of its points, in ascending voxel order (include/loner_hip.h:
+        lnr_voxel_down_sample)."""
+        return PointCloud(ops.voxel_down_sample(self.points, voxel_size))
+
+    def transform(self, T):
+        """Applies the 4x4 affine T (widened to fp64) in place and returns self, as open3d does."""
+        ops.cloud_transform(self.points, T, out=self.points)
+        return self
+
+    def compute_point_cloud_distance(self, target, cell_edge=None, stats=None):
+        """numpy fp64 [n]: for every point the exact distance to its nearest point of `target` (0 when target is empty).
+        cell_edge: the search grid's cell edge (None: the default rule; the distances do not depend on it); stats: an optional
+        dict that receives the search's counters."""
+        grid = ops.NNGrid(target.points.to(self.points.device), cell_edge)
+        return grid.distance(self.points, stats=stats).cpu().numpy()
+
+
+# ---------------------------------------------------------------- PCD v0.7
+_PCD_TYPES = {("F", 4): "<f4", ("F", 8): "<f8", ("I", 1): "i1", ("I", 2): "<i2", ("I", 4): "<i4", ("I", 8): "<i8", ("U", 1): "u1",
+              ("U", 2): "<u2", ("U", 4): "<u4", ("U", 8): "<u8"}
+
+
+def read_point_cloud(path, device=None):
+    """A PointCloud from a PCD v0.7 file (ascii or binary) whose x y z fields are F4 or F8; other fields are skipped."""
+    return PointCloud(read_pcd(path), device)
+
+
+def read_pcd(path):
+    """float64 [n,3]: the x y z fields of a PCD v0.7 file (read_point_cloud without the device)."""
+    with open(path, "rb") as f:
+        head = {}
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError(f"{path}: PCD header without DATA")
+            line = line.decode("ascii", "replace").strip()
+            if not line or line.startswith("#"):
+                continue
+            key, _, rest = line.partition(" ")
+            head[key.upper()] = rest.split()
+            if key.upper() == "DATA":
+                break
+        body = f.read()
+    fields = head["FIELDS"]
+    sizes = [int(s) for s in head.get("SIZE", ["4"] * len(fields))]
+    types = head.get("TYPE", ["F"] * len(fields))
+    counts = [int(c) for c in head.get("COUNT", ["1"] * len(fields))]
+    n = int(head["POINTS"][0]) if "POINTS" in head else int(head["WIDTH"][0]) * int(head.get("HEIGHT", ["1"])[0])
+    data = head["DATA"][0].lower()
+    for a in "xyz":
+        if a not in fields:
+            raise ValueError(f"{path}: no {a} field")
+        k = fields.index(a)
+        if types[k] != "F" or sizes[k] not in (4, 8) or counts[k] != 1:
+            raise ValueError(f"{path}: field {a} is {types[k]}{sizes[k]} x {counts[k]}; x y z must be F4 or F8")
+    if data == "binary_compressed":
+        raise ValueError(f"{path}: PCD DATA binary_compressed is not supported (ascii and binary are)")
+    if data == "binary":
+        dt = np.dtype([(f"f{k}", _PCD_TYPES[(t, s)], (c,)) for k, (t, s, c) in enumerate(zip(types, sizes, counts))])
+        rec = np.frombuffer(body[:n * dt.itemsize], dtype=dt, count=n)
+        pts = np.stack([rec[f"f{fields.index(a)}"][:, 0].astype(np.float64) for a in "xyz"], axis=1)
+    elif data == "ascii":
+        col = np.cumsum([0] + counts)
+        rows = [r.split() for r in body.decode("ascii").splitlines() if r.strip()][:n]
+        pts = np.empty((len(rows), 3), dtype=np.float64)
+        for j, a in enumerate("xyz"):
+            k = fields.index(a)
+            v = np.array([float(r[col[k]]) for r in rows], dtype=np.float64)
+            pts[:, j] = v.astype(np.float32).astype(np.float64) if sizes[k] == 4 else v
+    else:
+        raise ValueError(f"{path}: unknown PCD DATA {data!r}")
+    return pts.reshape(-1, 3)
+
+
+def write_point_cloud(path, cloud, write_ascii=False):
+    """PCD v0.7 with x y z as F4 (the fields and type open3d writes for a cloud without colours or normals)."""
+    pts = cloud.numpy() if isinstance(cloud, PointCloud) else np.asarray(cloud, dtype=np.float64).reshape(-1, 3)
+    pts = pts.astype(np.float32)
+    n = pts.shape[0]
+    head = ["# .PCD v0.7 - Point Cloud Data file format", "VERSION 0.7", "FIELDS x y z", "SIZE 4 4 4", "TYPE F F F", "COUNT 1 1 1",
+            f"WIDTH {n}", "HEIGHT 1", "VIEWPOINT 0 0 0 1 0 0 0", f"POINTS {n}", f"DATA {'ascii' if write_ascii else 'binary'}"]
+    with open(path, "wb") as f:
+        f.write(("\n".join(head) + "\n").encode("ascii"))
+        if write_ascii:
+            f.write("".join(f"{x!r} {y!r} {z!r}\n" for x, y, z in pts.astype(np.float64).tolist()).encode("ascii"))
+        else:
+            f.write(np.ascontiguousarray(pts, dtype="<f4").tobytes())
+    return True
+
+
+# ---------------------------------------------------------------- rendering
+class LidarMapRenderer:
+    """The reference's renderer_lidar.py as a class in Mesher's pattern: render_scan (sensor frame) and render_map (world frame,
+    metres, merged over keyframe poses)."""
+
+    def __init__(self, model, ckpt, world_cube, ray_range, lidar_vertical_fov=[-22.5, 22.5], resolution=0.1):
+        self.model = model
+        self.ckpt = ckpt
+        self.world_cube = world_cube
+        self.ray_range = ray_range
+        self.lidar_vertical_fov = lidar_vertical_fov
+        self.resolution = resolution
+        self._scans = {}
+
+    def _scan(self, device):
+        scan = self._scans.get(str(device))
+        if scan is None:
+            scan = self._scans[str(device)] = build_lidar_scan({"vertical_fov": self.lidar_vertical_fov, "vertical_resolution": self.resolution,
+                                                                "horizontal_resolution": self.resolution}, device)
+        return scan
+
+    def scan_rays(self, lidar_pose, device=None):
+        """-> (rays [m,13] of the rays the cube test keeps, their scan indices int64 [m], the scan's directions [3,N] fp32), all on
+        the device: the input of render_scan's one Model.forward call."""
+        dev = _device(device)
+        dirs, dist = device_scan(self._scan(dev), dev)
+        T = lidar_pose.get_transformation_matrix() if isinstance(lidar_pose, Pose) else torch.as_tensor(lidar_pose)
+        T12 = T.detach()[:3, :4].to(device=dev, dtype=torch.float32).contiguous().reshape(12)
+        rr = [float(self.ray_range[0]), float(self.ray_range[1])]
+        shift = self.world_cube.shift.detach().cpu().reshape(-1).tolist()
+        index = torch.arange(dirs.shape[1], device=dev, dtype=torch.int64)
+        rays, _, keep = ops.build_lidar_rays(dirs, dist, index, T12, rr, float(self.world_cube.scale_factor), shift)
+        if rays.shape[0] and bool((rays[0, :3].abs() > 1).any()):
+            raise AssertionError("ray origins are outside the world cube")
+        kept = keep.bool().nonzero().squeeze(1)
+        return rays[kept], kept, dirs
+
+    def _thresholds(self, var_threshold):
+        """fp32 (scale, variance bound, depth bound): the reference's fp32 products and compares (renderer_lidar.py:83-88)"""
+        scale = float(np.float32(float(self.world_cube.scale_factor)))
+        return scale, float(np.float32(var_threshold)), float(np.float32(float(self.ray_range[1]) - 0.25))
+
+    def _scan_points(self, lidar_pose, ray_sampler, var_threshold, device=None):
+        rays, kept, dirs = self.scan_rays(lidar_pose, device)
+        scale, var_max, depth_max = self._thresholds(var_threshold)
+        if rays.shape[0] == 0:
+            return torch.zeros(0, 3, device=dirs.device, dtype=torch.float64), torch.zeros(1, device=dirs.device, dtype=torch.int32)
+        with torch.no_grad():
+            out = self.model(rays, ray_sampler, self.world_cube.scale_factor, testing=True, return_variance=True, camera=False)
+        return ops.lidar_scan_points(out["depth_fine"], out["variance"], kept, dirs, scale, var_max, depth_max)
+
+    def render_scan(self, lidar_pose, ray_sampler, var_threshold=1e-2, device=None):
+        """PointCloud of one pose in the sensor frame (metres): the kept rays' points in ray order (renderer_lidar.py:71-91)."""
+        pts, count = self._scan_points(lidar_pose, ray_sampler, var_threshold, device)
+        return PointCloud(pts[:int(count.item())])
+
+    def render_map(self, device, ray_sampler, voxel_size, skip_step=5, var_threshold=1e-2, use_gt_poses=False, only_last_frame=False):
+        """PointCloud of the map in the world frame (metres): every selected pose's scan, down-sampled in the sensor frame, transformed
+        and merged in pose order, then down-sampled once more (renderer_lidar.py:278-290, :296-349).  voxel_size None: no
+        down-sampling, as in the reference."""
+        dev = _device(device)
+        poses = self.ckpt["poses"]
+        selected = [poses[-1]] if only_last_frame else poses[::skip_step]
+        key = "gt_lidar_pose" if use_gt_poses else "lidar_pose"
+        merged = torch.empty(0, 3, device=dev, dtype=torch.float64)
+        total = 0
+        for pose_state in selected:
+            lidar_pose = Pose(pose_tensor=pose_state[key]).to(dev) if isinstance(pose_state, dict) else Pose(pose_state).to(dev)
+            pts, count = self._scan_points(lidar_pose, ray_sampler, var_threshold, dev)
+            scan = ops.voxel_down_sample(pts, voxel_size, count) if voxel_size is not None else pts[:int(count.item())]
+            k = scan.shape[0]
+            if total + k > merged.shape[0]:
+                grown = torch.empty(max(2 * merged.shape[0], total + k), 3, device=dev, dtype=torch.float64)
+                grown[:total] = merged[:total]
+                merged = grown
+            ops.cloud_transform(scan, lidar_pose.get_transformation_matrix(), out=merged[total:total + k])
+            total += k
+        cloud = PointCloud(merged[:total])
+        return cloud.voxel_down_sample(voxel_size) if voxel_size is not None else cloud
+
+
+# ---------------------------------------------------------------- evaluation
+def compare_point_clouds(est_scan, gt_scan, output_dir, f_score_threshold, voxel_size=0.05, write_pointclouds=False,
+                         write_gt_cloud=False, id_str=None):
+    """Accuracy, completion, Chamfer distance, precision, recall and F-score of est_scan against gt_scan after down-sampling both
+    (evaluate_lidar_map.py:16-98 without the ICP refinement).  Writes {output_dir}/metrics/statistics{_id}.yaml and, when asked,
+    lidar_renders/rendered{_id}.pcd and gt{_id}.pcd; returns the statistics.  Quirks kept: precision = TP / len(accuracy), recall =
+    TP / (TP + FN) with TP counted on the estimate and FN on the ground truth, and 1e-8 in the F-score's denominator."""
+    import yaml
+    print("Downsampling clouds to voxel size", voxel_size)
+    est_scan = est_scan.voxel_down_sample(voxel_size)
+    gt_scan = gt_scan.voxel_down_sample(voxel_size)
+    if len(est_scan) == 0 or len(gt_scan) == 0:
+        raise ValueError(f"compare_point_clouds: {len(est_scan)} estimated and {len(gt_scan)} ground-truth points after down-sampling")
+    print("Computing metrics")
+    edge = 2.0 * voxel_size          # a cell then meets at most 27 occupied voxels of either cloud
+    accuracy = est_scan.compute_point_cloud_distance(gt_scan, cell_edge=edge)
+    completion = gt_scan.compute_point_cloud_distance(est_scan, cell_edge=edge)
+    chamfer_distance = accuracy.mean() + completion.mean()
+
+    false_negatives = (completion > f_score_threshold).sum().item()
+    false_positives = (accuracy > f_score_threshold).sum().item()
+    true_positives = (len(accuracy) - false_positives)
+
+    precision = true_positives / (true_positives + false_positives)
+    recall = true_positives / (true_positives + false_negatives)
+    f_score = 2 * (precision * recall) / (precision + recall + 1e-8)
+
+    stats = {
+        "accuracy": accuracy.mean().item(),
+        "completion": completion.mean().item(),
+        "chamfer_distance": chamfer_distance.item(),
+        "recall": recall,
+        "precision": precision,
+        "f-score": f_score,
+        "num_points": len(accuracy)
+    }
+
+    metrics_dir = f"{output_dir}/metrics"
+    os.makedirs(metrics_dir, exist_ok=True)
+    id_suffix = f"_{id_str}" if id_str is not None else ""
+    if write_pointclouds:
+        renders_dir = f"{output_dir}/lidar_renders/"
+        os.makedirs(renders_dir, exist_ok=True)
+        write_point_cloud(f"{renders_dir}/rendered{id_suffix}.pcd", est_scan)
+        if write_gt_cloud:
+            write_point_cloud(f"{renders_dir}/gt{id_suffix}.pcd", gt_scan)
+    with open(f"{metrics_dir}/statistics{id_suffix}.yaml", 'w+') as yaml_stats_f:
+        yaml.dump(stats, yaml_stats_f, indent=2)
+    return stats

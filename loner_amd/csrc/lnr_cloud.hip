@@ -1,0 +1,796 @@
+// Point clouds of a rendered map (gfx950): scan points, voxel down-sampling, the rigid transform of a merged scan, and exact
+// nearest-neighbour distances between two clouds.
+//
+// Replaces the open3d calls of analysis/renderer_lidar.py:71-91, :296-349 and analysis/evaluate_lidar_map.py:16-98:
+//   PointCloud.voxel_down_sample, PointCloud.transform, PointCloud.compute_point_cloud_distance
+// with the definitions stated in include/loner_hip.h ("point clouds").  This file is compiled with -ffp-contract=off (build.py EXACT):
+// every fp64 expression below rounds operation by operation, as the numpy restatement (tests/cloud_restatement.py) does; the divides
+// and square roots are IEEE (no fast-math).
+//
+// Everything is built from one device-wide stable sort of (uint64 key, uint32 index) pairs:
+//   bound      per-block min / max of the finite points and a count of the others, then one workgroup folds them into the
+//              parameters of the call (origin, edge, bits per axis, digit passes, status) in device memory
+//   key        per point: the packed cell index (x highest, z lowest), only as many bits as the bound needs
+//   sort       LSD radix, 8-bit digits: count (per-block histograms), exclusive scan of the [digit][block] table, stable scatter
+//              (rank within a 256-element chunk from eight ballots per wave).  All 8 passes are enqueued; those the key does not
+//              need return at once (the pass count is on the device, the host never waits for it)
+//   segments   heads (key differs from its predecessor), their exclusive scan and the start of each run
+//   voxel      one thread per occupied voxel sums its points in input order (the sort is stable) and divides by the count
+//   grid       the targets gathered in key order, one (key, start) per occupied cell
+// The nearest-neighbour query walks Chebyshev shells of cells around the query's cell and stops when its best squared distance is
+// below a rounding-safe lower bound on every unvisited cell; queries still open after NN_MAX_SHELL shells stream every target
+// through LDS.
+#include "lnr_common.h"
+
+#include <math.h>
+
+#define CL_BLOCK 256
+#define CL_SCAN_PER_THREAD 8
+#define CL_SCAN_TILE (CL_BLOCK * CL_SCAN_PER_THREAD)
+#define CL_SORT_TILE (CL_BLOCK * 16)
+#define CL_RADIX 256
+#define CL_MAX_PASSES 8
+#define CL_BOUND_BLOCKS 1024
+#define NN_MAX_SHELL 4
+#define NN_FB_TILE 1024
+
+enum { CL_MODE_VOXEL = 0, CL_MODE_GRID = 1 };
+enum { CL_ST_NONFINITE = 1, CL_ST_TOO_SMALL = 2, CL_ST_TOO_WIDE = 4 };
+
+// The parameters of one call, computed on the device.  For a grid they stay at the head of the grid buffer for its queries.
+struct CloudParams {
+    double origin[3];
+    double edge;
+    double lo[3], hi[3];            // min / max of the finite points
+    int64_t dims[3];                // cells per axis (largest index + 1)
+    uint32_t shift[3];              // key = ix << shift[0] | iy << shift[1] | iz
+    uint32_t bits;                  // sum of the per-axis bit lengths
+    int32_t npasses;                // digit passes the sort runs
+    uint32_t status;                // CL_ST_*
+    uint32_t n;                     // points the call works on (0 after an error)
+    uint32_t n_seg;                 // occupied voxels / cells
+    unsigned long long nonfinite;
+};
+
+namespace {
+
+__device__ inline uint32_t live_count(const int32_t* n_dev, uint32_t n_cap) {
+    if (!n_dev) return n_cap;
+    const int32_t v = *n_dev;
+    return v < 0 ? 0u : ((uint32_t)v < n_cap ? (uint32_t)v : n_cap);
+}
+
+__device__ inline bool finite3(double x, double y, double z) { return isfinite(x) && isfinite(y) && isfinite(z); }
+
+// exclusive prefix of v over a 256-thread block; *total gets the block's sum.  lds: 4 words.
+__device__ inline uint32_t block_exclusive_scan(uint32_t v, uint32_t* lds, uint32_t* total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t x = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t y = __shfl_up(x, o, 64);
+        if (lane >= o) x += y;
+    }
+    if (lane == 63) lds[w] = x;
+    __syncthreads();
+    uint32_t pre = 0, tot = 0;
+#pragma unroll
+    for (int k = 0; k < CL_BLOCK / 64; ++k) {
+        const uint32_t s = lds[k];
+        pre += k < w ? s : 0u;
+        tot += s;
+    }
+    __syncthreads();
+    *total = tot;
+    return pre + x - v;
+}
+
+// ------------------------------------------------------------------------------------------------ device-wide exclusive scan (uint32)
+// In place over a[0, L).  guard (nullable): the kernels return at once when pass >= *guard (a radix pass the key does not need).
+__global__ __launch_bounds__(CL_BLOCK) void scan_tile_sums(const uint32_t* __restrict__ a, uint32_t L, uint32_t* __restrict__ sums,
+                                                           const int32_t* guard, int pass) {
+    if (guard && pass >= *guard) return;
+    __shared__ uint32_t lds[CL_BLOCK / 64];
+    const uint64_t base = (uint64_t)blockIdx.x * CL_SCAN_TILE + (uint64_t)threadIdx.x * CL_SCAN_PER_THREAD;
+    uint32_t s = 0;
+#pragma unroll
+    for (int k = 0; k < CL_SCAN_PER_THREAD; ++k) s += base + k < L ? a[base + k] : 0u;
+    uint32_t tot;
+    block_exclusive_scan(s, lds, &tot);
+    if (threadIdx.x == 0) sums[blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(CL_BLOCK) void scan_block_sums(uint32_t* __restrict__ sums, uint32_t n_tiles, uint32_t* total,
+                                                            const int32_t* guard, int pass) {
+    if (guard && pass >= *guard) return;
+    __shared__ uint32_t lds[CL_BLOCK / 64];
+    uint32_t carry = 0;
+    for (uint32_t c0 = 0; c0 < n_tiles; c0 += CL_BLOCK) {
+        const uint32_t b = c0 + threadIdx.x;
+        const uint32_t v = b < n_tiles ? sums[b] : 0u;
+        uint32_t tot;
+        const uint32_t ex = block_exclusive_scan(v, lds, &tot);
+        if (b < n_tiles) sums[b] = carry + ex;
+        carry += tot;
+    }
+    if (total && threadIdx.x == 0) *total = carry;
+}
+
+__global__ __launch_bounds__(CL_BLOCK) void scan_tile_apply(uint32_t* __restrict__ a, uint32_t L, const uint32_t* __restrict__ sums,
+                                                            const int32_t* guard, int pass) {
+    if (guard && pass >= *guard) return;
+    __shared__ uint32_t lds[CL_BLOCK / 64];
+    const uint64_t base = (uint64_t)blockIdx.x * CL_SCAN_TILE + (uint64_t)threadIdx.x * CL_SCAN_PER_THREAD;
+    uint32_t v[CL_SCAN_PER_THREAD], s = 0;
+#pragma unroll
+    for (int k = 0; k < CL_SCAN_PER_THREAD; ++k) {
+        v[k] = base + k < L ? a[base + k] : 0u;
+        s += v[k];
+    }
+    uint32_t tot;
+    uint32_t run = sums[blockIdx.x] + block_exclusive_scan(s, lds, &tot);
+#pragma unroll
+    for (int k = 0; k < CL_SCAN_PER_THREAD; ++k) {
+        if (base + k < L) a[base + k] = run;
+        run += v[k];
+    }
+}
+
+uint32_t scan_tiles(uint64_t L) { return (uint32_t)((L + CL_SCAN_TILE - 1) / CL_SCAN_TILE); }
+
+void enqueue_scan(uint32_t* a, uint32_t L, uint32_t* sums, uint32_t* total, const int32_t* guard, int pass, hipStream_t st) {
+    const uint32_t nt = scan_tiles(L);
+    if (nt == 0) return;
+    hipLaunchKernelGGL(scan_tile_sums, dim3(nt), dim3(CL_BLOCK), 0, st, a, L, sums, guard, pass);
+    hipLaunchKernelGGL(scan_block_sums, dim3(1), dim3(CL_BLOCK), 0, st, sums, nt, total, guard, pass);
+    hipLaunchKernelGGL(scan_tile_apply, dim3(nt), dim3(CL_BLOCK), 0, st, a, L, sums, guard, pass);
+}
+
+// ------------------------------------------------------------------------------------------------ bound and parameters
+__global__ __launch_bounds__(CL_BLOCK) void bound_partial(const double* __restrict__ pts, const int32_t* n_dev, uint32_t n_cap,
+                                                          double* __restrict__ part, CloudParams* p) {
+    __shared__ double red[6][CL_BLOCK / 64];
+    const uint32_t n = live_count(n_dev, n_cap);
+    double m[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    unsigned long long bad = 0;
+    for (uint32_t i = blockIdx.x * CL_BLOCK + threadIdx.x; i < n; i += gridDim.x * CL_BLOCK) {
+        const double x = pts[3 * (size_t)i], y = pts[3 * (size_t)i + 1], z = pts[3 * (size_t)i + 2];
+        if (!finite3(x, y, z)) { ++bad; continue; }
+        m[0] = fmin(m[0], x); m[1] = fmin(m[1], y); m[2] = fmin(m[2], z);
+        m[3] = fmax(m[3], x); m[4] = fmax(m[4], y); m[5] = fmax(m[5], z);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            const double t = __shfl_xor(m[k], o, 64);
+            m[k] = k < 3 ? fmin(m[k], t) : fmax(m[k], t);
+        }
+        bad += __shfl_xor(bad, o, 64);
+    }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) red[k][w] = m[k];
+        if (bad) atomicAdd(&p->nonfinite, bad);
+    }
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        const int k = threadIdx.x;
+        double r = red[k][0];
+        for (int q = 1; q < CL_BLOCK / 64; ++q) r = k < 3 ? fmin(r, red[k][q]) : fmax(r, red[k][q]);
+        part[6 * (size_t)blockIdx.x + k] = r;
+    }
+}
+
+__device__ inline uint32_t bit_length(int64_t v) { return v <= 0 ? 0u : 64u - (uint32_t)__clzll((unsigned long long)v); }
+
+// one workgroup: folds the partial bounds, sets the call's parameters.  Voxel mode (open3d's VoxelDownSample): origin = min - 0.5 v,
+// the too-small test on max + 0.5 v.  Grid mode: origin = min, edge = the caller's or the default, doubled until the key fits 63 bits.
+__global__ __launch_bounds__(CL_BLOCK) void cloud_params(const double* __restrict__ part, int n_part, const int32_t* n_dev, uint32_t n_cap,
+                                                         int mode, double edge_in, CloudParams* p) {
+    __shared__ double red[6][CL_BLOCK];
+    double m[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    for (int b = threadIdx.x; b < n_part; b += CL_BLOCK)
+#pragma unroll
+        for (int k = 0; k < 6; ++k) m[k] = k < 3 ? fmin(m[k], part[6 * b + k]) : fmax(m[k], part[6 * b + k]);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) red[k][threadIdx.x] = m[k];
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int t = 1; t < CL_BLOCK; ++t)
+#pragma unroll
+        for (int k = 0; k < 6; ++k) m[k] = k < 3 ? fmin(m[k], red[k][t]) : fmax(m[k], red[k][t]);
+    const uint32_t n = live_count(n_dev, n_cap);
+    uint32_t status = p->nonfinite ? (uint32_t)CL_ST_NONFINITE : 0u;
+    for (int a = 0; a < 3; ++a) { p->lo[a] = m[a]; p->hi[a] = m[3 + a]; p->dims[a] = 0; p->shift[a] = 0; }
+    p->bits = 0;
+    p->npasses = 0;
+    p->n_seg = 0;
+    p->edge = edge_in;
+    if (n == 0 || status) {
+        p->status = status;
+        p->n = 0;
+        return;
+    }
+    double edge = edge_in;
+    if (mode == CL_MODE_VOXEL) {
+        const double half = edge * 0.5;
+        double ext = 0.0;
+        for (int a = 0; a < 3; ++a) {
+            p->origin[a] = m[a] - half;
+            ext = fmax(ext, (m[3 + a] + half) - p->origin[a]);
+        }
+        if (edge * (double)2147483647 < ext) status |= CL_ST_TOO_SMALL;
+    } else {
+        for (int a = 0; a < 3; ++a) p->origin[a] = m[a];
+        if (!(edge > 0.0)) {            // the default edge: cbrt of the bounding box's volume per point, every extent raised to at least
+            double e[3], emax = 0.0;    // 2^-10 of the largest (a flat or linear cloud), 1 when all points coincide
+            for (int a = 0; a < 3; ++a) { e[a] = m[3 + a] - m[a]; emax = fmax(emax, e[a]); }
+            if (emax > 0.0) {
+                for (int a = 0; a < 3; ++a) e[a] = fmax(e[a], emax * 0x1p-10);
+                edge = cbrt(((e[0] * e[1]) * e[2]) / (double)n);
+            } else {
+                edge = 1.0;
+            }
+        }
+    }
+    if (!status) {
+        for (;;) {
+            uint32_t bits = 0;
+            bool fits = true;
+            for (int a = 0; a < 3; ++a) {
+                const double f = floor((m[3 + a] - p->origin[a]) / edge);
+                if (!(f < 0x1p62)) { fits = false; break; }
+                p->dims[a] = (int64_t)f + 1;
+                bits += bit_length((int64_t)f);
+            }
+            if (fits && bits <= (mode == CL_MODE_VOXEL ? 64u : 63u)) {
+                p->bits = bits;
+                break;
+            }
+            if (mode == CL_MODE_VOXEL) { status |= CL_ST_TOO_WIDE; p->bits = fits ? bits : 0u; break; }
+            edge *= 2.0;
+        }
+    }
+    p->edge = edge;
+    p->status = status;
+    if (status) {
+        p->n = 0;
+        return;
+    }
+    const uint32_t bz = bit_length(p->dims[2] - 1), by = bit_length(p->dims[1] - 1);
+    p->shift[2] = 0;
+    p->shift[1] = bz;
+    p->shift[0] = bz + by;
+    p->npasses = (int32_t)((p->bits + 7) / 8);
+    p->n = n;
+}
+
+__global__ __launch_bounds__(CL_BLOCK) void cloud_keys(const double* __restrict__ pts, const CloudParams* __restrict__ p,
+                                                       uint64_t* __restrict__ keys, uint32_t* __restrict__ idx) {
+    const uint32_t i = blockIdx.x * CL_BLOCK + threadIdx.x;
+    if (i >= p->n) return;
+    const double e = p->edge;
+    uint64_t key = 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double c = floor((pts[3 * (size_t)i + a] - p->origin[a]) / e);
+        key |= (uint64_t)(int64_t)c << p->shift[a];
+    }
+    keys[i] = key;
+    idx[i] = i;
+}
+
+// ------------------------------------------------------------------------------------------------ stable LSD radix sort
+__global__ __launch_bounds__(CL_BLOCK) void radix_count(const uint64_t* __restrict__ keys, const CloudParams* __restrict__ p, int pass,
+                                                        uint32_t* __restrict__ counts, uint32_t n_blocks) {
+    if (pass >= p->npasses) return;
+    __shared__ uint32_t h[CL_RADIX];
+    h[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t n = p->n, shift = 8 * pass;
+    const uint64_t base = (uint64_t)blockIdx.x * CL_SORT_TILE;
+    for (int k = 0; k < CL_SORT_TILE / CL_BLOCK; ++k) {
+        const uint64_t i = base + (uint64_t)k * CL_BLOCK + threadIdx.x;
+        if (i < n) atomicAdd(&h[(keys[i] >> shift) & (CL_RADIX - 1)], 1u);
+    }
+    __syncthreads();
+    counts[(size_t)threadIdx.x * n_blocks + blockIdx.x] = h[threadIdx.x];
+}
+
+__global__ __launch_bounds__(CL_BLOCK) void radix_scatter(const uint64_t* __restrict__ keys_in, const uint32_t* __restrict__ idx_in,
+                                                          uint64_t* __restrict__ keys_out, uint32_t* __restrict__ idx_out,
+                                                          const CloudParams* __restrict__ p, int pass,
+                                                          const uint32_t* __restrict__ offsets, uint32_t n_blocks) {
+    if (pass >= p->npasses) return;
+    __shared__ uint32_t run[CL_RADIX];
+    __shared__ uint32_t wc[CL_BLOCK / 64][CL_RADIX];
+    const uint32_t n = p->n, shift = 8 * pass;
+    const uint64_t base = (uint64_t)blockIdx.x * CL_SORT_TILE;
+    if (base >= n) return;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    run[threadIdx.x] = offsets[(size_t)threadIdx.x * n_blocks + blockIdx.x];
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int k = 0; k < CL_SORT_TILE / CL_BLOCK; ++k) {
+#pragma unroll
+        for (int q = 0; q < CL_BLOCK / 64; ++q) wc[q][threadIdx.x] = 0;
+        __syncthreads();
+        const uint64_t i = base + (uint64_t)k * CL_BLOCK + threadIdx.x;
+        const bool valid = i < n;
+        const uint64_t key = valid ? keys_in[i] : 0ull;
+        const uint32_t id = valid ? idx_in[i] : 0u;
+        const uint32_t d = (uint32_t)(key >> shift) & (CL_RADIX - 1);
+        unsigned long long same = __ballot(valid);
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const bool on = (d >> b) & 1u;
+            const unsigned long long v = __ballot(on);
+            same &= on ? v : ~v;
+        }
+        const uint32_t rank = (uint32_t)__popcll(same & below);
+        if (valid && rank == 0) wc[w][d] = (uint32_t)__popcll(same);
+        __syncthreads();
+        if (valid) {
+            uint32_t pos = run[d] + rank;
+            for (int q = 0; q < w; ++q) pos += wc[q][d];
+            keys_out[pos] = key;
+            idx_out[pos] = id;
+        }
+        __syncthreads();
+        uint32_t add = 0;
+#pragma unroll
+        for (int q = 0; q < CL_BLOCK / 64; ++q) add += wc[q][threadIdx.x];
+        run[threadIdx.x] += add;
+        __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ segments
+__device__ inline const uint64_t* sorted_keys(const CloudParams* p, const uint64_t* a, const uint64_t* b) { return (p->npasses & 1) ? b : a; }
+__device__ inline const uint32_t* sorted_idx(const CloudParams* p, const uint32_t* a, const uint32_t* b) { return (p->npasses & 1) ? b : a; }
+
+__global__ __launch_bounds__(CL_BLOCK) void segment_heads(const uint64_t* __restrict__ ka, const uint64_t* __restrict__ kb,
+                                                          const CloudParams* __restrict__ p, uint32_t n_cap, uint32_t* __restrict__ flags) {
+    const uint32_t i = blockIdx.x * CL_BLOCK + threadIdx.x;
+    if (i >= n_cap) return;
+    const uint64_t* k = sorted_keys(p, ka, kb);
+    flags[i] = (i < p->n && (i == 0 || k[i] != k[i - 1])) ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(CL_BLOCK) void segment_starts(const uint64_t* __restrict__ ka, const uint64_t* __restrict__ kb,
+                                                           const CloudParams* __restrict__ p, const uint32_t* __restrict__ seg,
+                                                           uint32_t* __restrict__ starts) {
+    const uint32_t i = blockIdx.x * CL_BLOCK + threadIdx.x;
+    if (i >= p->n) return;
+    const uint64_t* k = sorted_keys(p, ka, kb);
+    if (i == 0 || k[i] != k[i - 1]) starts[seg[i]] = i;
+}
+
+// one thread per occupied voxel: the fp64 sum of its points in input order, divided by the count (open3d AccumulatedPoint)
+__global__ __launch_bounds__(CL_BLOCK) void voxel_average(const double* __restrict__ pts, const uint32_t* __restrict__ ia,
+                                                          const uint32_t* __restrict__ ib, const CloudParams* __restrict__ p,
+                                                          const uint32_t* __restrict__ starts, double* __restrict__ out) {
+    const uint32_t s = blockIdx.x * CL_BLOCK + threadIdx.x;
+    const uint32_t n_seg = p->n_seg;
+    if (s >= n_seg) return;
+    const uint32_t* idx = sorted_idx(p, ia, ib);
+    const uint32_t j0 = starts[s], j1 = s + 1 < n_seg ? starts[s + 1] : p->n;
+    double sx = 0.0, sy = 0.0, sz = 0.0;
+    for (uint32_t j = j0; j < j1; ++j) {
+        const size_t q = 3 * (size_t)idx[j];
+        sx = sx + pts[q];
+        sy = sy + pts[q + 1];
+        sz = sz + pts[q + 2];
+    }
+    const double c = (double)(j1 - j0);
+    out[3 * (size_t)s] = sx / c;
+    out[3 * (size_t)s + 1] = sy / c;
+    out[3 * (size_t)s + 2] = sz / c;
+}
+
+// the grid: targets in key order, one (key, first target) per occupied cell, and the end sentinel
+__global__ __launch_bounds__(CL_BLOCK) void grid_fill(const double* __restrict__ pts, const uint64_t* __restrict__ ka,
+                                                      const uint64_t* __restrict__ kb, const uint32_t* __restrict__ ia,
+                                                      const uint32_t* __restrict__ ib, const CloudParams* __restrict__ p,
+                                                      const uint32_t* __restrict__ starts, double* __restrict__ sorted,
+                                                      uint64_t* __restrict__ cell_key, uint32_t* __restrict__ cell_start) {
+    const uint32_t i = blockIdx.x * CL_BLOCK + threadIdx.x;
+    const uint32_t n = p->n, n_seg = p->n_seg;
+    if (i < n) {
+        const size_t q = 3 * (size_t)sorted_idx(p, ia, ib)[i];
+        sorted[3 * (size_t)i] = pts[q];
+        sorted[3 * (size_t)i + 1] = pts[q + 1];
+        sorted[3 * (size_t)i + 2] = pts[q + 2];
+    }
+    if (i < n_seg) {
+        cell_start[i] = starts[i];
+        cell_key[i] = sorted_keys(p, ka, kb)[starts[i]];
+    }
+    if (i == 0) cell_start[n_seg] = n;
+}
+
+__global__ void cloud_info(const CloudParams* __restrict__ p, int64_t* __restrict__ info) {
+    info[0] = p->status;
+    info[1] = p->n_seg;
+    info[2] = (int64_t)p->nonfinite;
+    info[3] = p->bits;
+    info[4] = (int64_t)__double_as_longlong(p->edge);
+    for (int a = 0; a < 3; ++a) info[5 + a] = p->dims[a];
+}
+
+// ------------------------------------------------------------------------------------------------ scan points and transform
+__device__ inline bool scan_keep(float depth, float var, float scale, float var_max, float depth_max, float* depth_m) {
+    const float d = depth * scale, v = var * scale;
+    *depth_m = d;
+    return v < var_max && d < depth_max;
+}
+
+__global__ __launch_bounds__(CL_BLOCK) void scan_flags(const float* __restrict__ depth, const float* __restrict__ var, uint32_t m,
+                                                       float scale, float var_max, float depth_max, uint32_t* __restrict__ flags) {
+    const uint32_t i = blockIdx.x * CL_BLOCK + threadIdx.x;
+    if (i >= m) return;
+    float d;
+    flags[i] = scan_keep(depth[i], var[i], scale, var_max, depth_max, &d) ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(CL_BLOCK) void scan_emit(const float* __restrict__ depth, const float* __restrict__ var,
+                                                      const int64_t* __restrict__ ray_index, const float* __restrict__ dirs, int64_t n_dirs,
+                                                      uint32_t m, float scale, float var_max, float depth_max,
+                                                      const uint32_t* __restrict__ pos, double* __restrict__ out) {
+    const uint32_t i = blockIdx.x * CL_BLOCK + threadIdx.x;
+    if (i >= m) return;
+    float d;
+    if (!scan_keep(depth[i], var[i], scale, var_max, depth_max, &d)) return;
+    const int64_t r = ray_index[i];
+    if (r < 0 || r >= n_dirs) return;
+    const size_t o = 3 * (size_t)pos[i];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) out[o + a] = (double)(dirs[a * n_dirs + r] * d);
+}
+
+struct Affine { double t[12]; };
+
+__global__ __launch_bounds__(CL_BLOCK) void append_transformed(const double* src, uint32_t n, Affine T, double* dst) {
+    const uint32_t i = blockIdx.x * CL_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const double x = src[3 * (size_t)i], y = src[3 * (size_t)i + 1], z = src[3 * (size_t)i + 2];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) dst[3 * (size_t)i + a] = ((T.t[4 * a] * x + T.t[4 * a + 1] * y) + T.t[4 * a + 2] * z) + T.t[4 * a + 3];
+}
+
+// ------------------------------------------------------------------------------------------------ nearest-neighbour distance
+struct GridView {
+    const CloudParams* p;
+    const double* pts;
+    const uint64_t* cell_key;
+    const uint32_t* cell_start;
+};
+
+__device__ inline double sq_dist(double qx, double qy, double qz, const double* t) {
+    const double dx = qx - t[0], dy = qy - t[1], dz = qz - t[2];
+    return (dx * dx + dy * dy) + dz * dz;
+}
+
+// the cells of row (x, y) with z in [z0, z1]: lower_bound on the sorted cell keys, then forward while the key is in the row
+__device__ inline void visit_row(const GridView& g, uint32_t n_cells, int64_t x, int64_t y, int64_t z0, int64_t z1, double qx, double qy,
+                                 double qz, double& best) {
+    const CloudParams* p = g.p;
+    const uint64_t k0 = ((uint64_t)x << p->shift[0]) | ((uint64_t)y << p->shift[1]) | (uint64_t)z0;
+    const uint64_t k1 = ((uint64_t)x << p->shift[0]) | ((uint64_t)y << p->shift[1]) | (uint64_t)z1;
+    uint32_t lo = 0, hi = n_cells;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (g.cell_key[mid] < k0) lo = mid + 1; else hi = mid;
+    }
+    for (uint32_t c = lo; c < n_cells && g.cell_key[c] <= k1; ++c)
+        for (uint32_t j = g.cell_start[c]; j < g.cell_start[c + 1]; ++j) best = fmin(best, sq_dist(qx, qy, qz, g.pts + 3 * (size_t)j));
+}
+
+__global__ __launch_bounds__(CL_BLOCK) void nn_shells(GridView g, const double* __restrict__ q, uint32_t n_q, double* __restrict__ dist,
+                                                      double* __restrict__ d2_out, uint32_t* __restrict__ fallback,
+                                                      unsigned long long* __restrict__ counters) {
+    const uint32_t i = blockIdx.x * CL_BLOCK + threadIdx.x;
+    unsigned long long shells = 0;
+    if (i < n_q) {
+        const CloudParams* p = g.p;
+        const double qv[3] = {q[3 * (size_t)i], q[3 * (size_t)i + 1], q[3 * (size_t)i + 2]};
+        if (!finite3(qv[0], qv[1], qv[2])) {
+            atomicAdd(&counters[1], 1ull);
+            dist[i] = NAN;
+            if (d2_out) d2_out[i] = NAN;
+        } else if (p->n == 0) {                         // no target: open3d's SearchKNN finds nothing and the distance stays 0
+            dist[i] = 0.0;
+            if (d2_out) d2_out[i] = 0.0;
+        } else {
+            const double h = p->edge;
+            int64_t c[3];
+            double slack[3];
+            for (int a = 0; a < 3; ++a) {
+                double f = floor((qv[a] - p->origin[a]) / h);
+                f = fmin(fmax(f, 0.0), (double)(p->dims[a] - 1));
+                c[a] = (int64_t)f;
+                slack[a] = 1e-14 * ((fabs(p->origin[a]) + fabs(qv[a])) + (double)(p->dims[a] + 1) * h);
+            }
+            const uint32_t n_cells = p->n_seg;
+            double best = INFINITY;
+            bool done = false;
+            for (int r = 0; r <= NN_MAX_SHELL && !done; ++r) {
+                ++shells;
+                const int64_t x0 = c[0] - r > 0 ? c[0] - r : 0, x1 = c[0] + r < p->dims[0] - 1 ? c[0] + r : p->dims[0] - 1;
+                const int64_t y0 = c[1] - r > 0 ? c[1] - r : 0, y1 = c[1] + r < p->dims[1] - 1 ? c[1] + r : p->dims[1] - 1;
+                const int64_t zl = c[2] - r, zh = c[2] + r, zmax = p->dims[2] - 1;
+                for (int64_t x = x0; x <= x1; ++x)
+                    for (int64_t y = y0; y <= y1; ++y) {
+                        const bool ring = x == c[0] - r || x == c[0] + r || y == c[1] - r || y == c[1] + r;
+                        if (ring) {
+                            visit_row(g, n_cells, x, y, zl > 0 ? zl : 0, zh < zmax ? zh : zmax, qv[0], qv[1], qv[2], best);
+                        } else {
+                            if (zl >= 0) visit_row(g, n_cells, x, y, zl, zl, qv[0], qv[1], qv[2], best);
+                            if (zh <= zmax && zh != zl) visit_row(g, n_cells, x, y, zh, zh, qv[0], qv[1], qv[2], best);
+                        }
+                    }
+                // a lower bound on the distance to any target in a cell outside the shells visited: per axis and side, the gap to the
+                // first unvisited layer of cells, less a slack that covers the rounding of both cell assignments
+                double bound = INFINITY;
+                for (int a = 0; a < 3; ++a) {
+                    if (c[a] - r - 1 >= 0)
+                        bound = fmin(bound, fmax((qv[a] - (p->origin[a] + (double)(c[a] - r) * h)) - slack[a], 0.0));
+                    if (c[a] + r + 1 <= p->dims[a] - 1)
+                        bound = fmin(bound, fmax(((p->origin[a] + (double)(c[a] + r + 1) * h) - qv[a]) - slack[a], 0.0));
+                }
+                done = bound == INFINITY || best <= (bound * bound) * (1.0 - 1e-14);
+            }
+            if (done) {
+                dist[i] = sqrt(best);
+                if (d2_out) d2_out[i] = best;
+            } else {
+                fallback[atomicAdd(&counters[0], 1ull)] = i;
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) shells += __shfl_xor(shells, o, 64);
+    if ((threadIdx.x & 63) == 0 && shells) atomicAdd(&counters[2], shells);
+}
+
+// the exact fallback: one query per thread, every target streamed through LDS in tiles
+__global__ __launch_bounds__(CL_BLOCK) void nn_brute(GridView g, const double* __restrict__ q, const uint32_t* __restrict__ fallback,
+                                                     const unsigned long long* __restrict__ counters, double* __restrict__ dist,
+                                                     double* __restrict__ d2_out) {
+    __shared__ double tile[NN_FB_TILE * 3];
+    const uint32_t n_fb = (uint32_t)counters[0];
+    if ((uint64_t)blockIdx.x * CL_BLOCK >= n_fb) return;
+    const uint32_t k = blockIdx.x * CL_BLOCK + threadIdx.x;
+    const bool active = k < n_fb;
+    const uint32_t i = active ? fallback[k] : 0u;
+    const double qx = active ? q[3 * (size_t)i] : 0.0, qy = active ? q[3 * (size_t)i + 1] : 0.0, qz = active ? q[3 * (size_t)i + 2] : 0.0;
+    const uint32_t n = g.p->n;
+    double best = INFINITY;
+    for (uint32_t t0 = 0; t0 < n; t0 += NN_FB_TILE) {
+        const uint32_t m = n - t0 < NN_FB_TILE ? n - t0 : NN_FB_TILE;
+        __syncthreads();
+        for (uint32_t e = threadIdx.x; e < 3 * m; e += CL_BLOCK) tile[e] = g.pts[3 * (size_t)t0 + e];
+        __syncthreads();
+        for (uint32_t j = 0; j < m; ++j) best = fmin(best, sq_dist(qx, qy, qz, tile + 3 * j));
+    }
+    if (active) {
+        dist[i] = sqrt(best);
+        if (d2_out) d2_out[i] = best;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ host
+size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+struct CloudLayout {
+    uint32_t n_cap, sort_blocks, scan_len;
+    size_t params, part, ka, kb, ia, ib, counts, flags, starts, sums, total;
+};
+CloudLayout cloud_layout(int64_t n) {
+    CloudLayout l;
+    l.n_cap = (uint32_t)n;
+    l.sort_blocks = (uint32_t)((n + CL_SORT_TILE - 1) / CL_SORT_TILE);
+    const uint64_t count_len = (uint64_t)CL_RADIX * l.sort_blocks;
+    l.scan_len = (uint32_t)(count_len > (uint64_t)n ? count_len : (uint64_t)n);
+    l.params = 0;
+    l.part = align256(sizeof(CloudParams));
+    l.ka = align256(l.part + 6 * sizeof(double) * CL_BOUND_BLOCKS);
+    l.kb = align256(l.ka + 8 * (size_t)n);
+    l.ia = align256(l.kb + 8 * (size_t)n);
+    l.ib = align256(l.ia + 4 * (size_t)n);
+    l.counts = align256(l.ib + 4 * (size_t)n);
+    l.flags = align256(l.counts + 4 * count_len);
+    l.starts = align256(l.flags + 4 * (size_t)n);
+    l.sums = align256(l.starts + 4 * ((size_t)n + 1));
+    l.total = align256(l.sums + 4 * ((size_t)scan_tiles(l.scan_len) + 1));
+    return l;
+}
+
+struct GridLayout { size_t params, pts, cell_key, cell_start, total; };
+GridLayout grid_layout(int64_t n) {
+    GridLayout l;
+    l.params = 0;
+    l.pts = align256(sizeof(CloudParams));
+    l.cell_key = align256(l.pts + 24 * (size_t)n);
+    l.cell_start = align256(l.cell_key + 8 * (size_t)n);
+    l.total = align256(l.cell_start + 4 * ((size_t)n + 1));
+    return l;
+}
+
+uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + CL_BLOCK - 1) / CL_BLOCK); }
+
+const int64_t CL_MAX_POINTS = ((int64_t)1 << 31) - CL_SORT_TILE;
+
+// bound -> parameters -> keys -> sort -> segment starts, on `ws`; params at `p`
+int sort_cloud(const char* what, const double* pts, int64_t n, const int32_t* n_dev, int mode, double edge, char* ws, const CloudLayout& l,
+               CloudParams* p, hipStream_t st) {
+    if (hipMemsetAsync(p, 0, sizeof(CloudParams), st) != hipSuccess) {
+        lnr_set_error("%s: clearing the parameters failed", what);
+        return LNR_ERR_LAUNCH;
+    }
+    if (n == 0) {
+        hipLaunchKernelGGL(cloud_params, dim3(1), dim3(CL_BLOCK), 0, st, (const double*)(ws + l.part), 0, n_dev, 0u, mode, edge, p);
+        LNR_CHECK_LAUNCH(what);
+        return LNR_OK;
+    }
+    const uint32_t n_cap = l.n_cap;
+    const int nbr = (int)(blocks_for(n) < CL_BOUND_BLOCKS ? blocks_for(n) : CL_BOUND_BLOCKS);
+    uint64_t *ka = (uint64_t*)(ws + l.ka), *kb = (uint64_t*)(ws + l.kb);
+    uint32_t *ia = (uint32_t*)(ws + l.ia), *ib = (uint32_t*)(ws + l.ib);
+    uint32_t* counts = (uint32_t*)(ws + l.counts);
+    uint32_t* sums = (uint32_t*)(ws + l.sums);
+    hipLaunchKernelGGL(bound_partial, dim3(nbr), dim3(CL_BLOCK), 0, st, pts, n_dev, n_cap, (double*)(ws + l.part), p);
+    hipLaunchKernelGGL(cloud_params, dim3(1), dim3(CL_BLOCK), 0, st, (const double*)(ws + l.part), nbr, n_dev, n_cap, mode, edge, p);
+    hipLaunchKernelGGL(cloud_keys, dim3(blocks_for(n_cap)), dim3(CL_BLOCK), 0, st, pts, p, ka, ia);
+    LNR_CHECK_LAUNCH(what);
+    const int32_t* guard = &p->npasses;
+    for (int pass = 0; pass < CL_MAX_PASSES; ++pass) {
+        const uint64_t* kin = (pass & 1) ? kb : ka;
+        uint64_t* kout = (pass & 1) ? ka : kb;
+        const uint32_t* iin = (pass & 1) ? ib : ia;
+        uint32_t* iout = (pass & 1) ? ia : ib;
+        hipLaunchKernelGGL(radix_count, dim3(l.sort_blocks), dim3(CL_BLOCK), 0, st, kin, p, pass, counts, l.sort_blocks);
+        enqueue_scan(counts, CL_RADIX * l.sort_blocks, sums, nullptr, guard, pass, st);
+        hipLaunchKernelGGL(radix_scatter, dim3(l.sort_blocks), dim3(CL_BLOCK), 0, st, kin, iin, kout, iout, p, pass, counts, l.sort_blocks);
+        LNR_CHECK_LAUNCH(what);
+    }
+    uint32_t* flags = (uint32_t*)(ws + l.flags);
+    hipLaunchKernelGGL(segment_heads, dim3(blocks_for(n_cap)), dim3(CL_BLOCK), 0, st, ka, kb, p, n_cap, flags);
+    enqueue_scan(flags, n_cap, sums, &p->n_seg, nullptr, 0, st);
+    hipLaunchKernelGGL(segment_starts, dim3(blocks_for(n_cap)), dim3(CL_BLOCK), 0, st, ka, kb, p, flags, (uint32_t*)(ws + l.starts));
+    LNR_CHECK_LAUNCH(what);
+    return LNR_OK;
+}
+
+}  // namespace
+
+extern "C" size_t lnr_cloud_workspace(int64_t n_points) {
+    if (n_points < 0 || n_points > CL_MAX_POINTS) return 0;
+    return cloud_layout(n_points).total;
+}
+
+extern "C" size_t lnr_nn_grid_bytes(int64_t n_targets) {
+    if (n_targets < 0 || n_targets > CL_MAX_POINTS) return 0;
+    return grid_layout(n_targets).total;
+}
+
+extern "C" int lnr_lidar_scan_points(const float* depth, const float* variance, const int64_t* ray_index, int64_t n_rays,
+                                     const float* directions, int64_t n_directions, float scale, float var_max, float depth_max,
+                                     void* workspace, size_t workspace_bytes, double* points, int32_t* n_points_dev, void* stream) {
+    LNR_REQUIRE(n_rays >= 0 && n_rays <= CL_MAX_POINTS, "lnr_lidar_scan_points: %lld rays, the limit is %lld", (long long)n_rays,
+                (long long)CL_MAX_POINTS);
+    LNR_REQUIRE(n_directions >= 0 && n_directions < ((int64_t)1 << 40), "lnr_lidar_scan_points: bad direction count");
+    LNR_REQUIRE(n_points_dev && (n_rays == 0 || (depth && variance && ray_index && directions && points && workspace)),
+                "lnr_lidar_scan_points: null argument");
+    const CloudLayout l = cloud_layout(n_rays);
+    LNR_REQUIRE(workspace_bytes >= l.total, "lnr_lidar_scan_points: workspace of %zu bytes, %zu needed", workspace_bytes, l.total);
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(n_points_dev, 0, sizeof(int32_t), st) != hipSuccess) {
+        lnr_set_error("lnr_lidar_scan_points: clearing the count failed");
+        return LNR_ERR_LAUNCH;
+    }
+    if (n_rays == 0) return LNR_OK;
+    LnrProfScope prof("lidar_scan_points", st);
+    char* ws = (char*)workspace;
+    uint32_t* flags = (uint32_t*)(ws + l.flags);
+    const uint32_t m = (uint32_t)n_rays;
+    hipLaunchKernelGGL(scan_flags, dim3(blocks_for(m)), dim3(CL_BLOCK), 0, st, depth, variance, m, scale, var_max, depth_max, flags);
+    enqueue_scan(flags, m, (uint32_t*)(ws + l.sums), (uint32_t*)n_points_dev, nullptr, 0, st);
+    hipLaunchKernelGGL(scan_emit, dim3(blocks_for(m)), dim3(CL_BLOCK), 0, st, depth, variance, ray_index, directions, n_directions, m, scale,
+                       var_max, depth_max, flags, points);
+    LNR_CHECK_LAUNCH("lnr_lidar_scan_points");
+    return LNR_OK;
+}
+
+extern "C" int lnr_voxel_down_sample(const double* points, int64_t n_points, const int32_t* n_points_dev, double voxel_size,
+                                     void* workspace, size_t workspace_bytes, double* out, int64_t* info_dev, void* stream) {
+    LNR_REQUIRE(n_points >= 0 && n_points <= CL_MAX_POINTS, "lnr_voxel_down_sample: %lld points, the limit is %lld",
+                (long long)n_points, (long long)CL_MAX_POINTS);
+    LNR_REQUIRE(isfinite(voxel_size) && voxel_size > 0.0, "lnr_voxel_down_sample: voxel_size must be finite and > 0, got %g", voxel_size);
+    LNR_REQUIRE(info_dev && workspace && (n_points == 0 || (points && out)), "lnr_voxel_down_sample: null argument");
+    const CloudLayout l = cloud_layout(n_points);
+    LNR_REQUIRE(workspace_bytes >= l.total, "lnr_voxel_down_sample: workspace of %zu bytes, %zu needed", workspace_bytes, l.total);
+    hipStream_t st = (hipStream_t)stream;
+    LnrProfScope prof("voxel_down_sample", st);
+    char* ws = (char*)workspace;
+    CloudParams* p = (CloudParams*)(ws + l.params);
+    if (int rc = sort_cloud("lnr_voxel_down_sample", points, n_points, n_points_dev, CL_MODE_VOXEL, voxel_size, ws, l, p, st)) return rc;
+    if (n_points > 0) {
+        hipLaunchKernelGGL(voxel_average, dim3(blocks_for(n_points)), dim3(CL_BLOCK), 0, st, points, (const uint32_t*)(ws + l.ia),
+                           (const uint32_t*)(ws + l.ib), p, (const uint32_t*)(ws + l.starts), out);
+    }
+    hipLaunchKernelGGL(cloud_info, dim3(1), dim3(1), 0, st, p, info_dev);
+    LNR_CHECK_LAUNCH("lnr_voxel_down_sample");
+    return LNR_OK;
+}
+
+extern "C" int lnr_cloud_append_transformed(const double* src, int64_t n_points, const double* transform, double* dst, void* stream) {
+    LNR_REQUIRE(n_points >= 0 && n_points <= CL_MAX_POINTS, "lnr_cloud_append_transformed: %lld points, the limit is %lld",
+                (long long)n_points, (long long)CL_MAX_POINTS);
+    LNR_REQUIRE(transform && (n_points == 0 || (src && dst)), "lnr_cloud_append_transformed: null argument");
+    Affine T;
+    for (int k = 0; k < 12; ++k) {
+        T.t[k] = transform[k];
+        LNR_REQUIRE(isfinite(T.t[k]), "lnr_cloud_append_transformed: non-finite transform entry %d", k);
+    }
+    if (n_points == 0) return LNR_OK;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(append_transformed, dim3(blocks_for(n_points)), dim3(CL_BLOCK), 0, st, src, (uint32_t)n_points, T, dst);
+    LNR_CHECK_LAUNCH("lnr_cloud_append_transformed");
+    return LNR_OK;
+}
+
+extern "C" int lnr_nn_grid_build(const double* targets, int64_t n_targets, double cell_edge, void* workspace, size_t workspace_bytes,
+                                 void* grid, size_t grid_bytes, int64_t* info_dev, void* stream) {
+    LNR_REQUIRE(n_targets >= 0 && n_targets <= CL_MAX_POINTS, "lnr_nn_grid_build: %lld targets, the limit is %lld", (long long)n_targets,
+                (long long)CL_MAX_POINTS);
+    LNR_REQUIRE(!(cell_edge > 0.0) || isfinite(cell_edge), "lnr_nn_grid_build: cell_edge must be finite (or <= 0 for the default)");
+    LNR_REQUIRE(info_dev && workspace && grid && (n_targets == 0 || targets), "lnr_nn_grid_build: null argument");
+    const CloudLayout l = cloud_layout(n_targets);
+    const GridLayout g = grid_layout(n_targets);
+    LNR_REQUIRE(workspace_bytes >= l.total, "lnr_nn_grid_build: workspace of %zu bytes, %zu needed", workspace_bytes, l.total);
+    LNR_REQUIRE(grid_bytes >= g.total, "lnr_nn_grid_build: grid of %zu bytes, %zu needed", grid_bytes, g.total);
+    hipStream_t st = (hipStream_t)stream;
+    LnrProfScope prof("nn_grid_build", st);
+    char* ws = (char*)workspace;
+    char* gb = (char*)grid;
+    CloudParams* p = (CloudParams*)(gb + g.params);
+    if (int rc = sort_cloud("lnr_nn_grid_build", targets, n_targets, nullptr, CL_MODE_GRID, cell_edge > 0.0 ? cell_edge : 0.0, ws, l, p, st))
+        return rc;
+    hipLaunchKernelGGL(grid_fill, dim3(blocks_for(n_targets + 1)), dim3(CL_BLOCK), 0, st, targets, (const uint64_t*)(ws + l.ka),
+                       (const uint64_t*)(ws + l.kb), (const uint32_t*)(ws + l.ia), (const uint32_t*)(ws + l.ib), p,
+                       (const uint32_t*)(ws + l.starts), (double*)(gb + g.pts), (uint64_t*)(gb + g.cell_key), (uint32_t*)(gb + g.cell_start));
+    hipLaunchKernelGGL(cloud_info, dim3(1), dim3(1), 0, st, p, info_dev);
+    LNR_CHECK_LAUNCH("lnr_nn_grid_build");
+    return LNR_OK;
+}
+
+extern "C" int lnr_nn_distance(const void* grid, int64_t n_targets, const double* queries, int64_t n_queries, double* distance,
+                               double* sq_distance, void* workspace, size_t workspace_bytes, int64_t* counters_dev, void* stream) {
+    LNR_REQUIRE(n_targets >= 0 && n_targets <= CL_MAX_POINTS && n_queries >= 0 && n_queries <= CL_MAX_POINTS,
+                "lnr_nn_distance: %lld targets, %lld queries, the limit is %lld each", (long long)n_targets, (long long)n_queries,
+                (long long)CL_MAX_POINTS);
+    LNR_REQUIRE(grid && counters_dev && workspace && (n_queries == 0 || (queries && distance)), "lnr_nn_distance: null argument");
+    const size_t need = lnr_cloud_workspace(n_queries);
+    LNR_REQUIRE(workspace_bytes >= need, "lnr_nn_distance: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(counters_dev, 0, 4 * sizeof(int64_t), st) != hipSuccess) {
+        lnr_set_error("lnr_nn_distance: clearing the counters failed");
+        return LNR_ERR_LAUNCH;
+    }
+    if (n_queries == 0) return LNR_OK;
+    LnrProfScope prof("nn_distance", st);
+    const GridLayout gl = grid_layout(n_targets);
+    const char* gb = (const char*)grid;
+    GridView g{(const CloudParams*)(gb + gl.params), (const double*)(gb + gl.pts), (const uint64_t*)(gb + gl.cell_key),
+               (const uint32_t*)(gb + gl.cell_start)};
+    uint32_t* fb = (uint32_t*)workspace;
+    unsigned long long* cnt = (unsigned long long*)counters_dev;
+    const uint32_t nq = (uint32_t)n_queries;
+    hipLaunchKernelGGL(nn_shells, dim3(blocks_for(nq)), dim3(CL_BLOCK), 0, st, g, queries, nq, distance, sq_distance, fb, cnt);
+    hipLaunchKernelGGL(nn_brute, dim3(blocks_for(nq)), dim3(CL_BLOCK), 0, st, g, queries, (const uint32_t*)fb, (const unsigned long long*)cnt,
+                       distance, sq_distance);
+    LNR_CHECK_LAUNCH("lnr_nn_distance");
+    return LNR_OK;
+}

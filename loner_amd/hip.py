@@ -104,6 +104,13 @@ _SIGNATURES = {
     "lnr_mc_emit": (C.c_int, [P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), P, C.c_size_t,
                               C.c_int64, C.c_int64, P, P, P]),
     "lnr_mc_case_table": (C.c_int, [P]),
+    "lnr_cloud_workspace": (C.c_size_t, [C.c_int64]),
+    "lnr_lidar_scan_points": (C.c_int, [P, P, P, C.c_int64, P, C.c_int64, C.c_float, C.c_float, C.c_float, P, C.c_size_t, P, P, P]),
+    "lnr_voxel_down_sample": (C.c_int, [P, C.c_int64, P, C.c_double, P, C.c_size_t, P, P, P]),
+    "lnr_cloud_append_transformed": (C.c_int, [P, C.c_int64, C.POINTER(C.c_double), P, P]),
+    "lnr_nn_grid_bytes": (C.c_size_t, [C.c_int64]),
+    "lnr_nn_grid_build": (C.c_int, [P, C.c_int64, C.c_double, P, C.c_size_t, P, C.c_size_t, P, P]),
+    "lnr_nn_distance": (C.c_int, [P, C.c_int64, P, C.c_int64, P, P, P, C.c_size_t, P, P]),
     "lnr_points_grad_to_rays": (C.c_int, [P, P, C.c_int32, P, C.c_int32, P, P]),
     "lnr_weights_gt": (C.c_int, [P, P, P, C.c_float, C.c_int32, C.c_int32, C.c_int32, P, P]),
     "lnr_logits_grad": (C.c_int, [P, P, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, P, P]),

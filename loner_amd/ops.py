@@ -5,6 +5,7 @@ torch, and enqueues the kernel on torch's current stream.  No function here comp
 itself - the arithmetic is in libloner_hip.so.
 """
 import ctypes as C
+import math
 import os
 
 import torch
@@ -490,6 +491,142 @@ def marching_cubes(volume, level=0.0, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0,
     check(lib.lnr_mc_emit(_ptr(vol), nx, ny, nz, float(level), sp, org, _ptr(ws), int(ws_bytes), n_verts, n_tris, _ptr(verts), _ptr(faces),
                           _stream()), "lnr_mc_emit")
     return verts, faces
+
+
+# ---------------------------------------------------------------- point clouds
+_cloud_ws = {}
+
+
+def _cloud_workspace(n, device):
+    """lnr_cloud_workspace(n) bytes on `device`: one buffer per device, grown on demand (calls on one stream reuse it in order)."""
+    need = int(load().lnr_cloud_workspace(int(n)))
+    if need == 0:
+        raise RuntimeError(f"point clouds: {n} points, the limit per call is 2^31 - 4096")
+    key = str(device)
+    buf = _cloud_ws.get(key)
+    if buf is None or buf.numel() < need:
+        _cloud_ws.pop(key, None)
+        buf = _cloud_ws[key] = torch.empty(need, device=device, dtype=torch.uint8)
+    return buf, need
+
+
+def _f64_points(t, what):
+    require_device(t)
+    assert t.dim() == 2 and t.shape[1] == 3, f"{what}: points [n,3]"
+    return t.to(torch.float64).contiguous()
+
+
+_CLOUD_STATUS = {1: "non-finite input coordinates", 2: "voxel_size is too small", 4: "the voxel key needs more than 64 bits"}
+
+
+def _cloud_status(what, info):
+    status = int(info[0])
+    if status & 1:
+        raise RuntimeError(f"{what}: {int(info[2])} points with non-finite coordinates")
+    if status:
+        raise RuntimeError(f"{what}: " + ", ".join(m for b, m in _CLOUD_STATUS.items() if status & b))
+
+
+def lidar_scan_points(depth, variance, ray_index, directions, scale, var_max, depth_max):
+    """Scan points of one rendered pose (include/loner_hip.h: lnr_lidar_scan_points) -> (points [m,3] fp64, count int32 [1]); the
+    first count rows hold the kept rays' points in ray order, and the count stays on the device."""
+    require_device(depth, variance, ray_index, directions)
+    depth, variance, directions = _f32c(depth).reshape(-1), _f32c(variance).reshape(-1), _f32c(directions)
+    ray_index = ray_index.to(torch.int64).contiguous()
+    assert directions.dim() == 2 and directions.shape[0] == 3, "lidar_scan_points: directions [3, N]"
+    m = depth.shape[0]
+    assert variance.shape[0] == m and ray_index.shape[0] == m
+    dev = depth.device
+    ws, need = _cloud_workspace(m, dev)
+    points = torch.empty(m, 3, device=dev, dtype=torch.float64)
+    count = torch.empty(1, device=dev, dtype=torch.int32)
+    check(load().lnr_lidar_scan_points(_ptr(depth), _ptr(variance), _ptr(ray_index), m, _ptr(directions), directions.shape[1],
+                                       float(scale), float(var_max), float(depth_max), _ptr(ws), need, _ptr(points), _ptr(count),
+                                       _stream()), "lnr_lidar_scan_points")
+    return points, count
+
+
+def voxel_down_sample(points, voxel_size, count=None):
+    """open3d's VoxelDownSample with a defined order (include/loner_hip.h: lnr_voxel_down_sample): points [n,3] (fp64), count
+    (optional int32 [1] on the device) the live rows -> [k,3] fp64, one point per occupied voxel in ascending (i_x, i_y, i_z)
+    order.  One device -> host read."""
+    v = float(voxel_size)
+    if not (math.isfinite(v) and v > 0):
+        raise ValueError(f"voxel_down_sample: voxel_size must be finite and > 0, got {voxel_size!r}")
+    pts = _f64_points(points, "voxel_down_sample")
+    require_device(count)
+    n = pts.shape[0]
+    dev = pts.device
+    ws, need = _cloud_workspace(n, dev)
+    out = torch.empty(n, 3, device=dev, dtype=torch.float64)
+    info = torch.empty(8, device=dev, dtype=torch.int64)
+    check(load().lnr_voxel_down_sample(_ptr(pts), n, _ptr(count), v, _ptr(ws), need, _ptr(out), _ptr(info), _stream()),
+          "lnr_voxel_down_sample")
+    info = info.cpu()
+    _cloud_status("voxel_down_sample", info)
+    return out[:int(info[1])]
+
+
+def cloud_transform(points, T, out=None):
+    """out[i] = T[:3,:3] p_i + T[:3,3] in fp64 without fma (include/loner_hip.h: lnr_cloud_append_transformed).  T: a 4x4 affine
+    (tensor or array, any float dtype, widened to fp64); out (optional, [n,3] fp64, may be `points` itself or a slice of a larger
+    cloud) receives the result."""
+    import numpy as np
+    T = np.asarray(T.detach().cpu().numpy() if torch.is_tensor(T) else T, dtype=np.float64)
+    if T.shape != (4, 4) or not np.array_equal(T[3], [0.0, 0.0, 0.0, 1.0]):
+        raise ValueError(f"transform: T must be a 4x4 affine matrix with bottom row [0, 0, 0, 1], got {T.tolist()}")
+    pts = _f64_points(points, "transform")
+    out = torch.empty_like(pts) if out is None else out
+    assert out.dtype == torch.float64 and out.is_contiguous() and out.shape == pts.shape
+    t12 = (C.c_double * 12)(*[float(x) for x in T[:3].reshape(-1)])
+    check(load().lnr_cloud_append_transformed(_ptr(pts), pts.shape[0], t12, _ptr(out), _stream()), "lnr_cloud_append_transformed")
+    return out
+
+
+class NNGrid:
+    """The nearest-neighbour grid over a target cloud (include/loner_hip.h: lnr_nn_grid_build), reusable for any number of query
+    batches.  cell_edge: None for the default rule.  .edge, .n_cells, .dims: what the build chose (one host read)."""
+
+    def __init__(self, targets, cell_edge=None):
+        pts = _f64_points(targets, "NNGrid")
+        self.n = pts.shape[0]
+        dev = pts.device
+        lib = load()
+        gbytes = int(lib.lnr_nn_grid_bytes(self.n))
+        if gbytes == 0:
+            raise RuntimeError(f"NNGrid: {self.n} targets, the limit is 2^31 - 4096")
+        self.buf = torch.empty(gbytes, device=dev, dtype=torch.uint8)
+        ws, need = _cloud_workspace(self.n, dev)
+        info = torch.empty(8, device=dev, dtype=torch.int64)
+        edge = 0.0 if cell_edge is None else float(cell_edge)
+        if not math.isfinite(edge) or edge < 0:
+            raise ValueError(f"NNGrid: cell_edge must be finite and > 0, got {cell_edge!r}")
+        check(lib.lnr_nn_grid_build(_ptr(pts), self.n, edge, _ptr(ws), need, _ptr(self.buf), gbytes, _ptr(info), _stream()),
+              "lnr_nn_grid_build")
+        info = info.cpu()
+        _cloud_status("NNGrid", info)
+        self.n_cells = int(info[1])
+        self.edge = float(info[4:5].view(torch.float64)[0])
+        self.dims = tuple(int(x) for x in info[5:8])
+
+    def distance(self, queries, want_sq=False, stats=None):
+        """-> distance [m] fp64 to the nearest target (and d2 when want_sq); stats (a dict, optional) receives the counters
+        {"fallback": queries that took the exact pass, "shells": shells visited}.  One device -> host read."""
+        q = _f64_points(queries, "NNGrid.distance")
+        m = q.shape[0]
+        dev = q.device
+        dist = torch.empty(m, device=dev, dtype=torch.float64)
+        d2 = torch.empty(m, device=dev, dtype=torch.float64) if want_sq else None
+        ws, need = _cloud_workspace(m, dev)
+        counters = torch.empty(4, device=dev, dtype=torch.int64)
+        check(load().lnr_nn_distance(_ptr(self.buf), self.n, _ptr(q), m, _ptr(dist), _ptr(d2), _ptr(ws), need, _ptr(counters),
+                                     _stream()), "lnr_nn_distance")
+        c = counters.cpu()
+        if int(c[1]):
+            raise RuntimeError(f"compute_point_cloud_distance: {int(c[1])} queries with non-finite coordinates")
+        if stats is not None:
+            stats.update(fallback=int(c[0]), shells=int(c[2]))
+        return (dist, d2) if want_sq else dist
 
 
 def render_backward(sigma, z, rays, g_depth, g_weights, g_opacity, g_variance, noise=None, noise_std=0.0, seed=0,
