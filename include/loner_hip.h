@@ -472,6 +472,56 @@ int lnr_nn_grid_build(const double* targets, int64_t n_targets, double cell_edge
 int lnr_nn_distance(const void* grid, int64_t n_targets, const double* queries, int64_t n_queries, double* distance,
                     double* sq_distance, void* workspace, size_t workspace_bytes, int64_t* counters_dev, void* stream);
 
+/* The device-matrix form of lnr_cloud_append_transformed: transform_dev [12] fp64 in device memory (the top three rows of T, row-major),
+ * the same rounding.  ICP moves its working copy of the source with it, reading each round's update where the device computed it. */
+int lnr_cloud_append_transformed_dev(const double* src, int64_t n_points, const double* transform_dev, double* dst, void* stream);
+
+/* ---- normals and point-to-plane ICP (analysis/evaluate_lidar_map.py:23-53) ----------------------------------------------------- */
+#define LNR_KNN_MAX 32          /* the largest knn of lnr_cloud_normals */
+#define LNR_ICP_RESULT 64       /* fp64 entries of lnr_icp_point_to_plane's result */
+
+/* open3d's PointCloud::EstimateNormals(KDTreeSearchParamKNN(knn)) (evaluate_lidar_map.py:36-37) over the points a grid was built from
+ * (lnr_nn_grid_build, any cell edge: the results do not depend on it).  Neighbours of point i: the min(knn, n) smallest
+ * (d2, input index) pairs over all points, i itself included, d2 as lnr_nn_distance's (the lower input index wins a tie), found by the
+ * same shell walk with the k-th best in the stop rule and the same exact pass for points still open after 5 shells.  Covariance (fp64,
+ * no fma): with m >= 3 neighbours, the cumulants sum_x .. sum_zz summed in neighbour order, each divided by (double) m, then
+ * C_ab = m_ab - m_a m_b; with fewer, the identity.  Normal: the unit eigenvector of C's smallest eigenvalue by open3d's FastEigen3x3
+ * (C scaled by its largest entry, trigonometric roots, eigenvectors from cross products of rows); its sign is free.  C with zero
+ * off-diagonals gives (1,0,0) if C00 < C11 and C00 < C22, else (0,1,0) if C11 < C00 and C11 < C22, else (0,0,1); an all-zero C gives
+ * (0,0,1).  normals [n,3] and covariances [n,3,3] (nullable, row-major) in input order.  workspace: lnr_cloud_workspace(n) bytes.
+ * counters_dev int64 [4], written by the call: {points that took the exact pass, 1 if the grid is unusable (a non-finite point, or
+ * another n), shells visited, 0}. */
+int lnr_cloud_normals(const void* grid, int64_t n_points, int32_t knn, double* normals, double* covariances, void* workspace,
+                      size_t workspace_bytes, int64_t* counters_dev, void* stream);
+
+/* GetRegistrationResultAndCorrespondences' search (open3d KDTreeFlann::SearchHybrid(r, 1)): for every query the target with the
+ * smallest (d2, index) among those with d2 < r*r (strict), found on the grid within ceil(r / edge) + 1 shells.  index int32 [n]
+ * (the target's input index, -1 for none) and sq_distance [n] (d2; +inf for none, NaN for a non-finite query).  counters_dev int64
+ * [4]: {0, non-finite queries, 0, 0}. */
+int lnr_icp_correspondences(const void* grid, int64_t n_targets, const double* queries, int64_t n_queries, double max_distance,
+                            int32_t* index, double* sq_distance, int64_t* counters_dev, void* stream);
+
+/* open3d's RegistrationICP with TransformationEstimationPointToPlane (evaluate_lidar_map.py:44-48).  grid: over the n_targets targets,
+ * target_normals [n_targets,3] in their input order; source [n_source,3]; init host [16] (row-major 4x4, bottom row 0 0 0 1).
+ * The source is copied and transformed by init (lnr_cloud_append_transformed's rounding); correspondences are taken once
+ * (lnr_icp_correspondences' rule), then up to max_iteration rounds: the update, transformation = update @ transformation (each entry
+ * ((a0 b0 + a1 b1) + a2 b2) + a3 b3), the copy transformed by update, correspondences again; the loop stops after a round with
+ * |d fitness| < relative_fitness and |d rmse| < relative_rmse.  fitness = n_corr / n_source and inlier_rmse = sqrt(sum d2 / n_corr),
+ * both 0 without a correspondence.  The update: per correspondence (s, t, n) r = (s - t).n and J = [s x n, n]; JTJ = sum J J^T and
+ * JTr = sum J r over the correspondences in source order per thread, per-block partials and one workgroup's fold, all in a fixed order
+ * (bit-identical from run to run); x = LDLT(JTJ).solve(-JTr) as Eigen's (pivoting on the largest remaining |diagonal|, a zero
+ * component where |D_i| <= DBL_MIN); update = [Rz(x2) Ry(x1) Rx(x0) | x3..x5]; no correspondence gives the identity.  Every round is
+ * enqueued without a host read; rounds after convergence return at once.  workspace: lnr_icp_workspace(n_source) bytes.
+ * result_dev fp64 [LNR_ICP_RESULT]: [0:16] transformation, [16] fitness, [17] inlier_rmse, [18:39] the last solved JTJ (upper
+ * triangle, row by row), [39:45] its JTr, [45] its sum of d2, [46:52] its x.  info_dev int64 [8]: {status, correspondences, rounds
+ * run, non-finite source points, correspondences whose target normal is non-finite, correspondences of the last solved system,
+ * converged or stopped, 0}; status bit 1: a non-finite source point, 2: the grid is unusable (a non-finite target, or another
+ * n_targets), 4: a non-finite target normal, 8: a non-finite update (the transformation keeps its last finite value). */
+size_t lnr_icp_workspace(int64_t n_source);
+int lnr_icp_point_to_plane(const void* grid, int64_t n_targets, const double* target_normals, const double* source, int64_t n_source,
+                           double max_distance, const double* init, double relative_fitness, double relative_rmse, int32_t max_iteration,
+                           void* workspace, size_t workspace_bytes, double* result_dev, int64_t* info_dev, void* stream);
+
 /* ---- loss ------------------------------------------------------------------------------------------ */
 /* get_weights_gt (losses.py:29-51); eps_ray [n] per-ray or NULL -> eps_scalar. */
 int lnr_weights_gt(const float* s /*[n,S] metres*/, const float* g /*[n] metres*/, const float* eps_ray,

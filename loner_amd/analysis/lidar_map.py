@@ -5,8 +5,13 @@ LidarMapRenderer renders a dense synthetic scan from keyframe poses through Mode
 keeps the confident rays (ops.lidar_scan_points), voxel-down-samples each scan in the sensor frame, moves it to the world frame
 while appending it to the merged cloud (ops.cloud_transform) and down-samples the merged cloud once more (renderer_lidar.py:71-91,
 :296-349).  compare_point_clouds down-samples both clouds and takes exact nearest-neighbour distances both ways on the device
-(ops.NNGrid) before deriving the reference's statistics (evaluate_lidar_map.py:58-80).  Differences from the reference, by intent:
-  * no ICP refinement of the alignment (evaluate_lidar_map.py:23-53) and no est_align.pcd / gt_align.pcd in the working directory;
+(ops.NNGrid) before deriving the reference's statistics (evaluate_lidar_map.py:58-80).  With refine_alignment=True it first refines
+the alignment by point-to-plane ICP on the device (evaluate_lidar_map.py:23-53: registration_icp, ops.icp_point_to_plane), and
+evaluate_lidar_map restates the script's entry point (:101-148) with the refinement on.  Differences from the reference, by intent:
+  * the refinement is opt-in on compare_point_clouds (on in evaluate_lidar_map); its alignment subsets follow the ascending voxel
+    order (open3d's follows its hash map), so the refined transform is not open3d's even in principle; the source normals, which no
+    output reads, are not estimated; a degenerate or non-finite solve raises instead of propagating NaN;
+  * no est_align.pcd / gt_align.pcd in the working directory;
   * voxel_down_sample returns its voxels in ascending (i_x, i_y, i_z) order; open3d's order is its hash map's;
   * a ray the cube test drops gives no point (the reference would fail to assign a shorter chunk into its fixed slice);
   * an empty cloud after down-sampling raises ValueError (the reference divides by zero), and the statistics are returned.
@@ -29,7 +34,8 @@ def _device(device):
 
 
 class PointCloud:
-    """fp64 points [n,3] on the HIP device; the part of open3d's PointCloud the evaluation uses."""
+    """fp64 points [n,3] on the HIP device; the part of open3d's PointCloud the evaluation uses.  normals [n,3] and covariances
+    [n,3,3] (fp64, on the device) are None until estimated."""
 
     def __init__(self, points=None, device=None):
         pts = torch.zeros(0, 3, dtype=torch.float64) if points is None else points
@@ -38,6 +44,40 @@ class PointCloud:
             raise ValueError(f"PointCloud: points [n,3], got {tuple(pts.shape)}")
         dev = pts.device if device is None and pts.is_cuda else _device(device)
         self.points = pts.to(device=dev, dtype=torch.float64).contiguous()
+        self.normals = None
+        self.covariances = None
+
+    def has_normals(self):
+        return self.normals is not None and len(self) > 0
+
+    def estimate_normals(self, knn=30, cell_edge=None):
+        """open3d's estimate_normals(KDTreeSearchParamKNN(knn)) (include/loner_hip.h: lnr_cloud_normals).  As open3d does, a normal
+        that points against one already present is flipped.  cell_edge: the search grid's (the normals do not depend on it)."""
+        normals = ops.NNGrid(self.points, cell_edge).normals(knn) if len(self) else torch.zeros(0, 3, dtype=torch.float64,
+                                                                                                  device=self.points.device)
+        if self.normals is not None and self.normals.shape == normals.shape:
+            flip = (normals * self.normals).sum(1, keepdim=True) < 0
+            normals = torch.where(flip, -normals, normals)
+        self.normals = normals
+        return self
+
+    def estimate_covariances(self, knn=30, cell_edge=None):
+        """open3d's estimate_covariances(KDTreeSearchParamKNN(knn)): the covariances of the k-nearest neighbourhoods."""
+        if len(self):
+            _, self.covariances = ops.NNGrid(self.points, cell_edge).normals(knn, want_covariances=True)
+        else:
+            self.covariances = torch.zeros(0, 3, 3, dtype=torch.float64, device=self.points.device)
+        return self
+
+    def uniform_down_sample(self, every_k_points):
+        """A new cloud of the points whose index i satisfies i % every_k_points == 0, in order (with their normals and covariances)."""
+        k = int(every_k_points)
+        if k < 1:
+            raise ValueError(f"uniform_down_sample: every_k_points must be >= 1, got {every_k_points!r}")
+        out = PointCloud(self.points[::k].contiguous())
+        out.normals = None if self.normals is None else self.normals[::k].contiguous()
+        out.covariances = None if self.covariances is None else self.covariances[::k].contiguous()
+        return out
 
     def __len__(self):
         return int(self.points.shape[0])
@@ -51,8 +91,18 @@ class PointCloud:
         return PointCloud(ops.voxel_down_sample(self.points, voxel_size))
 
     def transform(self, T):
-        """Applies the 4x4 affine T (widened to fp64) in place and returns self, as open3d does."""
+        """Applies the 4x4 affine T (widened to fp64) in place and returns self, as open3d does: normals are rotated by T[:3,:3]
+        (with the same rounding, a zero translation) and covariances become R C R^T."""
         ops.cloud_transform(self.points, T, out=self.points)
+        if self.normals is not None or self.covariances is not None:
+            T = np.asarray(T.detach().cpu().numpy() if torch.is_tensor(T) else T, dtype=np.float64)
+            R = np.eye(4)
+            R[:3, :3] = T[:3, :3]
+            if self.normals is not None:
+                ops.cloud_transform(self.normals, R, out=self.normals)
+            if self.covariances is not None:
+                Rd = torch.from_numpy(R[:3, :3]).to(self.covariances.device)
+                self.covariances = (Rd @ self.covariances @ Rd.T).contiguous()
         return self
 
     def compute_point_cloud_distance(self, target, cell_edge=None, stats=None):
@@ -217,19 +267,76 @@ class LidarMapRenderer:
         return cloud.voxel_down_sample(voxel_size) if voxel_size is not None else cloud
 
 
+# ---------------------------------------------------------------- alignment
+class RegistrationResult:
+    """open3d's RegistrationResult: transformation (numpy fp64 4x4), fitness, inlier_rmse, and n_correspondences and iterations
+    (rounds run)."""
+
+    def __init__(self, transformation, fitness, inlier_rmse, n_correspondences, iterations):
+        self.transformation = transformation
+        self.fitness = fitness
+        self.inlier_rmse = inlier_rmse
+        self.n_correspondences = n_correspondences
+        self.iterations = iterations
+
+    def as_dict(self):
+        return {"transformation": self.transformation.tolist(), "fitness": self.fitness, "inlier_rmse": self.inlier_rmse,
+                "n_correspondences": self.n_correspondences, "iterations": self.iterations}
+
+
+def registration_icp(source, target, max_correspondence_distance, init=np.eye(4), relative_fitness=1e-6, relative_rmse=1e-6,
+                     max_iteration=30):
+    """open3d's registration_icp(source, target, d, init, TransformationEstimationPointToPlane(),
+    ICPConvergenceCriteria(relative_fitness, relative_rmse, max_iteration)) on the device (ops.icp_point_to_plane).  The target needs
+    normals (ValueError otherwise, as open3d); the source's are not read.  The search grid's cell edge is the correspondence
+    distance."""
+    if target.normals is None:
+        raise ValueError("registration_icp: point-to-plane ICP needs the target's normals (call target.estimate_normals())")
+    r = float(max_correspondence_distance)
+    if not (np.isfinite(r) and r > 0):
+        raise ValueError(f"registration_icp: max_correspondence_distance must be finite and > 0, got {max_correspondence_distance!r}")
+    grid = ops.NNGrid(target.points, r)
+    out = ops.icp_point_to_plane(grid, target.normals, source.points.to(target.points.device), r, init, relative_fitness, relative_rmse,
+                                 max_iteration)
+    return RegistrationResult(out["transformation"], out["fitness"], out["inlier_rmse"], out["n_correspondences"], out["iterations"])
+
+
+def alignment_skip(n):
+    """evaluate_lidar_map.py:26-29: the uniform_down_sample step of a cloud of n points."""
+    return int(n / 1_000_000) if n > 1_000_000 else 1
+
+
+def refine_alignment_icp(est_scan, gt_scan):
+    """evaluate_lidar_map.py:23-53 on down-sampled clouds: the alignment subsets, the target's normals (knn 30), and 10 rounds of
+    point-to-plane ICP at 0.125 m from the identity with criteria 1e-12.  -> RegistrationResult (est_scan is not moved)."""
+    gt_alignment = gt_scan.uniform_down_sample(alignment_skip(len(gt_scan)))
+    est_alignment = est_scan.uniform_down_sample(alignment_skip(len(est_scan)))
+    print("Estimating point cloud normals")
+    gt_alignment.estimate_normals(30)
+    print("Refining alignment")
+    return registration_icp(est_alignment, gt_alignment, 0.125, np.eye(4), 1e-12, 1e-12, 10)
+
+
 # ---------------------------------------------------------------- evaluation
 def compare_point_clouds(est_scan, gt_scan, output_dir, f_score_threshold, voxel_size=0.05, write_pointclouds=False,
-                         write_gt_cloud=False, id_str=None):
+                         write_gt_cloud=False, id_str=None, refine_alignment=False, alignment=None):
     """Accuracy, completion, Chamfer distance, precision, recall and F-score of est_scan against gt_scan after down-sampling both
-    (evaluate_lidar_map.py:16-98 without the ICP refinement).  Writes {output_dir}/metrics/statistics{_id}.yaml and, when asked,
-    lidar_renders/rendered{_id}.pcd and gt{_id}.pcd; returns the statistics.  Quirks kept: precision = TP / len(accuracy), recall =
-    TP / (TP + FN) with TP counted on the estimate and FN on the ground truth, and 1e-8 in the F-score's denominator."""
+    (evaluate_lidar_map.py:16-98).  refine_alignment: first move the down-sampled estimate by point-to-plane ICP
+    (refine_alignment_icp; evaluate_lidar_map.py:23-53); alignment (a dict, optional) receives the ICP result.  Writes
+    {output_dir}/metrics/statistics{_id}.yaml and, when asked, lidar_renders/rendered{_id}.pcd and gt{_id}.pcd; returns the
+    statistics.  Quirks kept: precision = TP / len(accuracy), recall = TP / (TP + FN) with TP counted on the estimate and FN on the
+    ground truth, and 1e-8 in the F-score's denominator."""
     import yaml
     print("Downsampling clouds to voxel size", voxel_size)
     est_scan = est_scan.voxel_down_sample(voxel_size)
     gt_scan = gt_scan.voxel_down_sample(voxel_size)
     if len(est_scan) == 0 or len(gt_scan) == 0:
         raise ValueError(f"compare_point_clouds: {len(est_scan)} estimated and {len(gt_scan)} ground-truth points after down-sampling")
+    if refine_alignment:
+        reg = refine_alignment_icp(est_scan, gt_scan)
+        est_scan.transform(reg.transformation)
+        if alignment is not None:
+            alignment.update(reg.as_dict())
     print("Computing metrics")
     edge = 2.0 * voxel_size          # a cell then meets at most 27 occupied voxels of either cloud
     accuracy = est_scan.compute_point_cloud_distance(gt_scan, cell_edge=edge)
@@ -266,3 +373,33 @@ def compare_point_clouds(est_scan, gt_scan, output_dir, f_score_threshold, voxel
     with open(f"{metrics_dir}/statistics{id_suffix}.yaml", 'w+') as yaml_stats_f:
         yaml.dump(stats, yaml_stats_f, indent=2)
     return stats
+
+
+def evaluate_lidar_map(experiment_directory, gt_map, gt_trajectory=None, estimated_map=None, f_score_threshold=0.1, voxel_size=0.05,
+                       initial_transform=None, est_traj=None, alignment=None):
+    """The entry point of evaluate_lidar_map.py (:101-148) with the refinement on: reads the estimated map (default
+    {experiment_directory}/lidar_renders/render_full.pcd, else {experiment_directory}/{estimated_map}) and gt_map, rough-aligns the
+    ground truth by the inverse of initial_transform (16 numbers, row-major) or of the first pose of the TUM trajectory gt_trajectory,
+    and the estimate by the inverse of est_traj's first pose when given, then scores them (compare_point_clouds, refine_alignment=True).
+    The reference's rounding is kept: both start poses are fp32 (torch.tensor of the list; build_poses_from_df's .float()), inverted in
+    fp32 and widened.  Returns the statistics."""
+    from ..common.pose_utils import build_poses_from_df, read_tum
+    est_map_path = (f"{experiment_directory}/lidar_renders/render_full.pcd" if estimated_map is None
+                    else f"{experiment_directory}/{estimated_map}")
+    if gt_trajectory is None and initial_transform is None:
+        print("Warning: No GT trajectory provided. Can't rough align maps")
+        start_pose = torch.eye(4)
+    elif initial_transform is not None:
+        print("Using supplied initial guess to rough-align clouds")
+        start_pose = torch.tensor([float(x) for x in np.asarray(initial_transform, dtype=np.float64).reshape(-1)]).reshape(4, 4)
+    else:
+        print("Using GT Trajectory to rough-align clouds")
+        start_pose = build_poses_from_df(read_tum(gt_trajectory), False)[0][0]
+    est_map = read_point_cloud(est_map_path)
+    gt_map = read_point_cloud(gt_map)
+    if est_traj is not None:
+        start_est_pose = build_poses_from_df(read_tum(est_traj), False)[0][0]
+        est_map.transform(start_est_pose.inverse().cpu().numpy())
+    gt_map.transform(start_pose.inverse().cpu().numpy())
+    return compare_point_clouds(est_map, gt_map, experiment_directory, f_score_threshold, voxel_size, refine_alignment=True,
+                                alignment=alignment)

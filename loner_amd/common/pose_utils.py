@@ -1,13 +1,14 @@
 """WorldCube and 6-vector <-> 4x4 conversions.
 
 Mirrors the part of the reference's src/common/pose_utils.py that the mapping hot path touches:
-WorldCube (:24-57) and tensor_to_transform (:288-302).  The reference delegates the axis-angle ->
+WorldCube (:24-57), tensor_to_transform (:288-302) and build_poses_from_df (:321-343).  The reference delegates the axis-angle ->
 matrix map to pytorch3d 0.7.2 (absent here); pytorch3d's published algorithm (axis-angle -> unit
 quaternion with the small-angle series, quaternion -> matrix) is written out in stock torch ops so
 that the pose-Jacobian tail stays in torch autograd on whatever device the pose lives on.
 """
 from dataclasses import dataclass
 
+import numpy as np
 import torch
 
 
@@ -90,3 +91,49 @@ def transform_to_tensor(T: torch.Tensor, device=None) -> torch.Tensor:
     """[4,4] -> [6] (pose_utils.py:255-282)."""
     out = torch.cat([T[:3, 3].detach(), matrix_to_axis_angle(T[:3, :3]).to(T.device)]).float()
     return out.to(device) if device is not None else out
+
+
+def quat_to_matrix(quat) -> np.ndarray:
+    """scipy's Rotation.from_quat(q).as_matrix() for rows q = (x, y, z, w), in numpy fp64: each quaternion normalised first."""
+    q = np.asarray(quat, dtype=np.float64).reshape(-1, 4)
+    q = q / np.linalg.norm(q, axis=1, keepdims=True)
+    x, y, z, w = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+    x2, y2, z2, w2 = x * x, y * y, z * z, w * w
+    xy, zw, xz, yw, yz, xw = x * y, z * w, x * z, y * w, y * z, x * w
+    R = np.empty((q.shape[0], 3, 3))
+    R[:, 0, 0] = x2 - y2 - z2 + w2
+    R[:, 1, 0] = 2 * (xy + zw)
+    R[:, 2, 0] = 2 * (xz - yw)
+    R[:, 0, 1] = 2 * (xy - zw)
+    R[:, 1, 1] = -x2 + y2 - z2 + w2
+    R[:, 2, 1] = 2 * (yz + xw)
+    R[:, 0, 2] = 2 * (xz + yw)
+    R[:, 1, 2] = 2 * (yz - xw)
+    R[:, 2, 2] = -x2 - y2 + z2 + w2
+    return R
+
+
+def read_tum(path) -> np.ndarray:
+    """The rows of a TUM trajectory file (ts x y z qx qy qz qw, space separated), fp64 [n, 8]; the reference reads it with
+    pd.read_csv(path, delimiter=' ', header=None)."""
+    return np.loadtxt(path, dtype=np.float64, ndmin=2, delimiter=" ")
+
+
+def build_poses_from_df(df, zero_origin=False):
+    """The reference's build_poses_from_df (pose_utils.py:321-343) without pandas or scipy: df is a [n, 8] array of TUM rows (or
+    anything with .to_numpy()).  -> (poses fp32 [n,4,4], timestamps fp64 [n]); the poses are built in fp64 and rounded to fp32 at the
+    end, as the reference's .float() does."""
+    data = torch.from_numpy(np.asarray(df.to_numpy(dtype=np.float64) if hasattr(df, "to_numpy") else df, dtype=np.float64))
+    ts = data[:, 0]
+    xyz = data[:, 1:4]
+    rots = torch.from_numpy(quat_to_matrix(data[:, 4:].numpy()))
+    poses = torch.cat((rots, xyz.unsqueeze(2)), dim=2)
+    homog = torch.tensor([0.0, 0.0, 0.0, 1.0], dtype=torch.float64).tile((poses.shape[0], 1, 1))
+    poses = torch.cat((poses, homog), dim=1)
+    if zero_origin:
+        rot_inv = poses[0, :3, :3].T
+        t_inv = -rot_inv @ poses[0, :3, 3]
+        start_inv = torch.hstack((rot_inv, t_inv.reshape(-1, 1)))
+        start_inv = torch.vstack((start_inv, torch.tensor([0, 0, 0, 1.0], dtype=torch.float64)))
+        poses = start_inv.unsqueeze(0) @ poses
+    return poses.float(), ts

@@ -628,6 +628,87 @@ class NNGrid:
             stats.update(fallback=int(c[0]), shells=int(c[2]))
         return (dist, d2) if want_sq else dist
 
+    def normals(self, knn=30, want_covariances=False, stats=None):
+        """open3d's EstimateNormals(KDTreeSearchParamKNN(knn)) over the grid's own targets (include/loner_hip.h: lnr_cloud_normals)
+        -> normals [n,3] fp64 in the targets' order, and covariances [n,3,3] when asked; stats (a dict, optional) receives
+        {"fallback", "shells"}.  One device -> host read."""
+        knn = int(knn)
+        if not 1 <= knn <= hip.KNN_MAX:
+            raise ValueError(f"normals: knn must be in [1, {hip.KNN_MAX}], got {knn}")
+        dev = self.buf.device
+        normals = torch.empty(self.n, 3, device=dev, dtype=torch.float64)
+        cov = torch.empty(self.n, 3, 3, device=dev, dtype=torch.float64) if want_covariances else None
+        ws, need = _cloud_workspace(self.n, dev)
+        counters = torch.empty(4, device=dev, dtype=torch.int64)
+        check(load().lnr_cloud_normals(_ptr(self.buf), self.n, knn, _ptr(normals), _ptr(cov), _ptr(ws), need, _ptr(counters), _stream()),
+              "lnr_cloud_normals")
+        c = counters.cpu()
+        if int(c[1]):
+            raise RuntimeError("normals: the grid is unusable (non-finite targets)")
+        if stats is not None:
+            stats.update(fallback=int(c[0]), shells=int(c[2]))
+        return (normals, cov) if want_covariances else normals
+
+    def correspondences(self, queries, max_distance):
+        """-> (index int32 [m]: the nearest target with d2 < max_distance^2, lower index on ties, -1 for none; d2 [m] fp64, +inf for
+        none) (include/loner_hip.h: lnr_icp_correspondences)."""
+        q = _f64_points(queries, "NNGrid.correspondences")
+        r = float(max_distance)
+        if not (math.isfinite(r) and r > 0):
+            raise ValueError(f"correspondences: max_distance must be finite and > 0, got {max_distance!r}")
+        m = q.shape[0]
+        index = torch.empty(m, device=q.device, dtype=torch.int32)
+        d2 = torch.empty(m, device=q.device, dtype=torch.float64)
+        counters = torch.empty(4, device=q.device, dtype=torch.int64)
+        check(load().lnr_icp_correspondences(_ptr(self.buf), self.n, _ptr(q), m, r, _ptr(index), _ptr(d2), _ptr(counters), _stream()),
+              "lnr_icp_correspondences")
+        if int(counters[1].item()):
+            raise RuntimeError(f"correspondences: {int(counters[1].item())} queries with non-finite coordinates")
+        return index, d2
+
+
+_ICP_STATUS = {1: "non-finite source points", 2: "the target grid is unusable (non-finite targets)", 4: "non-finite target normals",
+               8: "the update is not finite (a degenerate system)"}
+
+
+def icp_point_to_plane(grid, target_normals, source, max_distance, init=None, relative_fitness=1e-6, relative_rmse=1e-6,
+                       max_iteration=30):
+    """open3d's registration_icp with TransformationEstimationPointToPlane (include/loner_hip.h: lnr_icp_point_to_plane).  grid: an
+    NNGrid over the targets; target_normals [n,3] in the targets' order; source [m,3]; init 4x4 (default identity).  -> dict with
+    transformation (numpy fp64 4x4), fitness, inlier_rmse, n_correspondences, iterations, and the last solved system (JTJ 6x6, JTr,
+    sum_d2, x).  Every round is enqueued at once; one device -> host read.  Raises RuntimeError on a status bit."""
+    import numpy as np
+    src = _f64_points(source, "icp_point_to_plane")
+    nrm = _f64_points(target_normals, "icp_point_to_plane")
+    if nrm.shape[0] != grid.n:
+        raise ValueError(f"icp_point_to_plane: {nrm.shape[0]} normals for {grid.n} targets")
+    r = float(max_distance)
+    if not (math.isfinite(r) and r > 0):
+        raise ValueError(f"icp_point_to_plane: max_correspondence_distance must be finite and > 0, got {max_distance!r}")
+    T0 = np.eye(4) if init is None else np.asarray(init.detach().cpu().numpy() if torch.is_tensor(init) else init, dtype=np.float64)
+    if T0.shape != (4, 4) or not np.array_equal(T0[3], [0.0, 0.0, 0.0, 1.0]) or not np.isfinite(T0).all():
+        raise ValueError(f"icp_point_to_plane: init must be a finite 4x4 affine matrix, got {T0.tolist()}")
+    dev = src.device
+    lib = load()
+    need = int(lib.lnr_icp_workspace(src.shape[0]))
+    ws = torch.empty(need, device=dev, dtype=torch.uint8)
+    result = torch.empty(hip.ICP_RESULT, device=dev, dtype=torch.float64)
+    info = torch.empty(8, device=dev, dtype=torch.int64)
+    t16 = (C.c_double * 16)(*[float(x) for x in T0.reshape(-1)])
+    check(lib.lnr_icp_point_to_plane(_ptr(grid.buf), grid.n, _ptr(nrm), _ptr(src), src.shape[0], r, t16, float(relative_fitness),
+                                     float(relative_rmse), int(max_iteration), _ptr(ws), need, _ptr(result), _ptr(info), _stream()),
+          "lnr_icp_point_to_plane")
+    res = result.cpu().numpy()
+    info = [int(x) for x in info.cpu()]
+    if info[0]:
+        raise RuntimeError("icp_point_to_plane: " + ", ".join(m for b, m in _ICP_STATUS.items() if info[0] & b))
+    JTJ = np.zeros((6, 6))
+    JTJ[np.triu_indices(6)] = res[18:39]
+    JTJ = JTJ + np.triu(JTJ, 1).T
+    return {"transformation": res[:16].reshape(4, 4).copy(), "fitness": float(res[16]), "inlier_rmse": float(res[17]),
+            "n_correspondences": info[1], "iterations": info[2], "JTJ": JTJ, "JTr": res[39:45].copy(), "sum_d2": float(res[45]),
+            "x": res[46:52].copy(), "system_correspondences": info[5]}
+
 
 def render_backward(sigma, z, rays, g_depth, g_weights, g_opacity, g_variance, noise=None, noise_std=0.0, seed=0,
                     n_rays_dev=None):
