@@ -156,6 +156,29 @@ size_t lnr_density_workspace(const LnrNetSpec* spec /*host*/, int64_t n_points);
  * (Model.forward(testing=True), analysis/compute_l1_depth.py:42-64) never pay for the backward's record regions. */
 size_t lnr_density_workspace_forward(const LnrNetSpec* spec /*host*/, int64_t n_points);
 
+/* Which MLP kernels lnr_density_forward (backward = 0) / lnr_density_backward (backward = 1) launch for this network at up to
+ * n_points points per call, from the same function the launch path reads.  Host only: touches no device, needs no workspace.
+ *   LNR_ROUTE_UNSUPPORTED  no kernel: the density calls return LNR_ERR_UNSUPPORTED
+ *   LNR_ROUTE_WIDE         256 neurons x 2..3 hidden layers (and 256 x 1 in fp16 mode where the fused kernels do not fit), both
+ *                          precisions: layer by layer through chunk planes in the workspace
+ *   LNR_ROUTE_F16_FAST     fp16 mode, the reference's sigma network (16 levels x 2 features -> <= 64 ReLU neurons -> 1)
+ *   LNR_ROUTE_F16_FREQ     fp16 mode, frequency encoding evaluated inside the general fp16 kernels (no feature planes)
+ *   LNR_ROUTE_F16_GEN      fp16 mode, general kernels on half2 pair planes
+ *   LNR_ROUTE_BF3          LNR_PREC_F32, the default shape class on the bf16 matrix pipe with three-term operand splits
+ *   LNR_ROUTE_FAST32       the default shape class on the register-resident fp32 kernels (LNR_PREC_F32_CHAIN, frequency encodings)
+ *   LNR_ROUTE_REGS         fp32 backward that accumulates the weight gradient in registers; w_lds: 1 all weights, 2 the hidden
+ *                          matrices, 0 none in LDS
+ *   LNR_ROUTE_LDS          general fp32 kernels; w_lds (weights in LDS), waves per workgroup and - backward - dw64 (64-bit
+ *                          fixed-point weight-gradient accumulators) name the tier that fits the LDS
+ * f16_part: the object of the general fp16 kernels that holds the kernel (0: compile-time ReLU / Sine; run-time activations:
+ * forward 1, backward 1 up to 64 neurons and 2 from 128); 0 for every other route. */
+typedef enum LnrRouteKind {
+    LNR_ROUTE_UNSUPPORTED = 0, LNR_ROUTE_WIDE = 1, LNR_ROUTE_F16_FAST = 2, LNR_ROUTE_F16_FREQ = 3, LNR_ROUTE_F16_GEN = 4,
+    LNR_ROUTE_BF3 = 5, LNR_ROUTE_FAST32 = 6, LNR_ROUTE_REGS = 7, LNR_ROUTE_LDS = 8
+} LnrRouteKind;
+typedef struct LnrDensityRoute { int32_t kind, w_lds, waves, dw64, f16_part; } LnrDensityRoute;
+int lnr_density_route(const LnrNetSpec* spec /*host*/, int64_t n_points, int32_t backward, LnrDensityRoute* out /*host*/);
+
 /* The first LNR_WORKSPACE_STATUS_BYTES of a workspace are int32 status words the kernels write and the caller may read (with
  * the device in sync) and reset; lnr_density_workspace_init zeroes them - call it once after allocating a workspace.
  *   [LNR_STATUS_CLIPPED]  number of density outputs lnr_density_forward clipped since the last reset: non-finite values - and, with

@@ -425,7 +425,7 @@ static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 // F == 1; half as many x-pair records) to the `span` owners its table covers, from bpg workgroups.  Each level's regions hold
 // that expectation + 25 % + 24 records; anything beyond it (skewed data) goes to the level's 64-bit overflow accumulators, so
 // this is a performance knob only.
-static Layout make_layout(const LnrNetSpec* spec, int64_t n_points) {
+static Layout make_layout(const LnrNetSpec* spec, int64_t n_points, const DensityRoute& route) {
     Layout L;
     L.m_pad = (n_points + 63) / 64 * 64;
     if (L.m_pad < 64) L.m_pad = 64;
@@ -495,9 +495,9 @@ static Layout make_layout(const LnrNetSpec* spec, int64_t n_points) {
     size_t off = 0;
     L.off_status = off; off += LNR_WORKSPACE_STATUS_BYTES;          // status words (include/loner_hip.h), same place for every n_points
     // (fp16 mode + frequency encoding: the MLP kernels evaluate the encoding and its input gradient themselves - no planes at all)
-    const size_t plane_set = lnr_f16_fused_freq(spec) ? 0 : (size_t)spec->enc_dim * L.m_pad * sizeof(float);
+    const size_t plane_set = route.fused_enc ? 0 : (size_t)spec->enc_dim * L.m_pad * sizeof(float);
     L.off_feat = off; off += align256(plane_set);
-    L.off_wide = off; off += align256(lnr_wide_workspace(spec, n_points));     // chunk planes of the 256 x 2..3 route (0 bytes for every other network); the forward uses them too
+    L.off_wide = off; off += align256(route.wide_bytes);     // chunk planes of the 256 x 2..3 route (0 bytes for every other network); the forward uses them too
     L.off_dfeat = off; off += align256(plane_set);
     L.off_dxl = off; off += align256(plane_set == 0 ? 0 : (size_t)L.n_groups * 3 * L.m_pad * sizeof(float));
     L.off_dpts = off; off += align256((size_t)3 * L.m_pad * sizeof(float));      // d_pts scratch of the general d_rays route
@@ -548,13 +548,11 @@ static int check_spec(const LnrNetSpec* spec, const char* who) {
     return LNR_OK;
 }
 
-// LNR_PREC_F16 is implemented for the reference's sigma network shape class; anything else must say so, not fall back
-static int check_f16(const LnrNetSpec* spec, const char* who) {
-    if (spec->precision != LNR_PREC_F16 || lnr_f16_supported(spec) || lnr_wide_class(spec)) return LNR_OK;
-    lnr_set_error("%s: precision fp16 covers networks with an even number of encoded features per level, 16/32/64/128/256 neurons, "
-                  "at most 3 hidden layers and - below 256 neurons - at most 128 (padded) inputs whose weights fit the LDS; use precision "
-                  "fp32 for this network", who);
-    return LNR_ERR_UNSUPPORTED;
+// workgroups of an MLP launch: `waves` tiles of `tile` samples each, at most max_blocks (the kernels loop over the rest)
+static int mlp_blocks(int64_t n_points, int tile, int waves, int64_t max_blocks) {
+    const int64_t tiles = (n_points + tile - 1) / tile;
+    const int64_t blocks = (tiles + waves - 1) / waves;
+    return (int)(blocks > max_blocks ? max_blocks : (blocks < 1 ? 1 : blocks));
 }
 
 static size_t fwd_lds(const LnrNetSpec* s, int w_lds) { return ((w_lds ? (size_t)lnr_w_lds_floats(s->n_neurons, s->in_dim, s->n_hidden, true) : 0) + 4) * sizeof(float); }
@@ -564,29 +562,44 @@ static size_t bwd_lds(const LnrNetSpec* s, int w_lds, int waves, int dw64) {
     return ((w_lds ? 1 : 0) * (size_t)s->n_mlp_params + (dw64 ? 2 : 1) * (size_t)s->n_mlp_params + (size_t)waves * scratch) * sizeof(float);
 }
 
-// Launch shape of the MLP kernels.  The reference's default shape class (32 encoded features -> <= 64 ReLU neurons
-// -> 1) takes the register-resident kernels; everything else prefers weights in LDS and 4 waves per workgroup and
-// falls back to fewer waves, then to weights read from global memory (L2), until the workgroup fits the 160 KB LDS
-// of a CDNA4 CU.
-static int plan_launch(const LnrNetSpec* spec, int64_t n_points, bool backward, DensityPlan* plan, const char* who) {
-    const int64_t tiles = (n_points + 15) / 16;
-    if (lnr_wide_class(spec)) {          // 256 x 2..3: the layer-by-layer route plans its own launches (lnr_density_wide.hip)
-        plan->fast32 = 0; plan->w_lds = 0; plan->waves = 4; plan->dw64 = 0; plan->regs = 0; plan->lds = 0; plan->grid = 1; plan->n_slabs = 1;
-        return LNR_OK;
+// THE dispatch of the density MLP (DensityRoute, lnr_density_api.h): which kernel family runs a network and with which launch
+// shape.  256 x 2..3 goes layer by layer; fp16 mode takes its own kernels or nothing (it says so instead of falling back); in
+// fp32 the reference's default shape class (32 encoded features -> <= 64 ReLU neurons -> 1) takes the bf16x3 / register-resident
+// kernels, and everything else prefers weights in LDS and 4 waves per workgroup and falls back to fewer waves, then to weights
+// read from global memory (L2), until the workgroup fits the 160 KB LDS of a CDNA4 CU.
+static DensityRoute lnr_route(const LnrNetSpec* spec, int64_t n_points, bool backward) {
+    DensityRoute r{};
+    r.waves = 4;
+    const bool f16 = spec->precision == LNR_PREC_F16;
+    const int64_t max_blocks = backward ? LNR_BWD_MAX_BLOCKS : LNR_DENSITY_MAX_BLOCKS;
+    auto done = [&](int kind, int grid) {
+        if (f16 && kind >= LNR_ROUTE_BF3) return DensityRoute{};          // an fp16 network the fp16 kernels do not cover: unsupported, no fall-back to fp32
+        r.kind = kind; r.grid = grid;
+        r.n_slabs = kind == LNR_ROUTE_WIDE ? 1 : grid;                     // one slab per workgroup; 256 x n folds its partial slabs into slab 0 itself
+        return r;
+    };
+    if (lnr_wide_class(spec)) {          // the layer-by-layer route sizes its own launches (lnr_density_wide.hip)
+        r.w_lds = 0;
+        r.wide_bytes = lnr_wide_workspace(spec, n_points);
+        return done(LNR_ROUTE_WIDE, 1);
+    }
+    if (f16 && lnr_f16_supported(spec)) {          // 32-sample tiles
+        if (lnr_f16_fast_class(spec)) return done(LNR_ROUTE_F16_FAST, mlp_blocks(n_points, 32, 4, max_blocks));
+        const bool compile_time_act = spec->activation == LNR_ACT_RELU || spec->activation == LNR_ACT_SINE;
+        r.f16_part = compile_time_act ? 0 : (backward && spec->n_neurons > 64 ? 2 : 1);
+        r.fused_enc = lnr_f16_fused_freq(spec);
+        // backward: one workgroup per CU (LDS), persistent over the steps
+        return done(r.fused_enc ? LNR_ROUTE_F16_FREQ : LNR_ROUTE_F16_GEN, mlp_blocks(n_points, 32, 4, backward ? 256 : max_blocks));
     }
     // (the register-resident kernels address up to 32 padded planes with 32-bit byte offsets: m_pad < 2^25, see lnr_bf3_class)
     if (spec->activation == LNR_ACT_RELU && spec->n_hidden == 1 && spec->in_dim == 32 && spec->enc_dim == 32 && spec->n_neurons <= 64 &&
         n_points <= (1ll << 25) - 2048) {
-        plan->fast32 = 1; plan->w_lds = 1; plan->waves = 4; plan->dw64 = 0; plan->regs = 0;
-        plan->lds = backward ? (2 * (size_t)spec->n_mlp_params + 4 * (size_t)spec->n_neurons * 20) * sizeof(float)
-                             : (size_t)spec->n_mlp_params * sizeof(float);
-        int64_t blocks = (tiles + 3) / 4;
-        const int64_t max_blocks = backward ? LNR_BWD_MAX_BLOCKS : LNR_DENSITY_MAX_BLOCKS;
-        plan->grid = (int)(blocks > max_blocks ? max_blocks : (blocks < 1 ? 1 : blocks));
-        plan->n_slabs = plan->grid;
-        return LNR_OK;
+        r.w_lds = 1;
+        r.lds = backward ? (2 * (size_t)spec->n_mlp_params + 4 * (size_t)spec->n_neurons * 20) * sizeof(float)
+                         : (size_t)spec->n_mlp_params * sizeof(float);
+        if (lnr_bf3_class(spec, n_points)) return done(LNR_ROUTE_BF3, mlp_blocks(n_points, 32, 4, max_blocks));
+        return done(LNR_ROUTE_FAST32, mlp_blocks(n_points, 16, 4, max_blocks));
     }
-    plan->fast32 = 0; plan->dw64 = 0; plan->regs = 0;
     // backward of a general network: the register-accumulating kernel (lnr_density_regs.h) for up to three hidden layers and 128 padded
     // inputs (256 neurons: one hidden layer) - four waves, their dZ / layer-input images in LDS, the weights too when they fit
     // (from 64 neurons up: below that the whole gradient is small enough for the LDS-accumulating kernel to win - 32 Tanh x 2: 1.5 against 2.7 ms)
@@ -594,16 +607,11 @@ static int plan_launch(const LnrNetSpec* spec, int64_t n_points, bool backward, 
         const size_t scratch = (size_t)4 * (spec->n_hidden > 1 ? 2 : 1) * spec->n_neurons * 20 * sizeof(float);       // LNR_TDZ_STRIDE rows
         const size_t weights = (size_t)lnr_w_lds_floats(spec->n_neurons, spec->in_dim, spec->n_hidden, true) * sizeof(float);       // (padded rows)
         if (scratch <= (size_t)LNR_LDS_LIMIT) {
-            plan->regs = 1; plan->waves = 4;
             // weights in LDS: all of them, else the hidden matrices + output rows (read twice per step), else none
             const size_t hidden = (size_t)lnr_w_lds_floats(spec->n_neurons, spec->in_dim, spec->n_hidden, false) * sizeof(float);
-            plan->w_lds = scratch + weights <= (size_t)LNR_LDS_LIMIT ? 1 : (spec->n_hidden > 1 && scratch + hidden <= (size_t)LNR_LDS_LIMIT ? 2 : 0);
-            plan->lds = scratch + (plan->w_lds == 1 ? weights : (plan->w_lds == 2 ? hidden : 0));
-            int64_t blocks = (tiles + 3) / 4;
-            if (blocks > 256) blocks = 256;                          // one workgroup per CU (one wave per SIMD)
-            plan->grid = (int)(blocks < 1 ? 1 : blocks);
-            plan->n_slabs = plan->grid;
-            return LNR_OK;
+            r.w_lds = scratch + weights <= (size_t)LNR_LDS_LIMIT ? 1 : (spec->n_hidden > 1 && scratch + hidden <= (size_t)LNR_LDS_LIMIT ? 2 : 0);
+            r.lds = scratch + (r.w_lds == 1 ? weights : (r.w_lds == 2 ? hidden : 0));
+            return done(LNR_ROUTE_REGS, mlp_blocks(n_points, 16, 4, 256));            // one workgroup per CU (one wave per SIMD)
         }
     }
     // {weights in LDS, waves, 64-bit fixed-point weight-gradient accumulators}.  LDS-resident weights matter most (without
@@ -615,30 +623,63 @@ static int plan_launch(const LnrNetSpec* spec, int64_t n_points, bool backward, 
         if (!backward && (waves != 4 || dw64)) continue;           // forward scratch does not depend on these
         const size_t lds = backward ? bwd_lds(spec, w_lds, waves, dw64) : fwd_lds(spec, w_lds);
         if (lds > (size_t)LNR_LDS_LIMIT) continue;
-        plan->w_lds = w_lds; plan->waves = waves; plan->lds = lds; plan->dw64 = backward ? dw64 : 0;
-        int64_t blocks = (tiles + waves - 1) / waves;
-        const int64_t max_blocks = backward ? LNR_BWD_MAX_BLOCKS : LNR_DENSITY_MAX_BLOCKS;
-        if (blocks > max_blocks) blocks = max_blocks;
-        if (blocks < 1) blocks = 1;
-        plan->grid = (int)blocks;
-        plan->n_slabs = plan->grid;
-        return LNR_OK;
+        r.w_lds = w_lds; r.waves = waves; r.lds = lds; r.dw64 = backward ? dw64 : 0;
+        return done(LNR_ROUTE_LDS, mlp_blocks(n_points, 16, waves, max_blocks));
     }
-    lnr_set_error("%s: network (n_neurons=%d, n_hidden_layers=%d, in_dim=%d: %d MLP weights) does not fit the 160 KB LDS of a CU "
-                  "even with one wave per workgroup; not supported by the fp32 kernels", who, spec->n_neurons, spec->n_hidden,
-                  spec->in_dim, spec->n_mlp_params);
+    DensityRoute none{};
+    none.lds_misfit = 1;
+    return none;
+}
+
+// LNR_ROUTE_UNSUPPORTED as the density calls report it: a legal network no kernel covers must say so, not fall back
+static int route_unsupported(const LnrNetSpec* spec, const DensityRoute& route, const char* who) {
+    if (route.lds_misfit)
+        lnr_set_error("%s: network (n_neurons=%d, n_hidden_layers=%d, in_dim=%d: %d MLP weights) does not fit the 160 KB LDS of a CU "
+                      "even with one wave per workgroup; not supported by the fp32 kernels", who, spec->n_neurons, spec->n_hidden,
+                      spec->in_dim, spec->n_mlp_params);
+    else
+        lnr_set_error("%s: precision fp16 covers networks with an even number of encoded features per level, 16/32/64/128/256 neurons, "
+                      "at most 3 hidden layers and - below 256 neurons - at most 128 (padded) inputs whose weights fit the LDS; use precision "
+                      "fp32 for this network", who);
     return LNR_ERR_UNSUPPORTED;
 }
 
-// mlp_backward_regs_kernel: one translation unit per (width, depth)
-static int mlp_bwd_regs(const LnrNetSpec* spec, const float* params, const float* feat, int64_t m_pad, const MlpPoints* pt, const float* d_sigma,
-                        float* dfeat, float* slabs, int want_dfeat, const DensityPlan* plan, hipStream_t st) {
-#define LNR_REGS_CASE(HT, NH) case (HT) * 4 + (NH): return lnr_mlp_bwd_regs_ht##HT##_nh##NH(spec, params, feat, m_pad, pt, d_sigma, dfeat, slabs, want_dfeat, plan, st)
-    switch ((spec->n_neurons / 16) * 4 + spec->n_hidden) {
+extern "C" int lnr_density_route(const LnrNetSpec* spec, int64_t n_points, int32_t backward, LnrDensityRoute* out) {
+    int rc = check_spec(spec, "lnr_density_route");
+    if (rc) return rc;
+    LNR_REQUIRE(out != nullptr && n_points >= 0, "lnr_density_route: bad argument");
+    const DensityRoute r = lnr_route(spec, n_points, backward != 0);
+    *out = LnrDensityRoute{r.kind, r.w_lds, r.waves, r.dw64, r.f16_part};
+    return LNR_OK;
+}
+
+// the fp32 kernels on feature planes: one translation unit per width (forward, LDS-accumulating backward) / per (width, depth)
+// (mlp_backward_regs_kernel)
+static int mlp_fwd_ht(const MlpArgs& a) {
+    switch (a.spec->n_neurons / 16) {
+        case 1: return lnr_mlp_fwd_ht1(a);
+        case 2: return lnr_mlp_fwd_ht2(a);
+        case 4: return lnr_mlp_fwd_ht4(a);
+        case 8: return lnr_mlp_fwd_ht8(a);
+        default: return lnr_mlp_fwd_ht16(a);
+    }
+}
+static int mlp_bwd_ht(const MlpArgs& a) {
+    switch (a.spec->n_neurons / 16) {
+        case 1: return lnr_mlp_bwd_ht1(a);
+        case 2: return lnr_mlp_bwd_ht2(a);
+        case 4: return lnr_mlp_bwd_ht4(a);
+        case 8: return lnr_mlp_bwd_ht8(a);
+        default: return lnr_mlp_bwd_ht16(a);
+    }
+}
+static int mlp_bwd_regs(const MlpArgs& a) {
+#define LNR_REGS_CASE(HT, NH) case (HT) * 4 + (NH): return lnr_mlp_bwd_regs_ht##HT##_nh##NH(a)
+    switch ((a.spec->n_neurons / 16) * 4 + a.spec->n_hidden) {
         LNR_REGS_CASE(4, 1); LNR_REGS_CASE(4, 2); LNR_REGS_CASE(4, 3);
         LNR_REGS_CASE(8, 1); LNR_REGS_CASE(8, 2); LNR_REGS_CASE(8, 3);
         LNR_REGS_CASE(16, 1);
-        default: lnr_set_error("lnr_density_backward: no register-accumulating kernel for %d neurons x %d hidden layers", spec->n_neurons, spec->n_hidden); return LNR_ERR_UNSUPPORTED;
+        default: lnr_set_error("lnr_density_backward: no register-accumulating kernel for %d neurons x %d hidden layers", a.spec->n_neurons, a.spec->n_hidden); return LNR_ERR_UNSUPPORTED;
     }
 #undef LNR_REGS_CASE
 }
@@ -701,12 +742,12 @@ static int make_src(PointSrc* s, MlpPoints* mp, const float* pts, int64_t n_poin
 
 extern "C" size_t lnr_density_workspace(const LnrNetSpec* spec, int64_t n_points) {
     if (!spec || n_points < 0) return 0;
-    return make_layout(spec, n_points).total;
+    return make_layout(spec, n_points, lnr_route(spec, n_points, true)).total;
 }
 
 extern "C" size_t lnr_density_workspace_forward(const LnrNetSpec* spec, int64_t n_points) {
     if (!spec || n_points < 0) return 0;
-    return make_layout(spec, n_points).off_dfeat;          // status words + feature planes: all the forward touches
+    return make_layout(spec, n_points, lnr_route(spec, n_points, false)).off_dfeat;          // status words + feature planes: all the forward touches
 }
 
 extern "C" int lnr_density_workspace_init(void* workspace, size_t workspace_bytes, void* stream) {
@@ -737,7 +778,8 @@ extern "C" int lnr_density_forward(const LnrNetSpec* spec, const float* params, 
     const int64_t cap = mp.n_points;
     if (cap == 0) return LNR_OK;
     LNR_REQUIRE(params && sigma && workspace, "lnr_density_forward: null params/sigma/workspace");
-    const Layout L = make_layout(spec, cap);
+    const DensityRoute route = lnr_route(spec, cap, false);
+    const Layout L = make_layout(spec, cap, route);
     // (the limit is on the PADDED plane stride - the sample count rounded up to 64, plus the skew: ADVICE r5)
     LNR_REQUIRE(L.m_pad * (spec->n_features > 4 ? spec->n_features : 4) < (1ll << 30),
                 "lnr_density_forward: too many points per call for 32-bit plane offsets (padded n_points * max(n_features, 4) must be < 2^30)");
@@ -745,51 +787,28 @@ extern "C" int lnr_density_forward(const LnrNetSpec* spec, const float* params, 
         lnr_set_error("lnr_density_forward: workspace %zu < %zu (lnr_density_workspace_forward)", workspace_bytes, L.off_dfeat);
         return LNR_ERR_WORKSPACE;
     }
-    const bool f16 = spec->precision == LNR_PREC_F16;
-    rc = check_f16(spec, "lnr_density_forward");
-    if (rc) return rc;
-    DensityPlan plan;
-    rc = plan_launch(spec, cap, false, &plan, "lnr_density_forward");
-    if (rc) return rc;
+    if (route.kind == LNR_ROUTE_UNSUPPORTED) return route_unsupported(spec, route, "lnr_density_forward");
     hipStream_t st = (hipStream_t)stream;
     ws_touch(workspace, layout_signature(spec, cap));
     float* feat = (float*)((char*)workspace + L.off_feat);
     mp.clip_flag = reinterpret_cast<int32_t*>((char*)workspace + L.off_status) + LNR_STATUS_CLIPPED;
-    const bool fused_freq = lnr_f16_fused_freq(spec);          // the MLP kernel evaluates the encoding itself: no encode launch, no planes
-    if (!fused_freq) {
+    if (!route.fused_enc) {
         LnrProfScope prof("encode_forward", st);
-        rc = lnr_encode_forward(spec, params, &src, cap, feat, L.m_pad, f16, st);
+        rc = lnr_encode_forward(spec, params, &src, cap, feat, L.m_pad, spec->precision == LNR_PREC_F16, st);
     }
     if (rc) return rc;
     LNR_CHECK_LAUNCH("lnr_density_forward(encode)");
     LnrProfScope prof_mlp("mlp_forward", st);
-    if (lnr_wide_class(spec)) {
-        rc = lnr_mlp_fwd_wide(spec, params, feat, L.m_pad, &mp, sigma, (char*)workspace + L.off_wide, st);
-        if (rc) return rc;
-        LNR_CHECK_LAUNCH("lnr_density_forward(mlp 256 x n)");
-        return LNR_OK;
-    }
-    if (f16) {
-        rc = lnr_mlp_fwd_f16(spec, params, feat, L.m_pad, &mp, sigma, &src, st);
-        if (rc) return rc;
-        LNR_CHECK_LAUNCH("lnr_density_forward(mlp f16)");
-        return LNR_OK;
-    }
-    if (lnr_bf3_class(spec, cap)) {
-        rc = lnr_mlp_fwd_bf3(spec, params, feat, L.m_pad, &mp, sigma, st);
-        if (rc) return rc;
-        LNR_CHECK_LAUNCH("lnr_density_forward(mlp bf16x3)");
-        return LNR_OK;
-    }
-    switch (spec->n_neurons / 16) {
-        case 1: rc = lnr_mlp_fwd_ht1(spec, params, feat, L.m_pad, &mp, sigma, &plan, st); break;
-        case 2: rc = lnr_mlp_fwd_ht2(spec, params, feat, L.m_pad, &mp, sigma, &plan, st); break;
-        case 4: rc = lnr_mlp_fwd_ht4(spec, params, feat, L.m_pad, &mp, sigma, &plan, st); break;
-        case 8: rc = lnr_mlp_fwd_ht8(spec, params, feat, L.m_pad, &mp, sigma, &plan, st); break;
-        default: rc = lnr_mlp_fwd_ht16(spec, params, feat, L.m_pad, &mp, sigma, &plan, st); break;
+    const MlpArgs a{spec, &route, params, feat, L.m_pad, &mp, sigma, nullptr, nullptr, nullptr, 0, 0, &src, nullptr, (char*)workspace + L.off_wide, st};
+    const char* what;
+    switch (route.kind) {
+        case LNR_ROUTE_WIDE: rc = lnr_mlp_fwd_wide(a); what = "lnr_density_forward(mlp 256 x n)"; break;
+        case LNR_ROUTE_F16_FAST: case LNR_ROUTE_F16_FREQ: case LNR_ROUTE_F16_GEN: rc = lnr_mlp_fwd_f16(a); what = "lnr_density_forward(mlp f16)"; break;
+        case LNR_ROUTE_BF3: rc = lnr_mlp_fwd_bf3(a); what = "lnr_density_forward(mlp bf16x3)"; break;
+        default: rc = mlp_fwd_ht(a); what = "lnr_density_forward(mlp)"; break;          // LNR_ROUTE_FAST32, LNR_ROUTE_LDS
     }
     if (rc) return rc;
-    LNR_CHECK_LAUNCH("lnr_density_forward(mlp)");
+    LNR_CHECK_LAUNCH(what);
     return LNR_OK;
 }
 
@@ -817,16 +836,15 @@ extern "C" int lnr_density_backward(const LnrNetSpec* spec, const float* params,
     if (cap == 0) return empty_batch();
     LNR_REQUIRE(params && d_sigma && workspace, "lnr_density_backward: null argument");
     LNR_REQUIRE(grad_params || d_pts || d_rays, "lnr_density_backward: nothing to compute (no grad_params, d_pts or d_rays)");
-    const Layout L = make_layout(spec, cap);
+    const DensityRoute route = lnr_route(spec, cap, true);
+    const Layout L = make_layout(spec, cap, route);
     LNR_REQUIRE(L.m_pad * (spec->n_features > 4 ? spec->n_features : 4) < (1ll << 30),
                 "lnr_density_backward: too many points per call for 32-bit plane offsets (padded n_points * max(n_features, 4) must be < 2^30)");
     if (workspace_bytes < L.total) {
         lnr_set_error("lnr_density_backward: workspace %zu < %zu (lnr_density_workspace)", workspace_bytes, L.total);
         return LNR_ERR_WORKSPACE;
     }
-    DensityPlan plan;
-    rc = plan_launch(spec, cap, true, &plan, "lnr_density_backward");
-    if (rc) return rc;
+    if (route.kind == LNR_ROUTE_UNSUPPORTED) return route_unsupported(spec, route, "lnr_density_backward");
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     float* feat = (float*)(ws + L.off_feat);
@@ -844,15 +862,12 @@ extern "C" int lnr_density_backward(const LnrNetSpec* spec, const float* params,
         for (int l = 0; l < LNR_MAX_LEVELS; ++l) rplan.bytes[l] = 0;
     if (!(flags & LNR_BWD_BINS))
         for (int l = 0; l < LNR_MAX_LEVELS; ++l) rplan.binned[l] = 0;
-    const bool f16 = spec->precision == LNR_PREC_F16;
-    rc = check_f16(spec, "lnr_density_backward");
-    if (rc) return rc;
     const bool want_grad = grad_params != nullptr;
 
-    const bool fused_freq = lnr_f16_fused_freq(spec);          // encoding and its input gradient inside the MLP backward kernel
+    const bool fused_freq = route.fused_enc;          // encoding and its input gradient inside the MLP backward kernel
     if (!reuse_features && !fused_freq) {
         LnrProfScope prof("encode_forward", st);
-        rc = lnr_encode_forward(spec, params, &src, cap, feat, L.m_pad, f16, st);
+        rc = lnr_encode_forward(spec, params, &src, cap, feat, L.m_pad, spec->precision == LNR_PREC_F16, st);
         if (rc) return rc;
         LNR_CHECK_LAUNCH("lnr_density_backward(encode)");
     }
@@ -865,19 +880,15 @@ extern "C" int lnr_density_backward(const LnrNetSpec* spec, const float* params,
     float* d_pts_eff = d_pts;
     if (d_rays && !ray_accum) d_pts_eff = (float*)(ws + L.off_dpts);
     const int want_dfeat = ((hash && want_grad) || d_pts_eff != nullptr || ray_accum) ? 1 : 0;
-    int n_slabs = plan.n_slabs;
     {
     LnrProfScope prof("mlp_backward", st);
-    if (lnr_wide_class(spec)) rc = lnr_mlp_bwd_wide(spec, params, feat, L.m_pad, &mp, d_sigma, dfeat, slabs, want_dfeat, want_grad ? 1 : 0, &n_slabs, ws + L.off_wide, st);
-    else if (f16) rc = lnr_mlp_bwd_f16(spec, params, feat, L.m_pad, &mp, d_sigma, dfeat, slabs, want_dfeat, &n_slabs, &src, d_pts_eff, st);
-    else if (lnr_bf3_class(spec, cap)) rc = lnr_mlp_bwd_bf3(spec, params, feat, L.m_pad, &mp, d_sigma, dfeat, slabs, want_dfeat, &n_slabs, st);
-    else if (plan.regs) rc = mlp_bwd_regs(spec, params, feat, L.m_pad, &mp, d_sigma, dfeat, slabs, want_dfeat, &plan, st);
-    else switch (spec->n_neurons / 16) {
-        case 1: rc = lnr_mlp_bwd_ht1(spec, params, feat, L.m_pad, &mp, d_sigma, dfeat, slabs, want_dfeat, &plan, st); break;
-        case 2: rc = lnr_mlp_bwd_ht2(spec, params, feat, L.m_pad, &mp, d_sigma, dfeat, slabs, want_dfeat, &plan, st); break;
-        case 4: rc = lnr_mlp_bwd_ht4(spec, params, feat, L.m_pad, &mp, d_sigma, dfeat, slabs, want_dfeat, &plan, st); break;
-        case 8: rc = lnr_mlp_bwd_ht8(spec, params, feat, L.m_pad, &mp, d_sigma, dfeat, slabs, want_dfeat, &plan, st); break;
-        default: rc = lnr_mlp_bwd_ht16(spec, params, feat, L.m_pad, &mp, d_sigma, dfeat, slabs, want_dfeat, &plan, st); break;
+    const MlpArgs a{spec, &route, params, feat, L.m_pad, &mp, nullptr, d_sigma, dfeat, slabs, want_dfeat, want_grad ? 1 : 0, &src, d_pts_eff, ws + L.off_wide, st};
+    switch (route.kind) {
+        case LNR_ROUTE_WIDE: rc = lnr_mlp_bwd_wide(a); break;
+        case LNR_ROUTE_F16_FAST: case LNR_ROUTE_F16_FREQ: case LNR_ROUTE_F16_GEN: rc = lnr_mlp_bwd_f16(a); break;
+        case LNR_ROUTE_BF3: rc = lnr_mlp_bwd_bf3(a); break;
+        case LNR_ROUTE_REGS: rc = mlp_bwd_regs(a); break;
+        default: rc = mlp_bwd_ht(a); break;          // LNR_ROUTE_FAST32, LNR_ROUTE_LDS
     }
     }
     if (rc) return rc;
@@ -902,7 +913,7 @@ extern "C" int lnr_density_backward(const LnrNetSpec* spec, const float* params,
     const bool fold_in_reduce = want_grad && hash && L.nown > 0 && !(flags & LNR_BWD_DEFER_WEIGHT_FOLD);
     ReduceCtx rctx{spec, regions, counts, ovf, ovf_flag, epoch, grad_table, rplan, L.bpg, L.maxo, L.shift, spec->n_params - spec->n_mlp_params,
                    (flags & LNR_BWD_TABLE_ATOMICS) ? 0 : L.n_split, (flags & LNR_BWD_OVERWRITE_GRAD) ? 1 : 0,
-                   fold_in_reduce ? slabs : nullptr, n_slabs, spec->n_mlp_params, grad_params};
+                   fold_in_reduce ? slabs : nullptr, route.n_slabs, spec->n_mlp_params, grad_params};
     // hash grids (LNR_SPLIT_DX): the input gradient first, as launches of its own; the table-gradient partition follows behind the event
     const bool split = LNR_SPLIT_DX && hash;
     if (want_dfeat && !fused_freq) {
@@ -956,7 +967,7 @@ extern "C" int lnr_density_backward(const LnrNetSpec* spec, const float* params,
     if ((flags & LNR_BWD_DEFER_WEIGHT_FOLD) || fold_in_reduce) return LNR_OK;      // the caller folds them (lnr_density_fold_weight_grads) / done above
     const int n_mlp = spec->n_mlp_params;
     LnrProfScope prof_slabs("reduce_slabs", st);
-    hipLaunchKernelGGL(reduce_slabs_kernel, dim3(lnr_div_up(n_mlp, 64)), dim3(64 * LNR_SLAB_GROUPS), 0, st, slabs, n_slabs, n_mlp, grad_params,
+    hipLaunchKernelGGL(reduce_slabs_kernel, dim3(lnr_div_up(n_mlp, 64)), dim3(64 * LNR_SLAB_GROUPS), 0, st, slabs, route.n_slabs, n_mlp, grad_params,
                        (flags & LNR_BWD_OVERWRITE_GRAD) ? 1 : 0);
     LNR_CHECK_LAUNCH("lnr_density_backward(reduce)");
     return LNR_OK;
@@ -967,23 +978,15 @@ extern "C" int lnr_density_fold_weight_grads(const LnrNetSpec* spec, int64_t n_p
     int rc = check_spec(spec, "lnr_density_fold_weight_grads");
     if (rc) return rc;
     LNR_REQUIRE(grad_params && workspace && n_points > 0, "lnr_density_fold_weight_grads: bad argument");
-    const Layout L = make_layout(spec, n_points);
+    const DensityRoute route = lnr_route(spec, n_points, true);          // the route of the backward whose slabs these are
+    const Layout L = make_layout(spec, n_points, route);
     LNR_REQUIRE(workspace_bytes >= L.total, "lnr_density_fold_weight_grads: workspace too small");
-    int n_slabs;
-    if (lnr_wide_class(spec)) n_slabs = 1;
-    else if (spec->precision == LNR_PREC_F16) n_slabs = lnr_f16_bwd_slabs(spec, n_points);
-    else if (lnr_bf3_class(spec, n_points)) n_slabs = lnr_bf3_bwd_slabs(spec, n_points);
-    else {
-        DensityPlan plan;
-        rc = plan_launch(spec, n_points, true, &plan, "lnr_density_fold_weight_grads");
-        if (rc) return rc;
-        n_slabs = plan.n_slabs;
-    }
+    if (route.kind == LNR_ROUTE_UNSUPPORTED) return route_unsupported(spec, route, "lnr_density_fold_weight_grads");
     const int n_mlp = spec->n_mlp_params;
     hipStream_t st = (hipStream_t)stream;
     LnrProfScope prof_slabs("reduce_slabs", st);
     hipLaunchKernelGGL(reduce_slabs_kernel, dim3(lnr_div_up(n_mlp, 64)), dim3(64 * LNR_SLAB_GROUPS), 0, st,
-                       (const float*)((const char*)workspace + L.off_slabs), n_slabs, n_mlp, grad_params, (flags & LNR_BWD_OVERWRITE_GRAD) ? 1 : 0);
+                       (const float*)((const char*)workspace + L.off_slabs), route.n_slabs, n_mlp, grad_params, (flags & LNR_BWD_OVERWRITE_GRAD) ? 1 : 0);
     LNR_CHECK_LAUNCH("lnr_density_fold_weight_grads");
     return LNR_OK;
 }

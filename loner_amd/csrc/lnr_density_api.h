@@ -130,22 +130,27 @@ static inline bool lnr_level_can_use_xpairs(const LnrNetSpec& s, int l, float sc
            ((s.level_offset[l] * 2u) & ((1u << LNR_SLICE_SHIFT) - 1u)) == 0u;      // owner slices aligned with the level: low index bits stay inside a slice
 }
 
-// launch plan chosen by the dispatcher
 // padded LDS copies of the weight matrices (lnr_density_impl.h: lnr_fill_w_lds): row stride and total size in floats
 __host__ __device__ inline int lnr_w_stride(int cols) { return cols + 4; }
 __host__ __device__ inline int lnr_w_lds_floats(int H, int in_dim, int n_hidden, bool with_first) {
     return (with_first ? H * lnr_w_stride(in_dim) : 0) + (n_hidden - 1) * H * lnr_w_stride(H) + 16 * H;
 }
 
-struct DensityPlan {
-    int grid;        // workgroups
-    int waves;       // waves per workgroup (1, 2 or 4)
-    int w_lds;       // 1: MLP matrices staged in LDS, 0: read from global memory (regs kernel also 2: all but the first layer's in LDS)
-    size_t lds;      // dynamic LDS bytes
-    int fast32;      // 1: the register-resident kernels for 32 features -> <= 64 ReLU neurons -> 1
-    int dw64;        // general backward: weight gradients accumulate in LDS in 64-bit fixed point (1) or fp32 (0)
-    int regs;        // backward: 1 = mlp_backward_regs_kernel (weight gradient in registers, owned by rows; lnr_density_regs.h)
-    int n_slabs;     // weight-gradient slabs the backward writes
+// Which kernels a density network runs on and with which launch shape: decided ONCE per call by lnr_route (lnr_density.hip) from
+// (spec, n_points, backward).  Forward, backward, the weight-gradient fold, the workspace layout and every family launcher read
+// this; none of them decides again.  lnr_density_route (include/loner_hip.h) reports it.
+struct DensityRoute {
+    int kind;            // LNR_ROUTE_* (include/loner_hip.h)
+    int lds_misfit;      // LNR_ROUTE_UNSUPPORTED: 1 = no tier of the fp32 kernels fits the LDS, 0 = fp16 mode does not cover the shape
+    int grid;            // workgroups of the MLP launch (general fp16 forward: at most; its kernels cap it at what the chip holds)
+    int waves;           // waves per workgroup (1, 2 or 4)
+    int w_lds;           // 1: MLP matrices staged in LDS, 0: read from global memory (regs kernel also 2: all but the first layer's in LDS)
+    int dw64;            // LNR_ROUTE_LDS backward: weight gradients accumulate in LDS in 64-bit fixed point (1) or fp32 (0)
+    size_t lds;          // dynamic LDS bytes of the fp32 kernels (the fp16 and bf16x3 kernels' are constants of their instantiations)
+    int n_slabs;         // weight-gradient slabs the backward writes and the fold sums
+    int f16_part;        // general fp16 kernels: the LNR_FWD_PART / LNR_BWD_PART object that holds the kernel
+    bool fused_enc;      // the MLP kernels evaluate the encoding (and its input gradient) themselves: no encode launches, no planes
+    size_t wide_bytes;   // chunk planes of the 256 x n route in the workspace (0 for every other route)
 };
 
 // point count description for the MLP kernels (features come from planes)
@@ -156,16 +161,27 @@ struct MlpPoints {
     int32_t* clip_flag;          // workspace status word: number of sigma outputs clipped by the forward kernels (nullable)
 };
 
-#define LNR_DECLARE_HT(HT)                                                                                              \
-    int lnr_mlp_fwd_ht##HT(const LnrNetSpec* spec, const float* params, const float* feat, int64_t m_pad, const MlpPoints* pt, \
-                           float* sigma, const DensityPlan* plan, hipStream_t st);                                      \
-    int lnr_mlp_bwd_ht##HT(const LnrNetSpec* spec, const float* params, const float* feat, int64_t m_pad, const MlpPoints* pt, \
-                           const float* d_sigma, float* dfeat, float* slabs, int want_dfeat, const DensityPlan* plan,   \
-                           hipStream_t st);
-#define LNR_DECLARE_REGS(HT, NH)                                                                                        \
-    int lnr_mlp_bwd_regs_ht##HT##_nh##NH(const LnrNetSpec* spec, const float* params, const float* feat, int64_t m_pad, \
-                                         const MlpPoints* pt, const float* d_sigma, float* dfeat, float* slabs,         \
-                                         int want_dfeat, const DensityPlan* plan, hipStream_t st);
+// what a family launcher receives: one MLP forward (sigma) or backward (d_sigma .. d_pts) on feature planes
+struct MlpArgs {
+    const LnrNetSpec* spec;
+    const DensityRoute* route;
+    const float* params;
+    const float* feat;           // feature planes [enc_dim][m_pad] (fp16 mode: half2 pair planes); unused when route->fused_enc
+    int64_t m_pad;
+    const MlpPoints* pt;
+    float* sigma;                // forward
+    const float* d_sigma;        // backward from here on
+    float* dfeat;
+    float* slabs;
+    int want_dfeat, want_dw;
+    const PointSrc* src;         // the points the planes were encoded from (read by the fused-encoding kernels only)
+    float* d_pts;                // fused encoding: the input gradient [n][3] (nullable)
+    void* planes;                // 256 x n route: its chunk planes
+    hipStream_t st;
+};
+
+#define LNR_DECLARE_HT(HT) int lnr_mlp_fwd_ht##HT(const MlpArgs& a); int lnr_mlp_bwd_ht##HT(const MlpArgs& a);
+#define LNR_DECLARE_REGS(HT, NH) int lnr_mlp_bwd_regs_ht##HT##_nh##NH(const MlpArgs& a);
 LNR_DECLARE_REGS(4, 1) LNR_DECLARE_REGS(4, 2) LNR_DECLARE_REGS(4, 3)
 LNR_DECLARE_REGS(8, 1) LNR_DECLARE_REGS(8, 2) LNR_DECLARE_REGS(8, 3)
 LNR_DECLARE_REGS(16, 1)
@@ -205,32 +221,26 @@ struct RegionPlan {
 int lnr_encode_forward(const LnrNetSpec* spec, const float* params, const PointSrc* src, int64_t cap_points, float* feat,
                        int64_t m_pad, bool half_planes, hipStream_t st);
 
-// fp16-storage MLP kernels (lnr_density_f16.hip): features arrive as half2 planes [level][m_pad]
+// The per-family predicates and sizes below are lnr_route's inputs: nothing else calls them.
+// fp16-storage MLP kernels (lnr_density_f16.hip): features arrive as half2 pair planes [level][m_pad]
 bool lnr_f16_supported(const LnrNetSpec* spec);
+bool lnr_f16_fast_class(const LnrNetSpec* spec);      // the reference's sigma network: 16 levels x 2 -> <= 64 ReLU neurons -> 1
 // fp16 mode + frequency encoding (up to 16 frequencies): the encoding is evaluated inside the MLP kernels (lnr_f16_freq.h) - no
 // encode launches, no feature / d_feature planes; the backward writes d_pts itself
 bool lnr_f16_fused_freq(const LnrNetSpec* spec);
-int lnr_mlp_fwd_f16(const LnrNetSpec* spec, const float* params, const void* featp, int64_t m_pad, const MlpPoints* pt, float* sigma,
-                    const PointSrc* src, hipStream_t st);
-int lnr_mlp_bwd_f16(const LnrNetSpec* spec, const float* params, const void* featp, int64_t m_pad, const MlpPoints* pt, const float* d_sigma,
-                    float* dfeat, float* slabs, int want_dfeat, int* n_slabs, const PointSrc* src, float* d_pts, hipStream_t st);
-int lnr_f16_bwd_slabs(const LnrNetSpec* spec, int64_t n_points);
+int lnr_mlp_fwd_f16(const MlpArgs& a);
+int lnr_mlp_bwd_f16(const MlpArgs& a);
 int lnr_selftest_mfma_f16(float* out, hipStream_t st);
 // fp32 mode, default shape class, on the bf16 matrix pipe with three-term operand splits (lnr_density_bf3.hip)
 bool lnr_bf3_class(const LnrNetSpec* spec, int64_t n_points);
-int lnr_mlp_fwd_bf3(const LnrNetSpec* spec, const float* params, const float* feat, int64_t m_pad, const MlpPoints* pt, float* sigma, hipStream_t st);
-int lnr_mlp_bwd_bf3(const LnrNetSpec* spec, const float* params, const float* feat, int64_t m_pad, const MlpPoints* pt, const float* d_sigma,
-                    float* dfeat, float* slabs, int want_dfeat, int* n_slabs, hipStream_t st);
-int lnr_bf3_bwd_slabs(const LnrNetSpec* spec, int64_t n_points);
+int lnr_mlp_fwd_bf3(const MlpArgs& a);
+int lnr_mlp_bwd_bf3(const MlpArgs& a);
 int lnr_selftest_mfma_bf3(float* out, hipStream_t st);
 // 256 neurons x 2..3 hidden layers, both precisions: layer by layer through chunk planes in the workspace (lnr_density_wide.hip)
 bool lnr_wide_class(const LnrNetSpec* spec);
-size_t lnr_wide_workspace(const LnrNetSpec* spec, int64_t n_points);
-int lnr_wide_slabs(void);
-int lnr_mlp_fwd_wide(const LnrNetSpec* spec, const float* params, const float* feat, int64_t m_pad, const MlpPoints* pt, float* sigma,
-                     void* planes, hipStream_t st);
-int lnr_mlp_bwd_wide(const LnrNetSpec* spec, const float* params, const float* feat, int64_t m_pad, const MlpPoints* pt, const float* d_sigma,
-                     float* dfeat, float* slabs, int want_dfeat, int want_dw, int* n_slabs, void* planes, hipStream_t st);
+size_t lnr_wide_workspace(const LnrNetSpec* spec, int64_t n_points);     // bytes of chunk planes for calls of up to n_points points
+int lnr_mlp_fwd_wide(const MlpArgs& a);
+int lnr_mlp_bwd_wide(const MlpArgs& a);
 int lnr_encode_backward(const LnrNetSpec* spec, const float* params, const PointSrc* src, int64_t cap_points, const float* dfeat,
                         float* dxl, int64_t m_pad, float* grad_table, void* regions, const RegionPlan* plan, int* counts, int bpg,
                         int maxo, int shift, long long* ovf, int* ovf_flag, int epoch, float* d_pts, float* d_rays_acc, long long* ray_acc, bool bins_w8, int parts,

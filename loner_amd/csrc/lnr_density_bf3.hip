@@ -402,14 +402,11 @@ bool lnr_bf3_class(const LnrNetSpec* spec, int64_t n_points) {
            n_points <= (1ll << 25) - 2048;
 }
 
-int lnr_mlp_fwd_bf3(const LnrNetSpec* spec, const float* params, const float* feat, int64_t m_pad, const MlpPoints* pt, float* sigma, hipStream_t st) {
-    const int64_t tiles = (pt->n_points + 31) / 32;
-    int64_t blocks = (tiles + 3) / 4;
-    if (blocks > LNR_DENSITY_MAX_BLOCKS) blocks = LNR_DENSITY_MAX_BLOCKS;
-    if (blocks < 1) blocks = 1;
-    const dim3 grid((unsigned)blocks), block(LNR_DENSITY_BLOCK);
-#define LNR_BF3_FWD(HT) hipLaunchKernelGGL(mlp_forward_bf3_kernel<HT>, grid, block, 0, st, params, feat, m_pad, pt->n_points, pt->n_rays_dev, pt->n_rays, pt->n_samples, sigma, pt->clip_flag)
-    switch (spec->n_neurons / 16) {
+int lnr_mlp_fwd_bf3(const MlpArgs& a) {
+    const MlpPoints* pt = a.pt;
+    const dim3 grid((unsigned)a.route->grid), block(LNR_DENSITY_BLOCK);
+#define LNR_BF3_FWD(HT) hipLaunchKernelGGL(mlp_forward_bf3_kernel<HT>, grid, block, 0, a.st, a.params, a.feat, a.m_pad, pt->n_points, pt->n_rays_dev, pt->n_rays, pt->n_samples, a.sigma, pt->clip_flag)
+    switch (a.spec->n_neurons / 16) {
         case 1: LNR_BF3_FWD(1); break;
         case 2: LNR_BF3_FWD(2); break;
         default: LNR_BF3_FWD(4); break;
@@ -418,29 +415,17 @@ int lnr_mlp_fwd_bf3(const LnrNetSpec* spec, const float* params, const float* fe
     return LNR_OK;
 }
 
-// weight-gradient slabs lnr_mlp_bwd_bf3 writes for up to n_points points (one per workgroup)
-int lnr_bf3_bwd_slabs(const LnrNetSpec* spec, int64_t n_points) {
-    (void)spec;
-    const int64_t tiles = (n_points + 31) / 32;
-    int64_t blocks = (tiles + 3) / 4;
-    if (blocks > LNR_BWD_MAX_BLOCKS) blocks = LNR_BWD_MAX_BLOCKS;
-    if (blocks < 1) blocks = 1;
-    return (int)blocks;
-}
-
-int lnr_mlp_bwd_bf3(const LnrNetSpec* spec, const float* params, const float* feat, int64_t m_pad, const MlpPoints* pt, const float* d_sigma,
-                    float* dfeat, float* slabs, int want_dfeat, int* n_slabs, hipStream_t st) {
-    const int blocks = lnr_bf3_bwd_slabs(spec, pt->n_points);
-    *n_slabs = blocks;
-    const dim3 grid((unsigned)blocks), block(LNR_DENSITY_BLOCK);
+int lnr_mlp_bwd_bf3(const MlpArgs& a) {
+    const MlpPoints* pt = a.pt;
+    const dim3 grid((unsigned)a.route->grid), block(LNR_DENSITY_BLOCK);
 #define LNR_BF3_BWD(HT)                                                                                                          \
     do {                                                                                                                         \
         int rc_ = f16_set_lds(mlp_backward_bf3_kernel<HT>, Bf3Lds<HT>::BYTES, "lnr_density_backward");                           \
         if (rc_) return rc_;                                                                                                     \
-        hipLaunchKernelGGL(mlp_backward_bf3_kernel<HT>, grid, block, Bf3Lds<HT>::BYTES, st, params, spec->n_mlp_params, feat, m_pad, \
-                           pt->n_points, pt->n_rays_dev, pt->n_rays, pt->n_samples, d_sigma, dfeat, slabs, want_dfeat);         \
+        hipLaunchKernelGGL(mlp_backward_bf3_kernel<HT>, grid, block, Bf3Lds<HT>::BYTES, a.st, a.params, a.spec->n_mlp_params, a.feat, a.m_pad, \
+                           pt->n_points, pt->n_rays_dev, pt->n_rays, pt->n_samples, a.d_sigma, a.dfeat, a.slabs, a.want_dfeat); \
     } while (0)
-    switch (spec->n_neurons / 16) {
+    switch (a.spec->n_neurons / 16) {
         case 1: LNR_BF3_BWD(1); break;
         case 2: LNR_BF3_BWD(2); break;
         default: LNR_BF3_BWD(4); break;

@@ -292,20 +292,21 @@ mlp_backward_f16_kernel(const float* __restrict__ params, int n_mlp, const uint3
 // class the north star names besides the default one: frequency encoding + <= 128-wide SIREN / ReLU MLP) runs the general kernels:
 // forward lnr_f16_fwd_kernel.h / lnr_density_f16_fwd.hip, backward lnr_f16_bwd_kernel.h / lnr_density_f16_bwd.hip.
 // ------------------------------------------------------------------------------------------------ host side
-static bool f16_fast_class(const LnrNetSpec* spec) {
+bool lnr_f16_fast_class(const LnrNetSpec* spec) {
     return spec->encoding == LNR_ENC_HASHGRID && spec->n_features == 2 && spec->enc_dim == 32 && spec->in_dim == 32 &&
            spec->n_hidden == 1 && spec->activation == LNR_ACT_RELU && spec->n_neurons <= 64;
 }
 
-// frequency encodings the fused kernels evaluate themselves (lnr_f16_freq.h: at most 12 (sin, cos) pairs per lane = three K blocks)
-static bool lnr_f16_fused_freq_shape(const LnrNetSpec* spec) {
+// frequency encodings the fused kernels evaluate themselves (lnr_f16_freq.h: at most 12 (sin, cos) pairs per lane = three K blocks);
+// for a network lnr_f16_supported covers outside the 256 x n class
+bool lnr_f16_fused_freq(const LnrNetSpec* spec) {
     return spec->encoding == LNR_ENC_FREQUENCY && spec->n_frequencies >= 1 && lnr_freq_kt(spec->n_frequencies) != 0;
 }
 
 // what LNR_PREC_F16 covers: half2 pair planes need an even number of features per level; the general kernels hold dW in registers
 // (<= 128 neurons, <= 3 hidden layers) and the weights plus the transposes of four waves in LDS
 bool lnr_f16_supported(const LnrNetSpec* spec) {
-    if (f16_fast_class(spec)) return true;
+    if (lnr_f16_fast_class(spec)) return true;
     if (spec->encoding == LNR_ENC_HASHGRID && (spec->n_features & 1)) return false;
     if (spec->enc_dim & 1) return false;
     const int H = spec->n_neurons;
@@ -313,12 +314,8 @@ bool lnr_f16_supported(const LnrNetSpec* spec) {
     // hidden matrix neither fits the LDS beside the exchange buffers nor the registers as a gradient
     if (!(H == 16 || H == 32 || H == 64 || H == 128 || (H == 256 && spec->n_hidden == 1))) return false;
     if (spec->n_hidden < 1 || spec->n_hidden > F16_NH_MAX || spec->in_dim > 32 * F16_KB_MAX) return false;
-    const size_t lds = lnr_f16_fused_freq_shape(spec) ? lnr_f16_freq_bwd_lds(spec) : lnr_f16_gen_bwd_lds(spec);
+    const size_t lds = lnr_f16_fused_freq(spec) ? lnr_f16_freq_bwd_lds(spec) : lnr_f16_gen_bwd_lds(spec);
     return lds > 0 && lds <= (size_t)LNR_LDS_LIMIT;
-}
-
-bool lnr_f16_fused_freq(const LnrNetSpec* spec) {
-    return spec->precision == LNR_PREC_F16 && lnr_f16_fused_freq_shape(spec) && !lnr_wide_class(spec) && lnr_f16_supported(spec);
 }
 
 static size_t f16_bwd_lds(const LnrNetSpec* spec) {
@@ -327,67 +324,47 @@ static size_t f16_bwd_lds(const LnrNetSpec* spec) {
            (size_t)2 * kb * 64 * 16;
 }
 
-int lnr_mlp_fwd_f16(const LnrNetSpec* spec, const float* params, const void* featp, int64_t m_pad, const MlpPoints* pt, float* sigma,
-                    const PointSrc* src, hipStream_t st) {
-    const int64_t tiles = (pt->n_points + 31) / 32;
-    int64_t blocks = (tiles + 3) / 4;
-    if (blocks > LNR_DENSITY_MAX_BLOCKS) blocks = LNR_DENSITY_MAX_BLOCKS;
-    if (blocks < 1) blocks = 1;
-    const dim3 grid((unsigned)blocks), block(LNR_DENSITY_BLOCK);
-    const uint32_t* fp = reinterpret_cast<const uint32_t*>(featp);
-    if (f16_fast_class(spec)) {
-        switch (spec->n_neurons / 16) {
-            case 1: hipLaunchKernelGGL(mlp_forward_f16_kernel<1>, grid, block, 0, st, params, fp, m_pad, pt->n_points, pt->n_rays_dev, pt->n_rays, pt->n_samples, sigma, pt->clip_flag); break;
-            case 2: hipLaunchKernelGGL(mlp_forward_f16_kernel<2>, grid, block, 0, st, params, fp, m_pad, pt->n_points, pt->n_rays_dev, pt->n_rays, pt->n_samples, sigma, pt->clip_flag); break;
-            default: hipLaunchKernelGGL(mlp_forward_f16_kernel<4>, grid, block, 0, st, params, fp, m_pad, pt->n_points, pt->n_rays_dev, pt->n_rays, pt->n_samples, sigma, pt->clip_flag); break;
-        }
-        return LNR_OK;
+int lnr_mlp_fwd_f16(const MlpArgs& a) {
+    const MlpPoints* pt = a.pt;
+    const dim3 grid((unsigned)a.route->grid), block(LNR_DENSITY_BLOCK);
+    const uint32_t* fp = reinterpret_cast<const uint32_t*>(a.feat);
+    switch (a.route->kind) {
+        case LNR_ROUTE_F16_FREQ: return lnr_mlp_fwd_f16_freq(a);
+        case LNR_ROUTE_F16_GEN: return lnr_mlp_fwd_f16_gen(a);
     }
-    if (lnr_f16_fused_freq(spec)) return lnr_mlp_fwd_f16_freq(spec, params, fp, m_pad, pt, sigma, blocks, src, st);
-    return lnr_mlp_fwd_f16_gen(spec, params, fp, m_pad, pt, sigma, blocks, src, st);
+#define LNR_F16_FWD(HT) hipLaunchKernelGGL(mlp_forward_f16_kernel<HT>, grid, block, 0, a.st, a.params, fp, a.m_pad, pt->n_points, pt->n_rays_dev, pt->n_rays, pt->n_samples, a.sigma, pt->clip_flag)
+    switch (a.spec->n_neurons / 16) {
+        case 1: LNR_F16_FWD(1); break;
+        case 2: LNR_F16_FWD(2); break;
+        default: LNR_F16_FWD(4); break;
+    }
+#undef LNR_F16_FWD
+    return LNR_OK;
 }
 
-// weight-gradient slabs lnr_mlp_bwd_f16 writes for up to n_points points (one per workgroup)
-int lnr_f16_bwd_slabs(const LnrNetSpec* spec, int64_t n_points) {
-    const int64_t tiles = (n_points + 31) / 32;
-    int64_t blocks = (tiles + 3) / 4;
-    if (blocks > LNR_BWD_MAX_BLOCKS) blocks = LNR_BWD_MAX_BLOCKS;
-    if (blocks < 1) blocks = 1;
-    if (!f16_fast_class(spec) && blocks > 256) blocks = 256;
-    return (int)blocks;
-}
-
-int lnr_mlp_bwd_f16(const LnrNetSpec* spec, const float* params, const void* featp, int64_t m_pad, const MlpPoints* pt, const float* d_sigma,
-                    float* dfeat, float* slabs, int want_dfeat, int* n_slabs, const PointSrc* src, float* d_pts, hipStream_t st) {
-    const int64_t tiles = (pt->n_points + 31) / 32;
-    int64_t blocks = (tiles + 3) / 4;
-    if (blocks > LNR_BWD_MAX_BLOCKS) blocks = LNR_BWD_MAX_BLOCKS;
-    if (blocks < 1) blocks = 1;
-    const dim3 block(LNR_DENSITY_BLOCK);
-    const uint32_t* fp = reinterpret_cast<const uint32_t*>(featp);
-    if (f16_fast_class(spec)) {
-        *n_slabs = (int)blocks;
-        const dim3 grid((unsigned)blocks);
-        const size_t lds = f16_bwd_lds(spec);
+int lnr_mlp_bwd_f16(const MlpArgs& a) {
+    const MlpPoints* pt = a.pt;
+    const dim3 grid((unsigned)a.route->grid), block(LNR_DENSITY_BLOCK);
+    const uint32_t* fp = reinterpret_cast<const uint32_t*>(a.feat);
+    switch (a.route->kind) {
+        case LNR_ROUTE_F16_FREQ: return lnr_mlp_bwd_f16_freq(a);
+        case LNR_ROUTE_F16_GEN: return lnr_mlp_bwd_f16_gen(a);
+    }
+    const size_t lds = f16_bwd_lds(a.spec);
 #define LNR_F16_BWD(HT)                                                                                                          \
     do {                                                                                                                         \
         int rc_ = f16_set_lds(mlp_backward_f16_kernel<HT>, lds, "lnr_density_backward");                                         \
         if (rc_) return rc_;                                                                                                     \
-        hipLaunchKernelGGL(mlp_backward_f16_kernel<HT>, grid, block, lds, st, params, spec->n_mlp_params, fp, m_pad, pt->n_points, \
-                           pt->n_rays_dev, pt->n_rays, pt->n_samples, d_sigma, dfeat, slabs, want_dfeat);                       \
+        hipLaunchKernelGGL(mlp_backward_f16_kernel<HT>, grid, block, lds, a.st, a.params, a.spec->n_mlp_params, fp, a.m_pad, pt->n_points, \
+                           pt->n_rays_dev, pt->n_rays, pt->n_samples, a.d_sigma, a.dfeat, a.slabs, a.want_dfeat);               \
     } while (0)
-        switch (spec->n_neurons / 16) {
-            case 1: LNR_F16_BWD(1); break;
-            case 2: LNR_F16_BWD(2); break;
-            default: LNR_F16_BWD(4); break;
-        }
-#undef LNR_F16_BWD
-        return LNR_OK;
+    switch (a.spec->n_neurons / 16) {
+        case 1: LNR_F16_BWD(1); break;
+        case 2: LNR_F16_BWD(2); break;
+        default: LNR_F16_BWD(4); break;
     }
-    if (blocks > 256) blocks = 256;                                    // general kernels: one workgroup per CU (LDS), persistent over the steps
-    *n_slabs = (int)blocks;
-    if (lnr_f16_fused_freq(spec)) return lnr_mlp_bwd_f16_freq(spec, params, fp, m_pad, pt, d_sigma, dfeat, slabs, want_dfeat, (int)blocks, src, d_pts, st);
-    return lnr_mlp_bwd_f16_gen(spec, params, fp, m_pad, pt, d_sigma, dfeat, slabs, want_dfeat, (int)blocks, src, d_pts, st);
+#undef LNR_F16_BWD
+    return LNR_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ layout self-test

@@ -26,18 +26,25 @@ static int f16_gen_kt(const LnrNetSpec* spec) { return lnr_freq_kt(spec->n_frequ
 static int f16_gen_kt(const LnrNetSpec* spec) { return (spec->in_dim + 31) / 32 <= 2 ? 2 : 4; }   // first-layer K blocks (as the forward)
 #endif
 
-int LNR_BWD_OTHER(const LnrNetSpec* spec, const float* params, const uint32_t* featp, int64_t m_pad, const MlpPoints* pt, const float* d_sigma,
-                  float* dfeat, float* slabs, int want_dfeat, int blocks, const PointSrc* src, float* d_pts, hipStream_t st);
-int LNR_BWD_OTHER_WIDE(const LnrNetSpec* spec, const float* params, const uint32_t* featp, int64_t m_pad, const MlpPoints* pt, const float* d_sigma,
-                       float* dfeat, float* slabs, int want_dfeat, int blocks, const PointSrc* src, float* d_pts, hipStream_t st);
+// (want_dfeat: the entry point's, which the fused form derives from d_pts)
+int LNR_BWD_OTHER(const MlpArgs& a, int want_dfeat);
+int LNR_BWD_OTHER_WIDE(const MlpArgs& a, int want_dfeat);
+
+// what the launch macros below name: the network, the points, the half2 view of the planes, kt and the launch shape
+#define LNR_F16_GEN_BWD_LOCALS                                                                                                   \
+    const LnrNetSpec* spec = a.spec;                                                                                             \
+    const MlpPoints* pt = a.pt;                                                                                                  \
+    const uint32_t* featp = reinterpret_cast<const uint32_t*>(a.feat);                                                           \
+    const int kt = f16_gen_kt(spec);                                                                                             \
+    const dim3 grid((unsigned)a.route->grid), block(LNR_DENSITY_BLOCK) /* one workgroup per CU (LDS), persistent over the steps */
 
 #define LNR_F16_GEN_BWD_K(HT, ACT, NH, KT)                                                                                        \
     do {                                                                                                                         \
         const size_t lds = BwdLds<HT, NH, KT>::BYTES;                                                                            \
         int rc_ = f16_set_lds(mlp_backward_f16_gen_kernel<HT, ACT, NH, KT, LNR_BWD_FQ != 0>, lds, "lnr_density_backward");       \
         if (rc_) return rc_;                                                                                                     \
-        hipLaunchKernelGGL((mlp_backward_f16_gen_kernel<HT, ACT, NH, KT, LNR_BWD_FQ != 0>), grid, block, lds, st, *spec, params, featp, m_pad, pt->n_points, \
-                           pt->n_rays_dev, pt->n_rays, pt->n_samples, d_sigma, dfeat, slabs, want_dfeat, *src, d_pts);           \
+        hipLaunchKernelGGL((mlp_backward_f16_gen_kernel<HT, ACT, NH, KT, LNR_BWD_FQ != 0>), grid, block, lds, a.st, *spec, a.params, featp, a.m_pad, pt->n_points, \
+                           pt->n_rays_dev, pt->n_rays, pt->n_samples, a.d_sigma, a.dfeat, a.slabs, want_dfeat, *a.src, a.d_pts); \
     } while (0)
 #define LNR_F16_GEN_BWD(HT, ACT, NH) do { if (kt == LNR_BWD_KT_LO) LNR_F16_GEN_BWD_K(HT, ACT, NH, LNR_BWD_KT_LO); else LNR_F16_GEN_BWD_K(HT, ACT, NH, LNR_BWD_KT_HI); } while (0)
 #define LNR_F16_GEN_BWD_N(HT, ACT) do { if (spec->n_hidden == 1) LNR_F16_GEN_BWD(HT, ACT, 1); else if (spec->n_hidden == 2) LNR_F16_GEN_BWD(HT, ACT, 2); else LNR_F16_GEN_BWD(HT, ACT, 3); } while (0)
@@ -62,22 +69,22 @@ size_t LNR_BWD_LDS(const LnrNetSpec* spec) {
 }
 
 // planes form: src / d_pts unused; fused form (LNR_BWD_FQ): featp / m_pad / dfeat unused, want_dfeat = (d_pts != nullptr)
-int LNR_BWD_ENTRY(const LnrNetSpec* spec, const float* params, const uint32_t* featp, int64_t m_pad, const MlpPoints* pt, const float* d_sigma,
-                  float* dfeat, float* slabs, int want_dfeat, int blocks, const PointSrc* src, float* d_pts, hipStream_t st) {
+int LNR_BWD_ENTRY(const MlpArgs& a) {
 #if LNR_BWD_FQ
-    want_dfeat = d_pts != nullptr ? 1 : 0;
+    const int want_dfeat = a.d_pts != nullptr ? 1 : 0;
 #else
+    const int want_dfeat = a.want_dfeat;
+    const int64_t m_pad = a.m_pad;
     // a K block's 16 feature planes are one buffer descriptor (32-bit record count, 32-bit lane offsets); the feature gradient is
     // stored with 32-bit byte offsets over all its planes
-    if (m_pad * 4 * 16 > (int64_t)0x7FFFFFFF || (want_dfeat && (int64_t)spec->enc_dim * m_pad * 4 > (int64_t)0xFFFFFFFFll)) {
+    if (m_pad * 4 * 16 > (int64_t)0x7FFFFFFF || (want_dfeat && (int64_t)a.spec->enc_dim * m_pad * 4 > (int64_t)0xFFFFFFFFll)) {
         lnr_set_error("lnr_density_backward: too many points per call for the general fp16 kernels (a plane of %lld samples: 64 x plane bytes and enc_dim x plane bytes must fit 32 bits)", (long long)m_pad);
         return LNR_ERR_UNSUPPORTED;
     }
 #endif
+    if (a.route->f16_part != 0) return LNR_BWD_OTHER(a, want_dfeat);
+    LNR_F16_GEN_BWD_LOCALS;
     const int akind = spec->activation;
-    if (akind != LNR_ACT_RELU && akind != LNR_ACT_SINE) return LNR_BWD_OTHER(spec, params, featp, m_pad, pt, d_sigma, dfeat, slabs, want_dfeat, blocks, src, d_pts, st);
-    const int kt = f16_gen_kt(spec);
-    const dim3 grid((unsigned)blocks), block(LNR_DENSITY_BLOCK);          // one workgroup per CU (LDS), persistent over the steps
 #define LNR_F16_GEN_BWD_A(HT) do { if (akind == LNR_ACT_RELU) LNR_F16_GEN_BWD_N(HT, LNR_ACT_RELU); else LNR_F16_GEN_BWD_N(HT, LNR_ACT_SINE); } while (0)
 #define LNR_F16_GEN_BWD_W(ACT) LNR_F16_GEN_BWD(16, ACT, 1)           /* 256 neurons: one hidden layer (lnr_f16_supported) */
     switch (spec->n_neurons / 16) {
@@ -95,29 +102,25 @@ int LNR_BWD_ENTRY(const LnrNetSpec* spec, const float* params, const uint32_t* f
                                                   "dA = W^T dZ (hidden)", "barrier a", "dW hidden", "barrier b", "next step's features + d_sigma",
                                                   "first layer dX + chain rule", "write x image", "barrier c", "dW first", "barrier d", "slab write"};
         unsigned long long h[LNR_N_PHASES];
-        if (lnr_phase_fetch(HIP_SYMBOL(lnr_f16_bwd_phase_cycles), h, LNR_N_PHASES, st)) lnr_phase_print(LNR_BWD_FQ ? "mlp_backward_f16 fused" : "mlp_backward_f16 planes", names, h);
+        if (lnr_phase_fetch(HIP_SYMBOL(lnr_f16_bwd_phase_cycles), h, LNR_N_PHASES, a.st)) lnr_phase_print(LNR_BWD_FQ ? "mlp_backward_f16 fused" : "mlp_backward_f16 planes", names, h);
     }
 #endif
     return LNR_OK;
 }
 #elif LNR_BWD_PART == 1
-int LNR_BWD_OTHER(const LnrNetSpec* spec, const float* params, const uint32_t* featp, int64_t m_pad, const MlpPoints* pt, const float* d_sigma,
-                  float* dfeat, float* slabs, int want_dfeat, int blocks, const PointSrc* src, float* d_pts, hipStream_t st) {
-    const int kt = f16_gen_kt(spec);
-    const dim3 grid((unsigned)blocks), block(LNR_DENSITY_BLOCK);          // one workgroup per CU (LDS), persistent over the steps
+int LNR_BWD_OTHER(const MlpArgs& a, int want_dfeat) {
+    if (a.route->f16_part == 2) return LNR_BWD_OTHER_WIDE(a, want_dfeat);
+    LNR_F16_GEN_BWD_LOCALS;
     switch (spec->n_neurons / 16) {
         case 1: LNR_F16_GEN_BWD_N(1, -1); break;
         case 2: LNR_F16_GEN_BWD_N(2, -1); break;
-        case 4: LNR_F16_GEN_BWD_N(4, -1); break;
-        default: return LNR_BWD_OTHER_WIDE(spec, params, featp, m_pad, pt, d_sigma, dfeat, slabs, want_dfeat, blocks, src, d_pts, st);
+        default: LNR_F16_GEN_BWD_N(4, -1); break;
     }
     return LNR_OK;
 }
 #else
-int LNR_BWD_OTHER_WIDE(const LnrNetSpec* spec, const float* params, const uint32_t* featp, int64_t m_pad, const MlpPoints* pt, const float* d_sigma,
-                       float* dfeat, float* slabs, int want_dfeat, int blocks, const PointSrc* src, float* d_pts, hipStream_t st) {
-    const int kt = f16_gen_kt(spec);
-    const dim3 grid((unsigned)blocks), block(LNR_DENSITY_BLOCK);          // one workgroup per CU (LDS), persistent over the steps
+int LNR_BWD_OTHER_WIDE(const MlpArgs& a, int want_dfeat) {
+    LNR_F16_GEN_BWD_LOCALS;
     switch (spec->n_neurons / 16) {
         case 8: LNR_F16_GEN_BWD_N(8, -1); break;
         default: LNR_F16_GEN_BWD(16, -1, 1); break;           /* 256 neurons: one hidden layer (lnr_f16_supported) */

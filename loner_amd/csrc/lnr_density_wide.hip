@@ -884,7 +884,8 @@ size_t lnr_wide_workspace(const LnrNetSpec* spec, int64_t n_points) {
     if (!lnr_wide_class(spec)) return 0;
     return (size_t)(spec->n_hidden + 2) * LNR_WIDE_H * (size_t)wide_chunk_stride(n_points) * sizeof(float);
 }
-int lnr_wide_slabs(void) { return 3 + LNR_WIDE_SPLITS; }      // slab 0, the partial slabs, the transposed hidden matrices
+// of the workspace's slab area the route occupies slab 0, the partial slabs and the transposed hidden matrices
+static_assert(3 + LNR_WIDE_SPLITS <= LNR_BWD_MAX_BLOCKS, "the 256 x n route's slabs must fit the slab area of the workspace (make_layout)");
 
 namespace {
 struct WideCtx {
@@ -982,21 +983,19 @@ static int wide_backward(const WideCtx& c, const float* d_sigma, float* dfeat, f
     return LNR_OK;
 }
 
-static WideCtx wide_ctx(const LnrNetSpec* spec, const float* params, const float* feat, int64_t m_pad, const MlpPoints* pt, void* planes, hipStream_t st) {
-    return WideCtx{spec, params, feat, m_pad, pt, (float*)planes, st, spec->precision == LNR_PREC_F16, spec->n_neurons, spec->n_hidden, spec->in_dim, spec->activation, wide_chunk_stride(pt->n_points)};
+static WideCtx wide_ctx(const MlpArgs& a) {
+    const LnrNetSpec* spec = a.spec;
+    return WideCtx{spec, a.params, a.feat, a.m_pad, a.pt, (float*)a.planes, a.st, spec->precision == LNR_PREC_F16, spec->n_neurons, spec->n_hidden, spec->in_dim, spec->activation, wide_chunk_stride(a.pt->n_points)};
 }
 }  // namespace
 
-int lnr_mlp_fwd_wide(const LnrNetSpec* spec, const float* params, const float* feat, int64_t m_pad, const MlpPoints* pt, float* sigma,
-                     void* planes, hipStream_t st) {
-    const WideCtx c = wide_ctx(spec, params, feat, m_pad, pt, planes, st);
-    return c.half ? wide_forward<true>(c, sigma) : wide_forward<false>(c, sigma);
+int lnr_mlp_fwd_wide(const MlpArgs& a) {
+    const WideCtx c = wide_ctx(a);
+    return c.half ? wide_forward<true>(c, a.sigma) : wide_forward<false>(c, a.sigma);
 }
 
-// the weight gradient lands in slab 0 (slabs 1 .. LNR_WIDE_SPLITS are the weight-gradient kernel's partial sums): *n_slabs = 1
-int lnr_mlp_bwd_wide(const LnrNetSpec* spec, const float* params, const float* feat, int64_t m_pad, const MlpPoints* pt, const float* d_sigma,
-                     float* dfeat, float* slabs, int want_dfeat, int want_dw, int* n_slabs, void* planes, hipStream_t st) {
-    const WideCtx c = wide_ctx(spec, params, feat, m_pad, pt, planes, st);
-    *n_slabs = 1;
-    return c.half ? wide_backward<true>(c, d_sigma, dfeat, slabs, want_dfeat, want_dw) : wide_backward<false>(c, d_sigma, dfeat, slabs, want_dfeat, want_dw);
+// the weight gradient lands in slab 0 (slabs 1 .. LNR_WIDE_SPLITS are the weight-gradient kernel's partial sums): the fold sums one slab
+int lnr_mlp_bwd_wide(const MlpArgs& a) {
+    const WideCtx c = wide_ctx(a);
+    return c.half ? wide_backward<true>(c, a.d_sigma, a.dfeat, a.slabs, a.want_dfeat, a.want_dw) : wide_backward<false>(c, a.d_sigma, a.dfeat, a.slabs, a.want_dfeat, a.want_dw);
 }

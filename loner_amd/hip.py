@@ -52,6 +52,13 @@ class NetSpec(C.Structure):
                 ("level_hashed", C.c_uint32 * MAX_LEVELS)]
 
 
+ROUTE_KINDS = ("unsupported", "wide", "f16_fast", "f16_freq", "f16_gen", "bf3", "fast32", "regs", "lds")     # LnrRouteKind
+
+
+class DensityRoute(C.Structure):        # LnrDensityRoute
+    _fields_ = [("kind", C.c_int32), ("w_lds", C.c_int32), ("waves", C.c_int32), ("dw64", C.c_int32), ("f16_part", C.c_int32)]
+
+
 class LossConfig(C.Structure):
     _fields_ = [("selection", C.c_int32), ("min_js", C.c_float), ("max_js", C.c_float), ("js_alpha", C.c_float),
                 ("los_lambda", C.c_float), ("depth_lambda", C.c_float), ("min_eps", C.c_float),
@@ -74,6 +81,7 @@ _SIGNATURES = {
     "lnr_net_spec_finalize": (C.c_int, [C.POINTER(NetSpec)]),
     "lnr_density_workspace": (C.c_size_t, [C.POINTER(NetSpec), C.c_int64]),
     "lnr_density_workspace_forward": (C.c_size_t, [C.POINTER(NetSpec), C.c_int64]),
+    "lnr_density_route": (C.c_int, [C.POINTER(NetSpec), C.c_int64, C.c_int32, C.POINTER(DensityRoute)]),
     "lnr_density_workspace_init": (C.c_int, [P, C.c_size_t, P]),
     "lnr_density_workspace_release": (C.c_int, [P]),
     "lnr_density_forward": (C.c_int, [C.POINTER(NetSpec), P, P, C.c_int64, P, P, C.c_int32, C.c_int32, P, P, P, C.c_size_t, P]),

@@ -79,6 +79,13 @@ def _workspace(spec, device, n_points, forward_only=False):
     return ent, need
 
 
+def density_route(spec, n_points, backward=True):
+    """-> hip.DensityRoute: the MLP kernels the library launches for `spec` at `n_points` points (`kind` indexes hip.ROUTE_KINDS).  No GPU."""
+    r = hip.DensityRoute()
+    check(load().lnr_density_route(C.byref(spec), int(n_points), 1 if backward else 0, C.byref(r)), "lnr_density_route")
+    return r
+
+
 def density_clipped_count(device) -> int:
     """Number of density outputs the forward kernels have clipped on `device` so far (non-finite values, and values beyond
     +-65504 in the fp16 mode: nerf_tcnn.py:70-78).  Reads a status word of the workspace: synchronises with the device."""

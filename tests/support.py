@@ -23,98 +23,27 @@ def small_settings(n_rays, n_samples, voxel=32, n_test=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# Which MLP kernels a density network runs on: the host-side dispatch of the C library restated in Python, so that a test can assert the
-# route its shape is meant to cover (a change to the dispatch then fails a test instead of silently moving coverage elsewhere).
-# Mirrors loner_amd/csrc: lnr_density.hip plan_launch (:571-631), bwd_lds (:561-565), lnr_density_api.h lnr_w_lds_floats (:136-138),
-# lnr_density_wide.hip lnr_wide_class (:862-869), lnr_density_f16.hip f16_fast_class / lnr_f16_fused_freq_shape / lnr_f16_supported /
-# lnr_f16_fused_freq (:295-322), lnr_density_bf3.hip lnr_bf3_class (:397-403), the backward LDS of the general fp16 kernels
-# (lnr_f16_bwd_kernel.h BwdLds :34-44 over lnr_f16_fwd_kernel.h FwdLds :31-38) and lnr_f16_freq.h lnr_freq_kt (:23-26).
+# Which MLP kernels a density network runs on, so that a test can assert the route its shape is meant to cover (a change to the dispatch
+# then fails a test instead of silently moving coverage elsewhere).  The decision lives in one place, lnr_route of
+# loner_amd/csrc/lnr_density.hip, which the launch path reads; this asks the library for it (lnr_density_route).  No GPU.
 # ---------------------------------------------------------------------------------------------------------------------------
-LDS_LIMIT = 160 * 1024
-_LDS_TIERS = [(1, 4, 1), (1, 2, 1), (1, 1, 1), (1, 4, 0), (1, 2, 0), (1, 1, 0),
-              (0, 4, 1), (0, 2, 1), (0, 1, 1), (0, 4, 0), (0, 2, 0), (0, 1, 0)]      # {weights in LDS, waves, 64-bit accumulators}
-
-
-def _w_lds_floats(H, in_dim, nh, with_first):
-    return (H * (in_dim + 4) if with_first else 0) + (nh - 1) * H * (H + 4) + 16 * H
-
-
-def _freq_kt(nf):
-    slots = 3 * ((nf + 3) // 4)
-    return 2 if slots <= 6 else (3 if slots <= 9 else 0)
-
-
-def _f16_gen_bwd_lds(H, nh, kt):
-    ht = H // 16
-    kbh = (ht + 1) // 2
-    k0, kh = 32 * kt, 32 * kbh
-    s0 = k0 if k0 % 128 == 0 else k0 + 8
-    sh = kh if kh % 128 == 0 else kh + 8
-    n_w = (H * s0 + (nh - 1) * H * sh + H + 7) & ~7
-    nt = ht if (nh > 1 and ht > 2 * kt) else 2 * kt
-    off_sc = n_w + 2 * H + 4 * (ht + nt) * 32 * 16
-    return off_sc * 2 + 8 * 4 + 4 * H * 4 + 4 * 3 * 4
-
-
 def density_route(enc, net, n_points, backward=True):
     """-> dict(route=..., ...) for the tinycudann-style configs `enc`, `net` at `n_points` samples.
     routes: "wide" (256 x 2..3 layer by layer, both precisions); fp32: "bf3" / "fast32" (the default shape class), "regs" (register-
     accumulating backward, `w_lds` 1 all weights / 2 hidden matrices / 0 none in LDS), "lds" (LDS-accumulating kernels, tier `w_lds`,
     `waves`, `dw64`); fp16: "f16_fast" (the default shape class), "f16_freq" (fused frequency kernels) and "f16_gen" (features from pair
-    planes), the last two with `obj` = the object the run-time-activation kernels live in (1: <= 64 neurons, 2: 128 and 256)."""
-    from oracle.network import NetworkSpec
-    s = NetworkSpec.from_config(enc, net)
-    prec = str(net.get("precision", "fp32"))
-    f16 = s.precision == "fp16"
-    H, nh, in_dim, enc_dim, n_mlp = s.n_neurons, s.n_hidden, s.in_dim, s.enc_dim, s.n_mlp_params
-    hashgrid, freq = s.enc_type == "HashGrid", s.enc_type == "Frequency"
-    relu = s.activation == "ReLU"
-    run_time_obj = None if s.activation in ("ReLU", "Sine") else (1 if H <= 64 else 2)
-
-    f16_fast = hashgrid and s.n_features == 2 and enc_dim == 32 and in_dim == 32 and nh == 1 and relu and H <= 64
-    freq_shape = freq and s.n_frequencies >= 1 and _freq_kt(s.n_frequencies) != 0
-
-    def f16_supported():
-        if f16_fast:
-            return True
-        if (hashgrid and s.n_features % 2) or enc_dim % 2:
-            return False
-        if not (H in (16, 32, 64, 128) or (H == 256 and nh == 1)):
-            return False
-        if nh < 1 or nh > 3 or in_dim > 128:
-            return False
-        kt = _freq_kt(s.n_frequencies) if freq_shape else (2 if (in_dim + 31) // 32 <= 2 else 4)
-        return kt != 0 and _f16_gen_bwd_lds(H, nh, kt) <= LDS_LIMIT
-
-    pair_planes_ok = not (f16 and (enc_dim % 2 or (hashgrid and s.n_features % 2)))
-    if H == 256 and 1 <= nh <= 3 and in_dim % 16 == 0 and pair_planes_ok and (nh >= 2 or (f16 and not f16_supported())):
-        return dict(route="wide")
-    if f16:
-        if not f16_supported():
-            return dict(route="unsupported")
-        if f16_fast:
-            return dict(route="f16_fast")
-        return dict(route="f16_freq" if freq_shape else "f16_gen", obj=run_time_obj)
-    if relu and nh == 1 and in_dim == 32 and enc_dim == 32 and H <= 64 and n_points <= (1 << 25) - 2048:
-        return dict(route="bf3" if prec in ("fp32", "float32") and hashgrid else "fast32")
-    if backward and H >= 64 and nh <= 3 and in_dim <= 128 and not (H == 256 and nh > 1):
-        scratch = 4 * (2 if nh > 1 else 1) * H * 20 * 4
-        weights = _w_lds_floats(H, in_dim, nh, True) * 4
-        hidden = _w_lds_floats(H, in_dim, nh, False) * 4
-        if scratch <= LDS_LIMIT:
-            home = 1 if scratch + weights <= LDS_LIMIT else (2 if nh > 1 and scratch + hidden <= LDS_LIMIT else 0)
-            return dict(route="regs", w_lds=home)
-    for w_lds, waves, dw64 in _LDS_TIERS:
-        if not backward and (waves != 4 or dw64):
-            continue
-        if backward:
-            scratch = H * 16 + ((nh + 1) * H * 16 if nh > 1 else 0)
-            lds = (w_lds * n_mlp + (2 if dw64 else 1) * n_mlp + waves * scratch) * 4
-        else:
-            lds = ((_w_lds_floats(H, in_dim, nh, True) if w_lds else 0) + 4) * 4
-        if lds <= LDS_LIMIT:
-            return dict(route="lds", w_lds=w_lds, waves=waves, dw64=dw64 if backward else 0)
-    return dict(route="unsupported")
+    planes), the last two with `obj` = the object the run-time-activation kernels live in (backward 1: <= 64 neurons, 2: 128 and 256;
+    forward 1; None: the compile-time ReLU / Sine kernels)."""
+    from loner_amd import hip, ops
+    r = ops.density_route(hip.make_net_spec(enc, net), n_points, backward)
+    route = hip.ROUTE_KINDS[r.kind]
+    if route in ("f16_freq", "f16_gen"):
+        return dict(route=route, obj=r.f16_part or None)
+    if route == "regs":
+        return dict(route=route, w_lds=r.w_lds)
+    if route == "lds":
+        return dict(route=route, w_lds=r.w_lds, waves=r.waves, dw64=r.dw64)
+    return dict(route=route)
 
 
 ACTIVATION_NAMES = ["None", "ReLU", "Sine", "LeakyReLU", "Exponential", "Sigmoid", "Squareplus", "Softplus", "Tanh"]   # loner_amd/hip.py

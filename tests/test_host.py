@@ -272,9 +272,10 @@ def test_squareplus_and_softplus_carry_tiny_cuda_nn_k_act():
     assert abs(float(NW._activate(torch.zeros(1), "Squareplus")) - 0.1) < 1e-7 and abs(float(NW._activate(torch.zeros(1), "Softplus")) - 0.0693147) < 1e-6
 
 
-def test_density_route_helper_restates_the_dispatch():
-    """tests/support.py density_route against launch plans worked out by hand from plan_launch / lnr_wide_class / lnr_f16_supported
-    (LDS bytes in the comments): if the dispatch changes, this and the route assertions of test_gpu_activations.py say so."""
+def test_library_reports_the_hand_worked_density_routes(lib_path):
+    """lnr_density_route (through tests/support.py density_route) against launch plans worked out by hand from the dispatch and the
+    per-family predicates (LDS bytes in the comments): if the dispatch changes, this and the route assertions of
+    test_gpu_activations.py say so."""
     from tests.support import ACTIVATION_NAMES, ACTIVATION_ROUTES, density_route, route_of
     F = lambda nf: dict(otype="Frequency", n_frequencies=nf)
     Hg = lambda levels, f=2: dict(otype="HashGrid", n_levels=levels, n_features_per_level=f, log2_hashmap_size=12, base_resolution=8)

@@ -21,7 +21,10 @@ ALIAS = {"encode_backward_kernel": "encode_backward", "encode_forward_kernel<2, 
          "mlp_backward_bf3_kernel": "mlp_backward", "mlp_forward_bf3_kernel": "mlp_forward",
          "sum_dx_planes_kernel": "sum_dx_planes", "adam_kernel": "adam", "los_loss_fused_kernel": "los_loss_fused"}
 fetch, write = per_kernel("FETCH_SIZE"), per_kernel("WRITE_SIZE")
-out = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace), bench.py --quick --steps 8 --warmup 4 (tools/gpu_run.sh pmc:FETCH_SIZE pmc:WRITE_SIZE), 1x MI355X",
+# (the per-kernel means depend on the launches averaged: name the command that made them)
+command = "bench.py --steps 6 --warmup 2 --no-cpu-baseline (tools/pmc.sh)" if len(sys.argv) > 2 and sys.argv[2] == "" else \
+          "bench.py --quick --steps 8 --warmup 4 (tools/gpu_run.sh pmc:FETCH_SIZE pmc:WRITE_SIZE)"
+out = {"source": f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace), {command}, 1x MI355X",
        "units": "counter values are KiB; bytes = value*1024.  bytes_corrected doubles FETCH_SIZE as MI355X_MICROARCH.md prescribes for gfx950 "
                 "(64 B tallied per 128-B request on wide streaming reads; for 8-byte gathers the factor is uncalibrated, so it is an upper bound); "
                 "Infinity-Cache hits are counted, not excluded",
