@@ -914,13 +914,10 @@ extern "C" int lnr_density_backward(const LnrNetSpec* spec, const float* params,
     ReduceCtx rctx{spec, regions, counts, ovf, ovf_flag, epoch, grad_table, rplan, L.bpg, L.maxo, L.shift, spec->n_params - spec->n_mlp_params,
                    (flags & LNR_BWD_TABLE_ATOMICS) ? 0 : L.n_split, (flags & LNR_BWD_OVERWRITE_GRAD) ? 1 : 0,
                    fold_in_reduce ? slabs : nullptr, route.n_slabs, spec->n_mlp_params, grad_params};
-    // hash grids (LNR_SPLIT_DX): the input gradient first, as launches of its own; the table-gradient partition follows behind the event
-    const bool split = LNR_SPLIT_DX && hash;
     if (want_dfeat && !fused_freq) {
         rc = lnr_encode_backward(spec, params, &src, cap, dfeat, dxl, L.m_pad, grad_table, want_grad ? regions : nullptr, &rplan, counts,
                                  L.bpg, L.maxo, L.shift,
-                                 ovf, ovf_flag, epoch, d_pts_eff, ray_accum ? d_rays : nullptr, (long long*)(ws + L.off_rayacc), (flags & LNR_BWD_BINS_W8) != 0,
-                                 split ? LNR_ENC_PART_DX : (LNR_ENC_PART_DX | LNR_ENC_PART_RECORDS), st);
+                                 ovf, ovf_flag, epoch, d_pts_eff, ray_accum ? d_rays : nullptr, (long long*)(ws + L.off_rayacc), (flags & LNR_BWD_BINS_W8) != 0, st);
         if (rc) return rc;
         LNR_CHECK_LAUNCH("lnr_density_backward(encode backward)");
     }
@@ -937,12 +934,6 @@ extern "C" int lnr_density_backward(const LnrNetSpec* spec, const float* params,
     }
     if (!want_grad) return LNR_OK;       // frozen parameters: no table reduce, no weight-gradient fold
     if (want_dfeat) {
-        if (split) {
-            rc = lnr_encode_backward(spec, params, &src, cap, dfeat, dxl, L.m_pad, grad_table, regions, &rplan, counts, L.bpg, L.maxo, L.shift,
-                                     ovf, ovf_flag, epoch, nullptr, nullptr, nullptr, (flags & LNR_BWD_BINS_W8) != 0, LNR_ENC_PART_RECORDS, st);
-            if (rc) return rc;
-            LNR_CHECK_LAUNCH("lnr_density_backward(table-gradient partition)");
-        }
         if (hash && (flags & LNR_BWD_REPORT_REGIONS)) {           // diagnostic, call-time flag: synchronises the stream
             int64_t live = cap;
             int32_t nr = 0;

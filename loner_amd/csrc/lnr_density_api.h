@@ -45,12 +45,6 @@ struct PointSrc {
 #define LNR_XPAIR_SCALE_MIN 3000.0f   /* hashed power-of-two levels at least this fine take x-pair records (below: run-length combined 8-byte records) */
 #endif
 
-#ifndef LNR_SPLIT_DX
-#define LNR_SPLIT_DX 0      /* 1: hash grids take the input gradient as a kernel of its own (encode_dx_pair_kernel); measured SLOWER */
-#endif
-#define LNR_ENC_PART_DX 1        /* lnr_encode_backward: the input gradient (d_pts / d_rays) */
-#define LNR_ENC_PART_RECORDS 2   /* lnr_encode_backward: the table-gradient records */
-
 // rn(v * 2^42) as a 64-bit integer.  There is no f32 -> i64 convert instruction (the compiler's expansion is ~20 VALU
 // instructions, and these kernels are VALU-issue bound): for |v| < 2^8 the sum (double)v * 2^42 + 1.5 * 2^52 is exact up to
 // its one rounding to an integer (nearest even, like __float2ll_rn) and leaves that integer in the mantissa - a convert, an
@@ -243,5 +237,5 @@ int lnr_mlp_fwd_wide(const MlpArgs& a);
 int lnr_mlp_bwd_wide(const MlpArgs& a);
 int lnr_encode_backward(const LnrNetSpec* spec, const float* params, const PointSrc* src, int64_t cap_points, const float* dfeat,
                         float* dxl, int64_t m_pad, float* grad_table, void* regions, const RegionPlan* plan, int* counts, int bpg,
-                        int maxo, int shift, long long* ovf, int* ovf_flag, int epoch, float* d_pts, float* d_rays_acc, long long* ray_acc, bool bins_w8, int parts,
+                        int maxo, int shift, long long* ovf, int* ovf_flag, int epoch, float* d_pts, float* d_rays_acc, long long* ray_acc, bool bins_w8,
                         hipStream_t st);

@@ -28,15 +28,9 @@
 // load per operand, 16 MFMAs, repeat: latency-bound - so the parallelism has to come from the number of ranges: with 32 of them (512
 // workgroups for a 256 x 256 matrix, 2 waves per SIMD) the kernel took 0.84 ms per chunk, 7 TFLOP/s (profiles/r05_wide_networks.txt)
 #define LNR_WIDE_SPLITS 128
-#ifndef LNR_WIDE_F16_BWD
-#define LNR_WIDE_F16_BWD 1             /* fp16 mode: weight gradient and first-layer back-propagation on the f16 matrix pipe (0: round 5's fp32-MFMA kernels, A/B) */
-#endif
-// Back-propagation through a HIDDEN matrix on the f16 pipe: measured 292 us per chunk against 246 us for the fp32-MFMA kernel
-// (profiles/r06_wide_networks.txt) - with the matrix time gone the kernel is its plane traffic (dZ and Z_prev in, dZ_prev out as 4-byte
-// accesses of 64-byte row segments), and the fp32 kernel's epilogue carries less of it per MFMA.  Off; the kernel stays for the A/B.
-#ifndef LNR_WIDE_F16_DX_HIDDEN
-#define LNR_WIDE_F16_DX_HIDDEN 0
-#endif
+// fp16 mode: the weight gradient and the first-layer back-propagation run on the f16 matrix pipe; back-propagation through a HIDDEN
+// matrix stays on the fp32 MFMA (f16 pipe: 292 us per chunk against 246 us, profiles/r06_wide_networks.txt - with the matrix time gone
+// the kernel is its plane traffic, and the fp32 kernel's epilogue carries less of it per MFMA).
 #define LNR_WIDE_H 256
 #define WIDE_LDS_ROW 20                // floats per staged weight row of the forward: 16 + 4 padding (the 16 lanes of a 16-byte LDS read hit 16 distinct bank quads)
 #define WIDE_LDS_TROW 260              // floats per staged row of a transposed matrix (back-propagation): 256 + 4 padding, same reason
@@ -401,7 +395,7 @@ wide_dwo_kernel(int act, const float* __restrict__ z, int64_t chp, WideSamples s
 // (workgroup i runs on XCD i mod 8), i.e. one L2 - with the plain (rb, cb, split) order a split's workgroups sat on all eight and
 // every plane crossed the fabric 2 - 4 times.  (0.84 ms per chunk for a hidden matrix with 32 ranges, 0.46 with 128, 0.37 with the XCD
 // order and per-wave operand prefetch.)
-template <bool HALF, int IN>
+template <int IN>                      // fp32 modes only: WIDE_IN_FEAT or WIDE_IN_Z (the fp16 mode: wide_dw_h_kernel)
 __global__ void __launch_bounds__(256)
 wide_dw_kernel(const float* __restrict__ dz, int64_t chp, const float* __restrict__ in, int64_t in_stride, int enc_dim, int K, int act,
                WideSamples smp, float* __restrict__ partial, int64_t n_mlp, int64_t layer_off) {
@@ -420,21 +414,12 @@ wide_dw_kernel(const float* __restrict__ dz, int64_t chp, const float* __restric
     const int sc = threadIdx.x >> 2, sq = threadIdx.x & 3;
     const int sk = 64 * cb + sc;
     const bool s_load = sk < K && (IN == WIDE_IN_Z || sk < enc_dim);          // (else: a constant-one padding input, or beyond a ragged last block)
-    const float* s_src = in + (size_t)(IN == WIDE_IN_PAIR ? (sk >> 1) : sk) * in_stride + (IN == WIDE_IN_Z ? 0 : smp.lo) + 4 * sq;
+    const float* s_src = in + (size_t)sk * in_stride + (IN == WIDE_IN_Z ? 0 : smp.lo) + 4 * sq;
     float* s_dst0 = &b_s[0][sc * WIDE_LDS_ROW + 4 * sq];
     // (the planes hold whole 16-sample tiles - zero-filled features, finite Z columns - and dZ of a padding sample is 0: nothing is clamped)
     auto finish1 = [&](float v) -> float {
-        if (IN == WIDE_IN_FEAT) {
-            if (!s_load) v = 1.0f;
-            return HALF ? round_f16(v) : v;
-        } else if (IN == WIDE_IN_PAIR) {
-            typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-            const uint32_t w = __builtin_bit_cast(uint32_t, v);
-            const h2 p = __builtin_bit_cast(h2, w);
-            return s_load ? (float)((sk & 1) ? p.y : p.x) : 1.0f;
-        }
-        v = act_fwd(v, act);
-        return HALF ? round_f16(v) : v;
+        if (IN == WIDE_IN_FEAT) return s_load ? v : 1.0f;
+        return act_fwd(v, act);
     };
     auto finish = [&](float4 raw) -> float4 { return float4{finish1(raw.x), finish1(raw.y), finish1(raw.z), finish1(raw.w)}; };
     // the loop over the split's tiles, for a workgroup with NCT 16-column tiles (a compile-time count - and a loop body without
@@ -617,10 +602,9 @@ __device__ __forceinline__ float wide_wave_scale_of(float v, float* inv) {
     return __uint_as_float((254u - be) << 23);                               // 2^-e
 }
 
-// dZ_prev = act'(Z_prev) . (W^T dZ) for a hidden matrix (TO_FEAT: the d_feature planes of the first layer) on v_mfma_f32_16x16x32_f16:
-// wide_layer_fwd_h_kernel's loop with the TRANSPOSED weights WT [n_rows][256] (fp16-rounded where staged) as the matrix and the scaled
-// dZ columns of the wave's 32 samples as the B operands.  n_rt = output row tiles (16 for a hidden matrix, in_dim / 16 for the first).
-template <bool TO_FEAT>
+// The d_feature planes W_1^T dZ of the first layer on v_mfma_f32_16x16x32_f16: wide_layer_fwd_h_kernel's loop with the TRANSPOSED
+// weights WT [n_rows][256] (fp16-rounded where staged) as the matrix and the scaled dZ columns of the wave's 32 samples as the B
+// operands.  n_rt = output row tiles (in_dim / 16); act and z_prev are unused (the parameter list of wide_dx_kernel).
 __global__ void __launch_bounds__(256)
 wide_dx_h_kernel(const float* __restrict__ WT, int n_rt, const float* __restrict__ dz, int64_t chp, int act, WideSamples smp,
                  const float* __restrict__ z_prev, float* __restrict__ out, int64_t out_stride, int enc_dim) {
@@ -698,27 +682,12 @@ wide_dx_h_kernel(const float* __restrict__ WT, int n_rt, const float* __restrict
             const bool more = kb + 1 < n_kb;
             if (more) { WIDE_DXH_STAGE_LOAD(kb + 1); x_load(kb + 1); }
             const f16* wb = &w_h[kb & 1][c * WIDE_LDS_HROW + 8 * g];
-            if constexpr (!TO_FEAT) {
-                // a hidden matrix: all 16 row tiles, the loop of wide_layer_fwd_h_kernel - fragment jt + 1 requested in front of the MFMAs
-                // of fragment jt (with a branch per row tile and every read directly in front of its MFMAs the first version of this
-                // kernel took 317 us per chunk against the forward layer's 139)
-                f16x8 wa = *reinterpret_cast<const f16x8*>(wb);
 #pragma unroll
-                for (int jt = 0; jt < 16; ++jt) {
-                    const f16x8 wn = *reinterpret_cast<const f16x8*>(wb + 16 * (jt < 15 ? jt + 1 : 15) * WIDE_LDS_HROW);
+            for (int jt = 0; jt < 16; ++jt) {
+                if (jt < n_rt) {                              // (workgroup-uniform: the first layer has in_dim / 16 row tiles)
+                    const f16x8 wa = *reinterpret_cast<const f16x8*>(wb + 16 * jt * WIDE_LDS_HROW);
                     Z[0][jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wa, xb[0], Z[0][jt], 0, 0, 0);
                     Z[1][jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wa, xb[1], Z[1][jt], 0, 0, 0);
-                    wa = wn;
-                }
-                WIDE_PIPELINE_LDS_MFMA_H();
-            } else {
-#pragma unroll
-                for (int jt = 0; jt < 16; ++jt) {
-                    if (jt < n_rt) {                              // (workgroup-uniform: the first layer has in_dim / 16 row tiles)
-                        const f16x8 wa = *reinterpret_cast<const f16x8*>(wb + 16 * jt * WIDE_LDS_HROW);
-                        Z[0][jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wa, xb[0], Z[0][jt], 0, 0, 0);
-                        Z[1][jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wa, xb[1], Z[1][jt], 0, 0, 0);
-                    }
                 }
             }
             if (more) { WIDE_DXH_STAGE_STORE((kb + 1) & 1); x_finish(); }
@@ -732,30 +701,13 @@ wide_dx_h_kernel(const float* __restrict__ WT, int n_rt, const float* __restrict
             if (2 * pair + t >= n_tiles) continue;
             const int64_t col = (2 * pair + t) * 16 + c;
             const bool live = col < M;
-            if constexpr (!TO_FEAT) {
-                // Z_prev of four row tiles (16 loads) in flight at a time, in front of the 16 products and stores that use them
 #pragma unroll
-                for (int j0 = 0; j0 < 16; j0 += 4) {
-                    float zp[4][4];
+            for (int jt = 0; jt < 16; ++jt) {
+                if (jt < n_rt) {                              // (no break: the loop must unroll for the accumulators to stay registers)
 #pragma unroll
-                    for (int jj = 0; jj < 4; ++jj)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) zp[jj][r] = z_prev[(size_t)(16 * (j0 + jj) + 4 * g + r) * chp + col];
-#pragma unroll
-                    for (int jj = 0; jj < 4; ++jj)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r)
-                            out[(size_t)(16 * (j0 + jj) + 4 * g + r) * chp + col] = live ? Z[t][j0 + jj][r] * inv_sc * act_bwd(zp[jj][r], act) : 0.0f;
-                }
-            } else {
-#pragma unroll
-                for (int jt = 0; jt < 16; ++jt) {
-                    if (jt < n_rt) {                              // (no break: the loop must unroll for the accumulators to stay registers)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const int k = 16 * jt + 4 * g + r;
-                            if (k < enc_dim && live) out[(size_t)k * out_stride + smp.lo + col] = Z[t][jt][r] * inv_sc;
-                        }
+                    for (int r = 0; r < 4; ++r) {
+                        const int k = 16 * jt + 4 * g + r;
+                        if (k < enc_dim && live) out[(size_t)k * out_stride + smp.lo + col] = Z[t][jt][r] * inv_sc;
                     }
                 }
             }
@@ -954,28 +906,27 @@ static int wide_backward(const WideCtx& c, const float* d_sigma, float* dfeat, f
             const int K = l == 0 ? c.K1 : c.H;
             const int64_t layer_off = l == 0 ? 0 : (int64_t)c.H * c.K1 + (int64_t)(l - 1) * c.H * c.H;
             const dim3 grid_w((unsigned)(4 * ((K + 63) / 64) * LNR_WIDE_SPLITS));
-            if (!want_dw) {}                                       // frozen parameters (tracking phase): the input gradient only
-            else if (HALF && LNR_WIDE_F16_BWD && l > 0) hipLaunchKernelGGL((wide_dw_h_kernel<WIDE_IN_Z>), grid_w, block, 0, c.st, dz, c.chp, c.z(l - 1), c.chp, c.H, K, c.act, s, slabs, n_mlp, layer_off);
-            else if (HALF && LNR_WIDE_F16_BWD) hipLaunchKernelGGL((wide_dw_h_kernel<WIDE_IN_PAIR>), grid_w, block, 0, c.st, dz, c.chp, c.feat, c.m_pad, c.spec->enc_dim, K, c.act, s, slabs, n_mlp, layer_off);
-            else if (l > 0) hipLaunchKernelGGL((wide_dw_kernel<HALF, WIDE_IN_Z>), grid_w, block, 0, c.st, dz, c.chp, c.z(l - 1), c.chp, c.H, K, c.act, s, slabs, n_mlp, layer_off);
-            else if (HALF) hipLaunchKernelGGL((wide_dw_kernel<HALF, WIDE_IN_PAIR>), grid_w, block, 0, c.st, dz, c.chp, c.feat, c.m_pad, c.spec->enc_dim, K, c.act, s, slabs, n_mlp, layer_off);
-            else hipLaunchKernelGGL((wide_dw_kernel<HALF, WIDE_IN_FEAT>), grid_w, block, 0, c.st, dz, c.chp, c.feat, c.m_pad, c.spec->enc_dim, K, c.act, s, slabs, n_mlp, layer_off);
+            if (want_dw) {                                         // (else: frozen parameters, tracking phase - the input gradient only)
+                if constexpr (HALF) {
+                    if (l > 0) hipLaunchKernelGGL((wide_dw_h_kernel<WIDE_IN_Z>), grid_w, block, 0, c.st, dz, c.chp, c.z(l - 1), c.chp, c.H, K, c.act, s, slabs, n_mlp, layer_off);
+                    else hipLaunchKernelGGL((wide_dw_h_kernel<WIDE_IN_PAIR>), grid_w, block, 0, c.st, dz, c.chp, c.feat, c.m_pad, c.spec->enc_dim, K, c.act, s, slabs, n_mlp, layer_off);
+                } else {
+                    if (l > 0) hipLaunchKernelGGL((wide_dw_kernel<WIDE_IN_Z>), grid_w, block, 0, c.st, dz, c.chp, c.z(l - 1), c.chp, c.H, K, c.act, s, slabs, n_mlp, layer_off);
+                    else hipLaunchKernelGGL((wide_dw_kernel<WIDE_IN_FEAT>), grid_w, block, 0, c.st, dz, c.chp, c.feat, c.m_pad, c.spec->enc_dim, K, c.act, s, slabs, n_mlp, layer_off);
+                }
+            }
             const int64_t count = (int64_t)c.H * K;
             if (want_dw) hipLaunchKernelGGL(wide_fold_kernel, dim3((unsigned)((count + 255) / 256)), block, 0, c.st, slabs, n_mlp, layer_off, count);
             if (l > 0) {
-                if (HALF && LNR_WIDE_F16_BWD && LNR_WIDE_F16_DX_HIDDEN)
-                    hipLaunchKernelGGL((wide_dx_h_kernel<false>), grid_p, block, 0, c.st, wt + (size_t)(l - 1) * c.H * c.H, c.H / 16, dz, c.chp, c.act, s,
-                                       c.z(l - 1), dz_other, c.chp, 0);
-                else
-                    hipLaunchKernelGGL((wide_dx_kernel<HALF, false>), grid_p, block, 0, c.st, wt + (size_t)(l - 1) * c.H * c.H, c.H / 16, dz, c.chp, c.act, s,
-                                       c.z(l - 1), dz_other, c.chp, 0);
+                hipLaunchKernelGGL((wide_dx_kernel<HALF, false>), grid_p, block, 0, c.st, wt + (size_t)(l - 1) * c.H * c.H, c.H / 16, dz, c.chp, c.act, s,
+                                   c.z(l - 1), dz_other, c.chp, 0);
                 float* t = dz; dz = dz_other; dz_other = t;
             } else if (want_dfeat) {
-                if (HALF && LNR_WIDE_F16_BWD)
-                    hipLaunchKernelGGL((wide_dx_h_kernel<true>), grid_p, block, 0, c.st, wt_first, K / 16, dz, c.chp, c.act, s, (const float*)nullptr, dfeat,
+                if constexpr (HALF)
+                    hipLaunchKernelGGL(wide_dx_h_kernel, grid_p, block, 0, c.st, wt_first, K / 16, dz, c.chp, c.act, s, (const float*)nullptr, dfeat,
                                        c.m_pad, c.spec->enc_dim);
                 else
-                    hipLaunchKernelGGL((wide_dx_kernel<HALF, true>), grid_p, block, 0, c.st, wt_first, K / 16, dz, c.chp, c.act, s, (const float*)nullptr, dfeat,
+                    hipLaunchKernelGGL((wide_dx_kernel<false, true>), grid_p, block, 0, c.st, wt_first, K / 16, dz, c.chp, c.act, s, (const float*)nullptr, dfeat,
                                        c.m_pad, c.spec->enc_dim);
             }
         }

@@ -45,15 +45,11 @@ __device__ __forceinline__ bool level_slot(int bpg, int n_slots, bool xcd_affine
 #define LNR_XCD_AFFINE_MAX_POINTS (1 << 19)
 #endif
 static inline bool lnr_xcd_affine(int n_slots, int64_t n_points, bool forward) {
-    bool on = forward && n_points <= LNR_XCD_AFFINE_MAX_POINTS;
-#ifdef LNR_ABLATE
-    static const char* env = getenv("LNR_X_XCD");                 // development builds: 0 / 1 force it off / on for every encode kernel
-    if (env) on = atoi(env) != 0;
-#endif
+    const bool on = forward && n_points <= LNR_XCD_AFFINE_MAX_POINTS;
     return on && n_slots > 0 && n_slots % 8 == 0;
 }
 
-// the n-th (0-based) set bit of mask: the level a workgroup group works on (level_mask = all levels outside ablation builds)
+// the n-th (0-based) set bit of mask: the level a workgroup group works on (level_mask = all levels)
 __device__ __forceinline__ int nth_level(uint32_t mask, int n) {
     for (int i = 0; i < n; ++i) mask &= mask - 1u;
     return __builtin_ctz(mask);
@@ -73,59 +69,6 @@ __device__ __forceinline__ void gather_entries(const float* __restrict__ table, 
             for (int q = 0; q < F / 4; ++q) {
                 const float4 t4 = ld32<float4>(table, off + 16u * q);
                 tv[k][4 * q] = t4.x; tv[k][4 * q + 1] = t4.y; tv[k][4 * q + 2] = t4.z; tv[k][4 * q + 3] = t4.w;
-            }
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ paired lanes
-// (helpers of encode_dx_pair_kernel, the -DLNR_SPLIT_DX=1 experiment; the forward ran in this form for part of round 4 - see
-// forward_level_loop for what replaced it)
-// Two lanes per sample: lane 2i takes the four corners of the cell with x = b0, lane 2i+1 those with x = b0 + 1.
-// Why: a random table gather costs one L2 LINE per distinct line an instruction touches (tools/gather_bench.hip: 0.5 lines/clk/CU
-// whatever the access width), and the two x-neighbours of a corner pair sit in the same 64-byte line most of the time - dense levels:
-// e1 = e0 + 1; hashed levels: e1 = e0 ^ (2^(t+1) - 1), t = trailing one bits of x, i.e. inside one aligned group of 8 entries for
-// 7 of 8 cells.  With one lane per sample the two neighbours are fetched by DIFFERENT instructions (corner k and k + 1) and the line
-// is paid twice; with the pair in adjacent lanes of ONE instruction it is paid once: ~1.1 instead of 2 lines per corner pair on the
-// fine levels, where no two samples share a cell.  The price is the cell arithmetic done twice - VALU these kernels have to spare
-// (the gathers of 64 samples occupy a CU's L1 path for ~1000 clocks, their arithmetic the four SIMDs for ~40).
-__device__ __forceinline__ float pair_partner_f(float v) {       // the other lane of the pair (quad_perm [1,0,3,2]); all lanes active
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));
-}
-
-// entries of the 4 (y, z) rows of a cell at x = b0 + hx: row r = (y bit) + 2 (z bit) is corner k = hx + 2 r of cell_entries
-__device__ __forceinline__ void cell_entries_x(const LevelInfo& L, const Cell& c, uint32_t hx, uint32_t e[4]) {
-    if (L.hashed) {
-        const uint32_t x = c.b[0] + hx;
-        const uint32_t hy0 = c.b[1] * PRIME_Y, hy1 = hy0 + PRIME_Y;
-        const uint32_t hz0 = c.b[2] * PRIME_Z, hz1 = hz0 + PRIME_Z;
-        e[0] = x ^ (hy0 ^ hz0); e[1] = x ^ (hy1 ^ hz0); e[2] = x ^ (hy0 ^ hz1); e[3] = x ^ (hy1 ^ hz1);
-    } else {
-        const uint32_t sy = L.res, sz = L.res * L.res;
-        const uint32_t i0 = c.b[0] + hx + c.b[1] * sy + c.b[2] * sz;
-        e[0] = i0; e[1] = i0 + sy; e[2] = i0 + sz; e[3] = i0 + sy + sz;
-    }
-    if (L.pow2) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) e[r] = (e[r] & (L.size - 1u)) + L.offset;
-    } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) e[r] = e[r] % L.size + L.offset;
-    }
-}
-
-template <int F>
-__device__ __forceinline__ void gather_entries4(const float* __restrict__ table, const uint32_t e[4], float tv[4][F]) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const uint32_t off = e[r] * (uint32_t)(F * 4);
-        if constexpr (F == 1) tv[r][0] = ld32<float>(table, off);
-        else if constexpr (F == 2) { const float2 t2 = ld32<float2>(table, off); tv[r][0] = t2.x; tv[r][1] = t2.y; }
-        else {
-#pragma unroll
-            for (int q = 0; q < F / 4; ++q) {
-                const float4 t4 = ld32<float4>(table, off + 16u * q);
-                tv[r][4 * q] = t4.x; tv[r][4 * q + 1] = t4.y; tv[r][4 * q + 2] = t4.z; tv[r][4 * q + 3] = t4.w;
             }
         }
     }
@@ -406,9 +349,6 @@ struct EncSink {
     int xcd_affine;         // level_slot(): the launch's levels one per XCD (list.n a multiple of 8)
     int* ovf_flag;          // [level] workspace status words: a kernel that adds to a level's overflow accumulators stores `epoch` there, and
     int epoch;              // only then does the reduce read (and zero) them - the accumulators are all-zero between calls (lnr_density.hip)
-#ifdef LNR_ABLATE
-    int dbg;                // ablation bits (LNR_X_DBG), development builds only
-#endif
     float combine_scale_max;
 };
 
@@ -537,95 +477,7 @@ ray_grad_apply_kernel(const long long* __restrict__ ray_acc, int n_rays, const i
     if (__builtin_expect(ray_acc[(size_t)n_rays * 6 + i / 6] != 0ll, 0)) d_rays[(size_t)(i / 6) * LNR_RAY_STRIDE + (i % 6)] = __builtin_nanf("");
     else if (q != 0ll) d_rays[(size_t)(i / 6) * LNR_RAY_STRIDE + (i % 6)] += (float)((double)q * (1.0 / (double)LNR_FIX_SCALE));
 }
-
-// The input gradient d(level features . g)/dx as a kernel of its own, two lanes per sample (see encode_forward_pair_kernel): level-major
-// like the forward, no LDS, no barriers, 8 waves per SIMD.  Inside the partition kernel the term's gathers (the 8 corner entries of
-// every live sample, one line each on the fine levels) sat in a wave's dependent chain between three workgroup barriers at 4 waves per
-// SIMD, and the parts of that kernel ADDED (profiles/r03_ablate_binned_partition.txt); here they are all a wave does.
-//   lane hx holds the dots d_r = g . entry(x = b0 + hx, row r) of the cell's four (y, z) rows;
-//   d/dx from the differences to the partner lane's dots (even lanes only), d/dy and d/dz from differences of the lane's own dots,
-//   weighted with the lane's x weight: per-lane PARTIAL sums that the per-ray reduction (or the pair add of the planes form) completes.
-template <int F, int DXM>
-__global__ void __launch_bounds__(ENC_BLOCK)
-encode_dx_pair_kernel(const LnrNetSpec spec, const float* __restrict__ table, const PointSrc src, const float* __restrict__ dfeat,
-                      float* __restrict__ dxl, int64_t m_pad, int bpg, uint32_t level_mask, int xcd_affine) {
-    static_assert(DXM != ENC_DX_NONE, "nothing to compute");
-    int slot, chunk;
-    if (!level_slot(bpg, __builtin_popcount(level_mask), xcd_affine != 0, slot, chunk)) return;
-    const int lv = nth_level(level_mask, slot);
-    const LevelInfo L = level_info(spec, lv);
-    const int lane = threadIdx.x & 63;
-    const uint32_t hx = threadIdx.x & 1u;
-    const uint32_t M = (uint32_t)live_points(src);
-    if (M == 0u) return;
-    const uint32_t step = (uint32_t)bpg * (ENC_BLOCK / 2);
-    const uint32_t n_iter = (M + step - 1u) / step;                     // wave-uniform trip count: the body uses DPP
-    const float* gplanes = dfeat + (size_t)(lv * F) * m_pad;
-    float* dxplanes = dxl + (size_t)(lv * 3) * m_pad;
-    const uint32_t plane_bytes = (uint32_t)m_pad * 4u;
-    SampleCursor cur;
-    cur.init((uint32_t)chunk * (ENC_BLOCK / 2) + (threadIdx.x >> 1), step, src.pts ? 1u : (uint32_t)src.n_samples);
-    const uint32_t last_ray = src.pts ? 0u : (M - 1u) / cur.S;
-    const bool uni = ray_uniform(src, 32u);
-    for (uint32_t it = 0; it < n_iter; ++it) {
-        const uint32_t m = cur.m;
-        const bool live = m < M;
-        const uint32_t mc = live ? m : M - 1u;                           // unconditional (clamped) loads
-        float g[F];
-        bool any = false;
-#pragma unroll
-        for (int f = 0; f < F; ++f) {
-            const float v = ld32_stream<float>(gplanes, (uint32_t)f * plane_bytes + mc * 4u);
-            g[f] = live ? v : 0.0f;
-            any |= (g[f] != 0.0f);
-        }
-        RawPoint p;
-        load_raw_point(src, mc, live ? cur.ray : last_ray, p, uni);
-        const uint32_t ray_cur = cur.ray;
-        cur.advance();
-        const bool wave_any = __ballot(any) != 0ull;
-        float dx[3] = {0.0f, 0.0f, 0.0f};
-        if (wave_any) {                                                  // wave-uniform: all lanes active inside
-            float x[3];
-            unit_point(src, p, x);
-            const Cell c = cell_of(L, x);
-            uint32_t e[4];
-            cell_entries_x(L, c, hx, e);
-            float d[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-            if (any) {                                                   // (a gather costs per ACTIVE lane and line: dead samples must not gather)
-                float tv[4][F];
-                gather_entries4<F>(table, e, tv);
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-#pragma unroll
-                    for (int f = 0; f < F; ++f) d[r] += g[f] * tv[r][f];
-            }
-            float dd[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) dd[r] = pair_partner_f(d[r]) - d[r];          // even lanes: dot(x + 1) - dot(x) of row r
-            const float fx = c.frac[0], fy = c.frac[1], fz = c.frac[2];
-            const float gy = 1.0f - fy, gz = 1.0f - fz;
-            const float wxl = hx ? fx : 1.0f - fx;
-            // differences along one axis, interpolated along the other two (rows: 0 = y0 z0, 1 = y1 z0, 2 = y0 z1, 3 = y1 z1)
-            const float dxv = (dd[0] * gy + dd[1] * fy) * gz + (dd[2] * gy + dd[3] * fy) * fz;
-            const float dyv = ((d[1] - d[0]) * gz + (d[3] - d[2]) * fz) * wxl;
-            const float dzv = ((d[2] - d[0]) * gy + (d[3] - d[1]) * fy) * wxl;
-            dx[0] = hx ? 0.0f : dxv * L.scale; dx[1] = dyv * L.scale; dx[2] = dzv * L.scale;
-        }
-        if constexpr (DXM == ENC_DX_RAYS) {
-            // a wave's 32 samples lie on one ray (n_samples % 64 == 0, checked by the caller); lane 0 holds the wave's first sample
-            if (wave_any) ray_accumulate_dx(dxl, (uint32_t)__builtin_amdgcn_readfirstlane((int)ray_cur), p.z, dx, lane, src.n_rays);
-        } else {
-            float s[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) s[k] = dx[k] + pair_partner_f(dx[k]);
-            if (live && hx == 0u) {
-#pragma unroll
-                for (int k = 0; k < 3; ++k) st32<float>(dxplanes, (uint32_t)k * plane_bytes + m * 4u, s[k]);
-            }
-        }
-    }
-}
+// (The input gradient as a kernel of its own, two lanes per sample, was measured slower than this fused form: docs/HISTORY.md 4.3.)
 
 __device__ __forceinline__ void store_stream_b128(uint64_t global_addr, uint4 v) {
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -660,12 +512,6 @@ __device__ __forceinline__ void xpair_overflow(long long* ovf_level, uint32_t fi
 #ifdef LNR_PHASE_TIMING
 __device__ unsigned long long lnr_phase_cycles[2 * LNR_N_PHASES];          // [8-byte record levels | x-pair levels]
 #endif
-// -DLNR_ABLATE (development builds only): LNR_X_DBG bits switch parts of encode_backward_kernel off, to time what is left
-#ifdef LNR_ABLATE
-#define DBG_SKIP(bit) ((sink.dbg & (bit)) != 0)
-#else
-#define DBG_SKIP(bit) false
-#endif
 
 // dynamic LDS: int cnt[maxo4], gcur[maxo4]; OwnerSlot slot[maxo] (16-byte aligned); then the staging buffer
 // XP: the launch's levels take x-pair records (compile-time: the two record formats share little code, and a kernel that carries both
@@ -673,11 +519,6 @@ __device__ unsigned long long lnr_phase_cycles[2 * LNR_N_PHASES];          // [8
 template <int F, int DXM, bool XP>
 #ifndef LNR_ENC_BWD_WAVES
 #define LNR_ENC_BWD_WAVES 4
-#endif
-// 1: the d/dx term and the next batch's inputs are taken over in front of the record copy-out (see the batch loop): encode_backward
-// 0.832 -> 0.783 ms, the iteration 1.918 -> 1.867 ms (profiles/r06_encode_backward_dx_before_copyout.txt); 0: the d/dx term after the passes
-#ifndef LNR_ENC_DX_BEFORE_COPYOUT
-#define LNR_ENC_DX_BEFORE_COPYOUT 1
 #endif
 __global__ void __launch_bounds__(ENC_BWD_BLOCK, LNR_ENC_BWD_WAVES)   // (max threads, min waves per SIMD): 4 = 128 VGPRs
 encode_backward_kernel(const LnrNetSpec spec, const float* __restrict__ table, const PointSrc src, const float* __restrict__ dfeat,
@@ -759,7 +600,7 @@ encode_backward_kernel(const LnrNetSpec spec, const float* __restrict__ table, c
             const bool in = cur.m < M;
             const uint32_t mc = in ? cur.m : M - 1u;          // unconditional (clamped) loads: a static number in flight
 #pragma unroll
-            for (int f = 0; f < F; ++f) g_next[f] = DBG_SKIP(32) ? ld32<float>(gplanes, (uint32_t)f * plane_bytes + mc * 4u) : ld32_stream<float>(gplanes, (uint32_t)f * plane_bytes + mc * 4u);
+            for (int f = 0; f < F; ++f) g_next[f] = ld32_stream<float>(gplanes, (uint32_t)f * plane_bytes + mc * 4u);
             load_raw_point(src, mc, in ? cur.ray : last_ray, p_next, uni);
         }
         const bool wave_any = __ballot(any) != 0ull;
@@ -777,14 +618,14 @@ encode_backward_kernel(const LnrNetSpec spec, const float* __restrict__ table, c
             cell_entries(L, c, e);
             // (a gather costs per ACTIVE lane and line - tools/gather_bench.hip - and on the fine levels no two lanes share a line:
             // the 48 % of the samples without a gradient must not gather)
-            if constexpr (EARLY_DX) { if (any && !DBG_SKIP(4)) gather_entries<F>(table, e, tv); }
+            if constexpr (EARLY_DX) { if (any) gather_entries<F>(table, e, tv); }
             cell_weights(c, w);
             // runs = consecutive samples (lanes of one 16-lane row) in the same CELL, not merely the same hashed entry
             if (combine) cell_runs(c, lane, head, run);
         }
         PHASE(1);
 #pragma unroll
-        for (int pass = 0; pass < (emit && !DBG_SKIP(16) ? NPASS : 0); ++pass) {
+        for (int pass = 0; pass < (emit ? NPASS : 0); ++pass) {
             // ---- A: this thread's records of the batch; rank within the owner's bucket from an LDS histogram
             float rv0[8], rv1[8]; int rrank[8];
 #pragma unroll
@@ -902,7 +743,6 @@ encode_backward_kernel(const LnrNetSpec spec, const float* __restrict__ table, c
             PHASE(6);
             __syncthreads();
             PHASE(7);
-#if LNR_ENC_DX_BEFORE_COPYOUT
             // Everything this batch still WAITS for from memory is taken over here, in front of the copy-out: the next batch's inputs
             // (requested at the top) and the gathers of the d/dx term.  Loads and stores share one in-order counter (vmcnt) and the record
             // stores below are invisible to the compiler (inline asm, data-dependent trip count): a wait placed behind them - the d/dx
@@ -913,12 +753,12 @@ encode_backward_kernel(const LnrNetSpec spec, const float* __restrict__ table, c
                 asm volatile("" : "+v"(p_next.z));
                 if constexpr (WANT_DX) {
                     float dx[3] = {0.0f, 0.0f, 0.0f};
-                    if (any && !DBG_SKIP(2)) {
+                    if (any) {
                         if constexpr (EARLY_DX) dx_from_entries<F>(L, c, g, tv, dx);
                         else { float tl[8][F]; gather_entries<F>(table, e, tl); dx_from_entries<F>(L, c, g, tl, dx); }
                     }
                     if constexpr (DXM == ENC_DX_RAYS) {
-                        if (wave_any && !DBG_SKIP(1))            // wave-uniform; lane 0 holds the wave's first (live) sample
+                        if (wave_any)            // wave-uniform; lane 0 holds the wave's first (live) sample
                             ray_accumulate_dx(dxl, (uint32_t)__builtin_amdgcn_readfirstlane((int)ray_cur), p_cur.z, dx, lane, src.n_rays);
                     } else if (live) {
 #pragma unroll
@@ -926,7 +766,6 @@ encode_backward_kernel(const LnrNetSpec spec, const float* __restrict__ table, c
                     }
                 }
             }
-#endif
             // ---- D: linear copy-out; neighbouring lanes write neighbouring records of the same region
             const int total = s_total;
             if (xp) {
@@ -936,7 +775,6 @@ encode_backward_kernel(const LnrNetSpec spec, const float* __restrict__ table, c
                     const float a0 = __uint_as_float(r4.y), a1 = __uint_as_float(r4.z), fx = __uint_as_float(r4.w & ~0xFu);
                     const OwnerSlot os = oslot[(int)(idx >> sink.shift) - first_owner];
                     const int k = i - os.scan;
-                    if (DBG_SKIP(8)) continue;
                     if (k < os.room) {
                         const LnrXRec rec = lnr_pack_xpair((idx & ((1u << LNR_SLICE_SHIFT) - 1u)) >> 1, t, a0, a1, fx);
                         store_stream_b96((((uint64_t)os.ptr_hi << 32) | os.ptr_lo) + (uint64_t)k * 12u, rec.a, rec.b, rec.c);
@@ -955,7 +793,6 @@ encode_backward_kernel(const LnrNetSpec spec, const float* __restrict__ table, c
                 const int local = (int)(idx >> sink.shift) - first_owner;
                 const OwnerSlot os = oslot[local];
                 const int k = i - os.scan;
-                if (DBG_SKIP(8)) continue;
                 if (k < os.room) {
                     if (PAIR) r2 = lnr_pack_pair((idx & ((1u << LNR_SLICE_SHIFT) - 1u)) >> 1, v0, v1);
                     store_stream_b64((((uint64_t)os.ptr_hi << 32) | os.ptr_lo) + (uint64_t)k * 8u, r2);
@@ -973,16 +810,16 @@ encode_backward_kernel(const LnrNetSpec spec, const float* __restrict__ table, c
             // no barrier here: the next histogram only touches cnt[], and its first barrier orders D before the next B/C
             PHASE(8);
         }
-#if LNR_ENC_DX_BEFORE_COPYOUT
-        if (!(emit && !DBG_SKIP(16))) {                       // (no passes ran: parameters frozen)
+        if (!emit) {                       // (no passes ran: parameters frozen.  The block of the last pass again, written out: as a shared
+                                           // helper or lambda it compiles to other code - profiles/dead_variant_removal.txt)
             if constexpr (WANT_DX) {
                 float dx[3] = {0.0f, 0.0f, 0.0f};
-                if (any && !DBG_SKIP(2)) {
+                if (any) {
                     if constexpr (EARLY_DX) dx_from_entries<F>(L, c, g, tv, dx);
                     else { float tl[8][F]; gather_entries<F>(table, e, tl); dx_from_entries<F>(L, c, g, tl, dx); }
                 }
                 if constexpr (DXM == ENC_DX_RAYS) {
-                    if (wave_any && !DBG_SKIP(1))            // wave-uniform; lane 0 holds the wave's first (live) sample
+                    if (wave_any)            // wave-uniform; lane 0 holds the wave's first (live) sample
                         ray_accumulate_dx(dxl, (uint32_t)__builtin_amdgcn_readfirstlane((int)ray_cur), p_cur.z, dx, lane, src.n_rays);
                 } else if (live) {
 #pragma unroll
@@ -990,22 +827,6 @@ encode_backward_kernel(const LnrNetSpec spec, const float* __restrict__ table, c
                 }
             }
         }
-#else
-        if constexpr (WANT_DX) {
-            float dx[3] = {0.0f, 0.0f, 0.0f};
-            if (any && !DBG_SKIP(2)) {
-                if constexpr (EARLY_DX) dx_from_entries<F>(L, c, g, tv, dx);
-                else { float tl[8][F]; gather_entries<F>(table, e, tl); dx_from_entries<F>(L, c, g, tl, dx); }
-            }
-            if constexpr (DXM == ENC_DX_RAYS) {
-                if (wave_any && !DBG_SKIP(1))            // wave-uniform; lane 0 holds the wave's first (live) sample
-                    ray_accumulate_dx(dxl, (uint32_t)__builtin_amdgcn_readfirstlane((int)ray_cur), p_cur.z, dx, lane, src.n_rays);
-            } else if (live) {
-#pragma unroll
-                for (int d = 0; d < 3; ++d) st32<float>(dxplanes, (uint32_t)d * plane_bytes + m * 4u, dx[d]);
-            }
-        }
-#endif
         PHASE(9);
     }
     PHASE_FLUSH(lnr_phase_cycles, xp ? LNR_N_PHASES : 0);
@@ -1134,12 +955,12 @@ encode_backward_binned_kernel(const LnrNetSpec spec, const float* __restrict__ t
             unit_point(src, p_cur, x);
             c = cell_of(L, x);
             cell_entries(L, c, e);
-            if constexpr (EARLY_DX) { if (any && !DBG_SKIP(4)) gather_entries<F>(table, e, tv); }
+            if constexpr (EARLY_DX) { if (any) gather_entries<F>(table, e, tv); }
             cell_weights(c, w);
             if (combine) cell_runs(c, lane, head, run);
         }
 #pragma unroll
-        for (int pass = 0; pass < (emit && !DBG_SKIP(16) ? NPASS : 0); ++pass) {
+        for (int pass = 0; pass < (emit ? NPASS : 0); ++pass) {
             // ---- A: every record is packed and put into its owner's bin at the offset a returning atomic hands out.  All of a
             // thread's atomics are issued before the first offset is used: one LDS round trip per batch instead of one per record
             // (measured: the rank atomics cost 0.11 of the x-pair levels' 0.54 ms when each was waited for in turn).
@@ -1156,7 +977,7 @@ encode_backward_binned_kernel(const LnrNetSpec spec, const float* __restrict__ t
                     at[k2] = NO_SLOT;
                     if (((a0[k2] != 0.0f) | (a1[k2] != 0.0f)) & (xt < 12u)) {
                         const int o = (int)((e[2 * k2] * F) >> LNR_SLICE_SHIFT) - first_owner;
-                        at[k2] = DBG_SKIP(64) ? (uint32_t)((threadIdx.x * 4 + k2) & 31) * REC : (uint32_t)atomicAdd(&fill[o], (int)REC);
+                        at[k2] = (uint32_t)atomicAdd(&fill[o], (int)REC);
                     }
                 }
 #pragma unroll
@@ -1164,12 +985,10 @@ encode_backward_binned_kernel(const LnrNetSpec spec, const float* __restrict__ t
                     if ((a0[k2] != 0.0f) | (a1[k2] != 0.0f)) {
                         const uint32_t fi = e[2 * k2] * F;
                         if (at[k2] <= (uint32_t)BIN - REC) {
-                            if (!DBG_SKIP(128)) {
-                                const int o = (int)(fi >> LNR_SLICE_SHIFT) - first_owner;
-                                const LnrXRec rec = lnr_pack_xpair((fi & ((1u << LNR_SLICE_SHIFT) - 1u)) >> 1, xt, a0[k2], a1[k2], c.frac[0]);
-                                uint32_t* dst = reinterpret_cast<uint32_t*>(stage + (uint32_t)o * BIN + at[k2]);
-                                dst[0] = rec.a; dst[1] = rec.b; dst[2] = rec.c;
-                            }
+                            const int o = (int)(fi >> LNR_SLICE_SHIFT) - first_owner;
+                            const LnrXRec rec = lnr_pack_xpair((fi & ((1u << LNR_SLICE_SHIFT) - 1u)) >> 1, xt, a0[k2], a1[k2], c.frac[0]);
+                            uint32_t* dst = reinterpret_cast<uint32_t*>(stage + (uint32_t)o * BIN + at[k2]);
+                            dst[0] = rec.a; dst[1] = rec.b; dst[2] = rec.c;
                         } else {
                             // bin full or region closed: same rounding as a packed record.  Corners that straddle owner slices (xt >= 12): as
                             // the scan partition's two single-corner records (t = 0, fx = 0, the x weight applied here), so that the two
@@ -1219,81 +1038,79 @@ encode_backward_binned_kernel(const LnrNetSpec spec, const float* __restrict__ t
                     }
                 }
             }
-            if (!DBG_SKIP(256)) __syncthreads();
+            __syncthreads();
             // ---- B: whole lines out, tail to the front
-            if (!DBG_SKIP(32)) {
-                const uint32_t f_raw = own ? (uint32_t)fill[my_owner] : 0u;
-                uint32_t valid = 0u;
-                if (!closed) {
-                    const uint32_t n_new = (f_raw - tail) / REC, n_room = ((uint32_t)BIN - tail) / REC;
-                    valid = tail + (n_new < n_room ? n_new : n_room) * REC;
-                }
-                const uint32_t nlines = valid >> 7, rem = valid & 127u;
-                const char* bins = stage + (uint32_t)(wave * OPW) * BIN;
-                // tail: the G lanes of an owner move the (< 128) bytes behind its last whole line to the front of its bin
-                // (LDS operations of a wave execute in order: the line reads below come first, the tail's read next, its write last)
-                const uint32_t sub = (uint32_t)(lane % G) * (128u / G);
-                const bool mv = nlines > 0u && sub < rem;
-                char* my_bin = stage + (uint32_t)my_owner * BIN;
-                const int half = lane / LPB, piece = lane % LPB;                                            // which bin of a copy instruction, which 16 bytes of it
-#pragma unroll
-                for (int j0 = 0; j0 < OPW / BPI; j0 += 4) {
-                    uint4 v[4];
-                    uint32_t n16[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        // line count of the bin this lane copies from: wave-uniform per bin, selected per lane when an instruction covers two bins
-                        n16[j] = (uint32_t)__builtin_amdgcn_readlane((int)nlines, ((j0 + j) * BPI) * G) * 8u;
-                        if constexpr (BPI == 2) { const uint32_t n1 = (uint32_t)__builtin_amdgcn_readlane((int)nlines, ((j0 + j) * BPI + 1) * G) * 8u; if (half) n16[j] = n1; }
-                        if ((uint32_t)piece < n16[j]) v[j] = *reinterpret_cast<const uint4*>(bins + (j0 + j) * (BPI * BIN) + lane * 16);
-                    }
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int o0 = wave * OPW + (j0 + j) * BPI;
-                        uint64_t dst = reinterpret_cast<uint64_t>(level_regions) + ((size_t)o0 * bpg + chunk) * (size_t)region_bytes +
-                                       (uint32_t)__builtin_amdgcn_readlane((int)gpos, ((j0 + j) * BPI) * G);
-                        if constexpr (BPI == 2) {
-                            const uint64_t d1 = reinterpret_cast<uint64_t>(level_regions) + ((size_t)(o0 + 1) * bpg + chunk) * (size_t)region_bytes +
-                                                (uint32_t)__builtin_amdgcn_readlane((int)gpos, ((j0 + j) * BPI + 1) * G);
-                            if (half) dst = d1;
-                        }
-                        if ((uint32_t)piece < n16[j] && !DBG_SKIP(8)) store_stream_b128(dst + (uint32_t)piece * 16u, v[j]);
-                    }
-                }
-                if (mv) {
-                    uint4 t4[TQ];
-#pragma unroll
-                    for (int q = 0; q < TQ; ++q) if (sub + 16u * q < rem) t4[q] = *reinterpret_cast<const uint4*>(my_bin + (nlines << 7) + sub + 16u * q);
-#pragma unroll
-                    for (int q = 0; q < TQ; ++q) if (sub + 16u * q < rem) *reinterpret_cast<uint4*>(my_bin + sub + 16u * q) = t4[q];
-                }
-                gpos += nlines << 7;
-                tail = rem;
-                if (!closed && gpos + (uint32_t)(BIN + 128) > region_bytes) {
-                    // no room for another worst-case batch: the tail - now at the front of the bin - goes out as the region's last
-                    // (partial) line and the owner closes; whatever is addressed to it from here on takes the overflow path
-                    char* dst = level_regions + ((size_t)my_owner * bpg + chunk) * (size_t)region_bytes + gpos;
-#pragma unroll
-                    for (int q = 0; q < 32 / G; ++q) {
-                        const uint32_t off = sub + 4u * q;
-                        if (off < rem) *reinterpret_cast<uint32_t*>(dst + off) = *reinterpret_cast<const uint32_t*>(my_bin + off);
-                    }
-                    gpos += rem;
-                    tail = 0u;
-                    closed = true;
-                }
-                if (lane % G == 0 && own) fill[my_owner] = closed ? ENC_BIN_CLOSED : (int)tail;
+            const uint32_t f_raw = own ? (uint32_t)fill[my_owner] : 0u;
+            uint32_t valid = 0u;
+            if (!closed) {
+                const uint32_t n_new = (f_raw - tail) / REC, n_room = ((uint32_t)BIN - tail) / REC;
+                valid = tail + (n_new < n_room ? n_new : n_room) * REC;
             }
+            const uint32_t nlines = valid >> 7, rem = valid & 127u;
+            const char* bins = stage + (uint32_t)(wave * OPW) * BIN;
+            // tail: the G lanes of an owner move the (< 128) bytes behind its last whole line to the front of its bin
+            // (LDS operations of a wave execute in order: the line reads below come first, the tail's read next, its write last)
+            const uint32_t sub = (uint32_t)(lane % G) * (128u / G);
+            const bool mv = nlines > 0u && sub < rem;
+            char* my_bin = stage + (uint32_t)my_owner * BIN;
+            const int half = lane / LPB, piece = lane % LPB;                                            // which bin of a copy instruction, which 16 bytes of it
+#pragma unroll
+            for (int j0 = 0; j0 < OPW / BPI; j0 += 4) {
+                uint4 v[4];
+                uint32_t n16[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    // line count of the bin this lane copies from: wave-uniform per bin, selected per lane when an instruction covers two bins
+                    n16[j] = (uint32_t)__builtin_amdgcn_readlane((int)nlines, ((j0 + j) * BPI) * G) * 8u;
+                    if constexpr (BPI == 2) { const uint32_t n1 = (uint32_t)__builtin_amdgcn_readlane((int)nlines, ((j0 + j) * BPI + 1) * G) * 8u; if (half) n16[j] = n1; }
+                    if ((uint32_t)piece < n16[j]) v[j] = *reinterpret_cast<const uint4*>(bins + (j0 + j) * (BPI * BIN) + lane * 16);
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int o0 = wave * OPW + (j0 + j) * BPI;
+                    uint64_t dst = reinterpret_cast<uint64_t>(level_regions) + ((size_t)o0 * bpg + chunk) * (size_t)region_bytes +
+                                   (uint32_t)__builtin_amdgcn_readlane((int)gpos, ((j0 + j) * BPI) * G);
+                    if constexpr (BPI == 2) {
+                        const uint64_t d1 = reinterpret_cast<uint64_t>(level_regions) + ((size_t)(o0 + 1) * bpg + chunk) * (size_t)region_bytes +
+                                            (uint32_t)__builtin_amdgcn_readlane((int)gpos, ((j0 + j) * BPI + 1) * G);
+                        if (half) dst = d1;
+                    }
+                    if ((uint32_t)piece < n16[j]) store_stream_b128(dst + (uint32_t)piece * 16u, v[j]);
+                }
+            }
+            if (mv) {
+                uint4 t4[TQ];
+#pragma unroll
+                for (int q = 0; q < TQ; ++q) if (sub + 16u * q < rem) t4[q] = *reinterpret_cast<const uint4*>(my_bin + (nlines << 7) + sub + 16u * q);
+#pragma unroll
+                for (int q = 0; q < TQ; ++q) if (sub + 16u * q < rem) *reinterpret_cast<uint4*>(my_bin + sub + 16u * q) = t4[q];
+            }
+            gpos += nlines << 7;
+            tail = rem;
+            if (!closed && gpos + (uint32_t)(BIN + 128) > region_bytes) {
+                // no room for another worst-case batch: the tail - now at the front of the bin - goes out as the region's last
+                // (partial) line and the owner closes; whatever is addressed to it from here on takes the overflow path
+                char* dst = level_regions + ((size_t)my_owner * bpg + chunk) * (size_t)region_bytes + gpos;
+#pragma unroll
+                for (int q = 0; q < 32 / G; ++q) {
+                    const uint32_t off = sub + 4u * q;
+                    if (off < rem) *reinterpret_cast<uint32_t*>(dst + off) = *reinterpret_cast<const uint32_t*>(my_bin + off);
+                }
+                gpos += rem;
+                tail = 0u;
+                closed = true;
+            }
+            if (lane % G == 0 && own) fill[my_owner] = closed ? ENC_BIN_CLOSED : (int)tail;
             __syncthreads();
         }
         if constexpr (WANT_DX) {
             float dx[3] = {0.0f, 0.0f, 0.0f};
-            if (any && !DBG_SKIP(2)) {
+            if (any) {
                 if constexpr (EARLY_DX) dx_from_entries<F>(L, c, g, tv, dx);
                 else { float tl[8][F]; gather_entries<F>(table, e, tl); dx_from_entries<F>(L, c, g, tl, dx); }
             }
             if constexpr (DXM == ENC_DX_RAYS) {
-                if (wave_any && !DBG_SKIP(1)) ray_accumulate_dx(dxl, (uint32_t)__builtin_amdgcn_readfirstlane((int)ray_cur), p_cur.z, dx, lane, src.n_rays);
+                if (wave_any) ray_accumulate_dx(dxl, (uint32_t)__builtin_amdgcn_readfirstlane((int)ray_cur), p_cur.z, dx, lane, src.n_rays);
             } else if (live) {
 #pragma unroll
                 for (int d = 0; d < 3; ++d) st32<float>(dxplanes, (uint32_t)d * plane_bytes + m * 4u, dx[d]);
@@ -1386,12 +1203,7 @@ int lnr_encode_forward(const LnrNetSpec* spec, const float* params, const PointS
         }
         return LNR_OK;
     }
-    uint32_t level_mask = spec->n_levels >= 32 ? 0xFFFFFFFFu : (1u << spec->n_levels) - 1u;
-#ifdef LNR_ABLATE
-    // development builds, read at every call (tools/probe_forward_levels.py walks them in one process): time a subset of the levels
-    if (const char* v = getenv("LNR_X_FWD_LEVELS")) level_mask &= (uint32_t)strtol(v, nullptr, 0);
-    if (level_mask == 0u) return LNR_OK;
-#endif
+    const uint32_t level_mask = spec->n_levels >= 32 ? 0xFFFFFFFFu : (1u << spec->n_levels) - 1u;
     const dim3 mgrid((unsigned)(__builtin_popcount(level_mask) * bpg));
     const int xcd = lnr_xcd_affine(__builtin_popcount(level_mask), cap_points, true) ? 1 : 0;
 #define LNR_FWD(F, H) hipLaunchKernelGGL((encode_forward_kernel<F, H>), mgrid, block, 0, st, *spec, table, *src, feat, m_pad, (int)bpg, level_mask, xcd)
@@ -1417,66 +1229,26 @@ int lnr_encode_forward(const LnrNetSpec* spec, const float* params, const PointS
 int lnr_encode_backward(const LnrNetSpec* spec, const float* params, const PointSrc* src, int64_t cap_points, const float* dfeat,
                         float* dxl, int64_t m_pad, float* grad_table, void* regions, const RegionPlan* plan, int* counts, int bpg,
                         int maxo, int shift, long long* ovf, int* ovf_flag, int epoch, float* d_pts, float* d_rays_acc, long long* ray_acc, bool bins_w8,
-                        int parts, hipStream_t st) {
+                        hipStream_t st) {
     const float* table = params + spec->n_mlp_params;
     const bool hash = spec->encoding == LNR_ENC_HASHGRID;
     // d/dx mode: d_rays_acc (rays form, n_samples % 64 == 0, checked by the caller) > d_pts (planes) > none
     const int dxm = d_rays_acc ? ENC_DX_RAYS : (d_pts ? ENC_DX_PLANES : ENC_DX_NONE);
     float* dx_out = d_rays_acc ? reinterpret_cast<float*>(ray_acc) : dxl;
-    // parts (LNR_ENC_PART_*): the input gradient and the table-gradient partition are separate launches of a hash grid's backward
-    // (LNR_SPLIT_DX), so that the caller can hand the input gradient on before the partition starts; the partition kernels then carry no d/dx
-    const bool do_dx = (parts & LNR_ENC_PART_DX) != 0, do_part = (parts & LNR_ENC_PART_RECORDS) != 0;
-#if LNR_SPLIT_DX
-    const int dxm_part = hash ? ENC_DX_NONE : dxm;
-#else
-    const int dxm_part = dxm;
-    LNR_REQUIRE(do_dx && do_part, "lnr_encode_backward: this build computes d/dx inside the partition kernels");
-#endif
     // six sums + one non-finite word per ray, rounded up to 16 bytes (one fill kernel instead of an aligned part and a tail; the workspace has the room)
-    if (do_dx && d_rays_acc && hipMemsetAsync(ray_acc, 0, ((((size_t)src->n_rays * 7) * sizeof(long long)) + 15) & ~(size_t)15, st) != hipSuccess) {
+    if (d_rays_acc && hipMemsetAsync(ray_acc, 0, ((((size_t)src->n_rays * 7) * sizeof(long long)) + 15) & ~(size_t)15, st) != hipSuccess) {
         lnr_set_error("lnr_density_backward: hipMemsetAsync failed");
         return LNR_ERR_LAUNCH;
     }
     int n_groups = 1;
-#if LNR_SPLIT_DX
-    if (hash && do_dx && dxm != ENC_DX_NONE) {
-        uint32_t level_mask = spec->n_levels >= 32 ? 0xFFFFFFFFu : (1u << spec->n_levels) - 1u;
-#ifdef LNR_ABLATE
-        static const long dx_levels = getenv("LNR_X_LEVELS") ? strtol(getenv("LNR_X_LEVELS"), nullptr, 0) : -1;
-        level_mask &= (uint32_t)dx_levels;
-#endif
-        int64_t b = (cap_points + ENC_BLOCK * 4 - 1) / (ENC_BLOCK * 4);          // ~8 samples per lane pair
-        if (b < 1) b = 1;
-        if (b > 2048) b = 2048;
-        const dim3 dgrid((unsigned)(__builtin_popcount(level_mask) * b)), dblock(ENC_BLOCK);
-        const int xcd = lnr_xcd_affine(__builtin_popcount(level_mask), cap_points, false) ? 1 : 0;
-        LnrProfScope prof("encode_dx", st);
-#define LNR_LAUNCH_DXP(F)                                                                                                                   \
-        do {                                                                                                                               \
-            if (dxm == ENC_DX_RAYS) hipLaunchKernelGGL((encode_dx_pair_kernel<F, ENC_DX_RAYS>), dgrid, dblock, 0, st, *spec, table, *src, dfeat, dx_out, m_pad, (int)b, level_mask, xcd); \
-            else hipLaunchKernelGGL((encode_dx_pair_kernel<F, ENC_DX_PLANES>), dgrid, dblock, 0, st, *spec, table, *src, dfeat, dx_out, m_pad, (int)b, level_mask, xcd);               \
-        } while (0)
-        if (level_mask != 0u) switch (spec->n_features) {
-            case 1: LNR_LAUNCH_DXP(1); break;
-            case 2: LNR_LAUNCH_DXP(2); break;
-            case 4: LNR_LAUNCH_DXP(4); break;
-            default: LNR_LAUNCH_DXP(8); break;
-        }
-#undef LNR_LAUNCH_DXP
-    }
-#endif
     if (hash) n_groups = spec->n_levels;
-    if (hash && do_part && (regions != nullptr || dxm_part != ENC_DX_NONE)) {
+    if (hash && (regions != nullptr || dxm != ENC_DX_NONE)) {
         LevelList rec_levels, xp_levels, brec_levels, bxp_levels;          // 8-byte record levels, x-pair record levels, and their binned forms: one launch each
         rec_levels.n = xp_levels.n = brec_levels.n = bxp_levels.n = 0;
         const bool allow_binned = regions != nullptr && maxo <= LNR_BIN_MAX_OWNERS;
         int ovf_total = 0;
         for (int l = 0; l < spec->n_levels; ++l) {
             const int nfl = (int)spec->level_size[l] * spec->n_features;
-#ifdef LNR_ABLATE
-            static const int lmask = getenv("LNR_X_LEVELS") ? (int)strtol(getenv("LNR_X_LEVELS"), nullptr, 0) : -1;
-            if (!((lmask >> l) & 1)) { ovf_total += nfl; continue; }
-#endif
             const bool is_xp = spec->n_features == 2 && plan->xp[l] != 0;
             const bool is_binned = allow_binned && plan->binned[l] != 0 && plan->bytes[l] != 0;
             LevelList& ll = is_xp ? (is_binned ? bxp_levels : xp_levels) : (is_binned ? brec_levels : rec_levels);
@@ -1487,13 +1259,13 @@ int lnr_encode_backward(const LnrNetSpec* spec, const float* params, const Point
 #define LNR_LAUNCH_DXM(KERNEL, F, XP, ...)                                                                                    \
         do {                                                                                                                  \
             hipError_t e_ = hipSuccess;                                                                                       \
-            const void* fn_ = dxm_part == ENC_DX_RAYS ? reinterpret_cast<const void*>(KERNEL<F, ENC_DX_RAYS, XP>)                  \
-                            : dxm_part == ENC_DX_PLANES ? reinterpret_cast<const void*>(KERNEL<F, ENC_DX_PLANES, XP>)              \
+            const void* fn_ = dxm == ENC_DX_RAYS ? reinterpret_cast<const void*>(KERNEL<F, ENC_DX_RAYS, XP>)                  \
+                            : dxm == ENC_DX_PLANES ? reinterpret_cast<const void*>(KERNEL<F, ENC_DX_PLANES, XP>)              \
                                                    : reinterpret_cast<const void*>(KERNEL<F, ENC_DX_NONE, XP>);               \
             e_ = hipFuncSetAttribute(fn_, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                              \
             if (e_ != hipSuccess) { lnr_set_error("lnr_density_backward: hipFuncSetAttribute(%zu) failed", lds); return LNR_ERR_LAUNCH; } \
-            if (dxm_part == ENC_DX_RAYS) hipLaunchKernelGGL((KERNEL<F, ENC_DX_RAYS, XP>), grid, block, lds, st, __VA_ARGS__);   \
-            else if (dxm_part == ENC_DX_PLANES) hipLaunchKernelGGL((KERNEL<F, ENC_DX_PLANES, XP>), grid, block, lds, st, __VA_ARGS__); \
+            if (dxm == ENC_DX_RAYS) hipLaunchKernelGGL((KERNEL<F, ENC_DX_RAYS, XP>), grid, block, lds, st, __VA_ARGS__);   \
+            else if (dxm == ENC_DX_PLANES) hipLaunchKernelGGL((KERNEL<F, ENC_DX_PLANES, XP>), grid, block, lds, st, __VA_ARGS__); \
             else hipLaunchKernelGGL((KERNEL<F, ENC_DX_NONE, XP>), grid, block, lds, st, __VA_ARGS__);                      \
         } while (0)
 #define LNR_LAUNCH_F(KERNEL, ...)                                                   \
@@ -1509,32 +1281,15 @@ int lnr_encode_backward(const LnrNetSpec* spec, const float* params, const Point
             sink.ovf_flag = ovf_flag; sink.epoch = epoch;
             sink.grad_table = grad_table; sink.ovf = ovf; sink.regions = regions; sink.plan = *plan; sink.counts = counts; sink.maxo = maxo; sink.shift = shift;
             sink.combine_scale_max = LNR_COMBINE_SCALE_MAX;
-#ifdef LNR_ABLATE
-            sink.dbg = getenv("LNR_X_DBG") ? atoi(getenv("LNR_X_DBG")) : 0;
-#endif
             LnrProfScope prof("encode_backward", st);
             const int maxo4 = (maxo + 3) & ~3;
-            size_t lds = (size_t)(2 * maxo4 + 4 * maxo) * sizeof(int) + (size_t)ENC_STAGE_RECORDS * (spec->n_features >= 2 ? 16 : 8);
-            // development probe (-DLNR_DEV_PROBES builds only; profiles/r06_occupancy_probes.txt): unused LDS behind the staging buffer, so that ONE workgroup fits a CU
-            // (two waves per SIMD instead of four) - does the pair wait for latencies more waves would cover, or for throughput?
-#ifdef LNR_DEV_PROBES
-            static const int lds_pad = getenv("LNR_ENC_BWD_LDS_PAD") ? atoi(getenv("LNR_ENC_BWD_LDS_PAD")) : 0;
-#else
-            const int lds_pad = 0;
-#endif
-            lds += (size_t)lds_pad;
+            const size_t lds = (size_t)(2 * maxo4 + 4 * maxo) * sizeof(int) + (size_t)ENC_STAGE_RECORDS * (spec->n_features >= 2 ? 16 : 8);
             if (rec_levels.n > 0) {
                 const dim3 grid((unsigned)(rec_levels.n * bpg));
                 sink.xcd_affine = lnr_xcd_affine(rec_levels.n, cap_points, false) ? 1 : 0;
                 LNR_LAUNCH_F(encode_backward_kernel, *spec, table, *src, dfeat, dx_out, m_pad, bpg, rec_levels, sink);
             }
             if (xp_levels.n > 0) {                                          // n_features == 2
-                // development probe: a smaller staging buffer for the x-pair launch (4 records per sample + straddling cells), so that
-                // three workgroups fit a CU when the kernel is built for six waves per SIMD (-DLNR_ENC_BWD_WAVES=6)
-#ifdef LNR_DEV_PROBES
-                static const int xp_stage = getenv("LNR_ENC_BWD_XP_STAGE") ? atoi(getenv("LNR_ENC_BWD_XP_STAGE")) : 0;
-                if (xp_stage > 0) lds = (size_t)(2 * maxo4 + 4 * maxo) * sizeof(int) + (size_t)xp_stage * 16 + (size_t)lds_pad;
-#endif
                 const dim3 grid((unsigned)(xp_levels.n * bpg));
                 sink.xcd_affine = lnr_xcd_affine(xp_levels.n, cap_points, false) ? 1 : 0;
                 LNR_LAUNCH_DXM(encode_backward_kernel, 2, true, *spec, table, *src, dfeat, dx_out, m_pad, bpg, xp_levels, sink);
@@ -1549,11 +1304,11 @@ int lnr_encode_backward(const LnrNetSpec* spec, const float* params, const Point
                     const dim3 grid_b((unsigned)((LIST).n * bpg));                                                                  \
                     sink.xcd_affine = lnr_xcd_affine((LIST).n, cap_points, false) ? 1 : 0;                                                             \
                     const void* fn_ = nullptr;                                                                                      \
-                    if (nw == 8) fn_ = dxm_part == ENC_DX_RAYS ? (const void*)encode_backward_binned_kernel<F, ENC_DX_RAYS, XP, 8>       \
-                                     : dxm_part == ENC_DX_PLANES ? (const void*)encode_backward_binned_kernel<F, ENC_DX_PLANES, XP, 8>   \
+                    if (nw == 8) fn_ = dxm == ENC_DX_RAYS ? (const void*)encode_backward_binned_kernel<F, ENC_DX_RAYS, XP, 8>       \
+                                     : dxm == ENC_DX_PLANES ? (const void*)encode_backward_binned_kernel<F, ENC_DX_PLANES, XP, 8>   \
                                                             : (const void*)encode_backward_binned_kernel<F, ENC_DX_NONE, XP, 8>;    \
-                    else fn_ = dxm_part == ENC_DX_RAYS ? (const void*)encode_backward_binned_kernel<F, ENC_DX_RAYS, XP, 4>               \
-                             : dxm_part == ENC_DX_PLANES ? (const void*)encode_backward_binned_kernel<F, ENC_DX_PLANES, XP, 4>           \
+                    else fn_ = dxm == ENC_DX_RAYS ? (const void*)encode_backward_binned_kernel<F, ENC_DX_RAYS, XP, 4>               \
+                             : dxm == ENC_DX_PLANES ? (const void*)encode_backward_binned_kernel<F, ENC_DX_PLANES, XP, 4>           \
                                                     : (const void*)encode_backward_binned_kernel<F, ENC_DX_NONE, XP, 4>;            \
                     if (hipFuncSetAttribute(fn_, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b) != hipSuccess) {           \
                         lnr_set_error("lnr_density_backward: hipFuncSetAttribute(%zu) failed", lds_b); return LNR_ERR_LAUNCH;       \
@@ -1587,13 +1342,12 @@ int lnr_encode_backward(const LnrNetSpec* spec, const float* params, const Point
         }
 #undef LNR_LAUNCH_F
 #undef LNR_LAUNCH_DXM
-    } else if (!hash && do_dx && dxm != ENC_DX_NONE) {
+    } else if (!hash && dxm != ENC_DX_NONE) {
         // frequency encoding: no table, one plane group; the per-ray mode is served through the planes by the caller
         int64_t blocks = (cap_points + ENC_BLOCK - 1) / ENC_BLOCK;
         if (blocks > 4096) blocks = 4096;
         hipLaunchKernelGGL(freq_backward_kernel, dim3((unsigned)blocks), dim3(ENC_BLOCK), 0, st, *spec, *src, dfeat, dxl, m_pad);
     }
-    if (!do_dx) return LNR_OK;
     if (dxm == ENC_DX_RAYS) {
         hipLaunchKernelGGL(ray_grad_apply_kernel, dim3((unsigned)((src->n_rays * 6 + ENC_BLOCK - 1) / ENC_BLOCK)), dim3(ENC_BLOCK), 0, st,
                            ray_acc, src->n_rays, src->n_rays_dev, d_rays_acc);

@@ -35,16 +35,13 @@ __host__ __device__ inline int lnr_freq_feature_at(int p, int nf) {
 // 2^(4 (sl / 3)): the literal part of slot sl's frequency
 __device__ __forceinline__ float lnr_freq_slot_scale(int sl) { return __uint_as_float((uint32_t)(127 + 4 * (sl / 3)) << 23); }
 
-// LNR_FREQ_HW_SIN = 1 (default): sin / cos of the phase from the hardware's v_sin_f32 / v_cos_f32.  Measured on MI355X
+// sin / cos of the phase come from the hardware's v_sin_f32 / v_cos_f32.  Measured on MI355X
 // (tools/valu_rate.hip, profiles/r06_valu_rate.txt): max abs error 1.25e-7 over [-1, 1] revolutions - as good as the minimax
 // polynomials - at 7.2 cycles per wave instruction, against ~25 instructions (~70 cycles, four of them selects) for the Cody-Waite
 // route.  The instructions take REVOLUTIONS: with y = x 2^f (exact) the reference's phase ph = rn(y fl(pi)) is
 //   ph = pi y + dl,   dl = y (fl(pi) - pi) - e1,   e1 = y fl(pi) - ph  (the product's rounding error, exact from one fma),
 // so sin(ph) = sin(pi y) cos(dl) + cos(pi y) sin(dl) with sin(pi y) = v_sin(fract(y / 2)) - the reduction is an exact v_fract, no
-// Cody-Waite - and |dl| < 4.2e-4 for f <= 11 (first order; the fused kernels take nf <= 12).  0: the polynomial route of sincos_f32 (A/B, parity checks).
-#ifndef LNR_FREQ_HW_SIN
-#define LNR_FREQ_HW_SIN 1
-#endif
+// Cody-Waite - and |dl| < 4.2e-4 for f <= 11 (first order; the fused kernels take nf <= 12).
 
 // The slot-independent part of a phase.  Slot sl of a lane evaluates y = xg S with xg = x 2^g (the lane's share) and S = 2^(4 (sl / 3)) a
 // literal; scaling by a power of two commutes with every rounding below, so ph(y) = S ph(xg) and dl(y) = S dl(xg) EXACTLY: the three
@@ -57,7 +54,7 @@ __device__ __forceinline__ FreqBase freq_base(float xg) {
     b.dl0 = __builtin_fmaf(xg, 8.742278000372485e-8f, -e1);
     return b;
 }
-// freq_pair<false>(xg S, ...) from the shared part (bit-identical; LNR_FREQ_HW_SIN route only)
+// freq_pair<false>(xg S, ...) from the shared part (bit-identical)
 __device__ __forceinline__ uint32_t freq_pair_scaled(float xg, const FreqBase& b, float S) {
     typedef _Float16 h2 __attribute__((ext_vector_type(2)));
     const float ph = b.ph0 * S, dl = b.dl0 * S;                                // (exact)
@@ -78,17 +75,12 @@ template <bool DERIV>
 __device__ __forceinline__ uint32_t freq_pair(float y, float dph, float& ds, float& dc) {
     typedef _Float16 h2 __attribute__((ext_vector_type(2)));
     const float ph = lnr_mul_rn(y, LNR_PI_F);
-    float s, c;
-#if LNR_FREQ_HW_SIN
     const float e1 = __builtin_fmaf(y, LNR_PI_F, -ph);
     const float dl = __builtin_fmaf(y, 8.742278000372485e-8f, -e1);          // ph - pi y: |dl| < 4.2e-4, the dropped dl^2 / 2 < 9e-8
     const float r = __builtin_amdgcn_fractf(y * 0.5f);
     const float S = __builtin_amdgcn_sinf(r), C = __builtin_amdgcn_cosf(r);
-    s = __builtin_fmaf(C, dl, S);
-    c = __builtin_fmaf(-S, dl, C);
-#else
-    sincos_f32(ph, &s, &c);
-#endif
+    const float s = __builtin_fmaf(C, dl, S);
+    const float c = __builtin_fmaf(-S, dl, C);
     // the reference's second phase h = rn(ph + fl(pi/2)) and e = its rounding error, by Fast2Sum (three operations): exact whenever
     // |ph| >= fl(pi/2), and otherwise (h < pi: half an ulp is 1.2e-7) off by at most that - the size of v_sin_f32's own error; Knuth's
     // branch-free TwoSum, exact everywhere, is six (freq_forward_h16_kernel, whose planes nf > 12 still use)

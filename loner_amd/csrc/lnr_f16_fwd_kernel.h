@@ -343,17 +343,11 @@ mlp_forward_f16_gen_kernel(const LnrNetSpec spec, const float* __restrict__ para
         if (sl < fq_slots) {
 #pragma unroll
             for (int t = 0; t < CT; ++t) {
-#if LNR_FREQ_HW_SIN
                 float y = xu[t][sl % 3];
                 asm volatile("" : "+v"(y));                               // (pinned: see fq_slot)
                 uint32_t v = freq_pair_scaled(y, fb[t][sl % 3], lnr_freq_slot_scale(sl));
                 asm volatile("" : "+v"(v));
                 x[sl >> 2][t][sl & 3] = v;
-#else
-                (void)fb;
-                float d0, d1;
-                x[sl >> 2][t][sl & 3] = freq_pair<false>(xu[t][sl % 3] * lnr_freq_slot_scale(sl), 0.0f, d0, d1);
-#endif
             }
         } else if (sl < 4 * KT) {                                         // a dead slot of a live K block: zero (its weights are zero too)
 #pragma unroll

@@ -13,8 +13,7 @@ import os
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# (LNR_LIB_PATH: the experiment scripts under tools/ point this at development builds, e.g. -DLNR_ABLATE)
-LIB_PATH = os.environ.get("LNR_LIB_PATH") or os.path.join(_HERE, "_lib", "libloner_hip.so")
+LIB_PATH = os.environ.get("LNR_LIB_PATH") or os.path.join(_HERE, "_lib", "libloner_hip.so")    # (LNR_LIB_PATH: tools/ scripts load development builds)
 
 MAX_LEVELS = 32
 RAY_STRIDE = 13

@@ -51,7 +51,7 @@ def test_pair_reduction_reproduces_both_features():
 
 
 def test_hardware_sine_route_reproduces_both_features():
-    """freq_pair with LNR_FREQ_HW_SIN (lnr_f16_freq.h): sin / cos(pi y) from v_sin_f32 / v_cos_f32 of fract(y / 2) (revolutions; modelled
+    """freq_pair (lnr_f16_freq.h): sin / cos(pi y) from v_sin_f32 / v_cos_f32 of fract(y / 2) (revolutions; modelled
     here as the exact function + the 1.25e-7 the instructions were measured at, profiles/r06_valu_rate.txt) and the first-order correction
     for dl = ph - pi y, recovered exactly from one fma - against the reference's sin(ph), sin(rn(ph + pi/2))."""
     rng = np.random.default_rng(2)
