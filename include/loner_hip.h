@@ -545,6 +545,42 @@ int lnr_icp_point_to_plane(const void* grid, int64_t n_targets, const double* ta
                            double max_distance, const double* init, double relative_fitness, double relative_rmse, int32_t max_iteration,
                            void* workspace, size_t workspace_bytes, double* result_dev, int64_t* info_dev, void* stream);
 
+/* ---- tracking (src/common/frame.py:104-145; src/common/sensors.py:176-232; src/tracking/tracker.py:257-297) ----------------- */
+#define LNR_MOCOMP_CONSTS 30      /* fp64 entries of lnr_motion_compensate's consts */
+#define LNR_SKY_MAX_RAYS 65160    /* 181 x 360: the row stride lnr_sky_rays' output needs */
+
+/* Frame.build_point_cloud (frame.py:136-144): the points of scan entries start, start + step, ... below stop (0 <= start,
+ * stop <= n_points, step >= 1; the host derives them from the timestamps with the reference's expressions).  ray_directions fp32
+ * [3, n_points], distances fp32 [n_points]; points fp64 [m,3], m = ceil((stop - start) / step): each coordinate is the fp32 product
+ * dir * dist widened to fp64, the array the reference hands to open3d, in the layout lnr_nn_grid_build and the ICP take. */
+int lnr_frame_cloud(const float* ray_directions, const float* distances, int64_t n_points, int64_t start, int64_t stop, int64_t step,
+                    double* points, void* stream);
+
+/* LidarScan.motion_compensate (sensors.py:176-232), in place on ray_directions [3, n_points] and distances [n_points]; timestamps
+ * [n_points] (fp32, or fp64 when timestamps_fp64 != 0) are only read.  Per point f = (t_i - t0) / denom in the timestamps' type
+ * (denom = t1 - t0 as the caller's own subtraction gave it; not clamped: the reference extrapolates), then in fp64:
+ * trans = t_start + f (t_end - t_start); R = R_start exp(f theta axis) by Rodrigues' formula, R = R_start when theta < 1e-9 (the
+ * reference's NUMERIC_TOLERANCE branch); q = T_target^-1 [R | trans] (dir dist); distances = |q| and ray_directions = q / |q|, each
+ * rounded to fp32 once, at the store.  The reference's own chain is fp32 through pytorch3d; the fp64 value is this entry's
+ * definition.  consts host fp64 [LNR_MOCOMP_CONSTS]: theta axis [3] (the axis-angle of R_start^-1 R_end), R_start [9] row-major,
+ * t_start [3], t_end [3], the top three rows of T_target^-1 [12]; all must be finite (LNR_ERR_INVALID_ARG otherwise). */
+int lnr_motion_compensate(float* ray_directions, float* distances, const void* timestamps, int32_t timestamps_fp64, int64_t n_points,
+                          double t0, double denom, const double* consts /*host*/, void* stream);
+
+/* Tracker.compute_sky_rays (tracker.py:257-297).  Per direction, in fp32: theta = round(rad2deg(atan2(y, x))) and
+ * phi = round(rad2deg(atan2(sqrt(x x + y y), z))) (round half to even).  The occupancy image has phi_max - phi_min + 1 rows and 360
+ * columns, a point sets pixel (phi - phi_min, theta - theta_min) with column 360 folded to 0; a 3x3 dilation and a 3x3 erosion follow,
+ * both ignoring out-of-image neighbours (kornia's geodesic border) and without azimuth wrap; the top three rows are set.  Every zero
+ * pixel (r, c), in row-major order, gives the unit vector (sin p cos t, sin p sin t, cos p) of p = deg2rad(r + phi_min),
+ * t = deg2rad(c + theta_min); it is rotated by rotation (device fp32 [9], row-major) and kept when
+ * 90 - rad2deg(atan2(sqrt(xw xw + yw yw), zw)) > 10.  sky fp32 [3, sky_stride] (sky_stride >= LNR_SKY_MAX_RAYS) receives the kept
+ * vectors in that order in its first m columns.  workspace: lnr_sky_rays_workspace() bytes.  info_dev int32 [8], written by the call:
+ * {status, m, zero pixels, rows, phi_min, theta_min, non-finite directions, 0}; status bit 1: a non-finite direction (it sets no
+ * pixel).  One host read of info_dev gives m. */
+size_t lnr_sky_rays_workspace(void);
+int lnr_sky_rays(const float* ray_directions, int64_t n_points, const float* rotation, void* workspace, size_t workspace_bytes,
+                 float* sky, int64_t sky_stride, int32_t* info_dev, void* stream);
+
 /* ---- loss ------------------------------------------------------------------------------------------ */
 /* get_weights_gt (losses.py:29-51); eps_ray [n] per-ray or NULL -> eps_scalar. */
 int lnr_weights_gt(const float* s /*[n,S] metres*/, const float* g /*[n] metres*/, const float* eps_ray,

@@ -1,5 +1,7 @@
-"""Frame: lidar points + poses for one instant (subset of src/common/frame.py:22-156)."""
+"""Frame: lidar points + poses for one instant (src/common/frame.py:22-156 without the image members' own classes)."""
 from typing import Union
+
+import torch
 
 from .pose import Pose
 from .sensors import LidarScan
@@ -21,8 +23,71 @@ class Frame:
                 pose.to(device)
         return self
 
+    def clone(self) -> "Frame":
+        """An independent copy: image, scan, calibration and both poses are cloned where present.  The id is the tracker's to give
+        and is not carried over."""
+        dup = lambda member: None if member is None else member.clone()
+        twin = Frame(dup(self.image), dup(self.lidar_points), dup(self._lidar_to_camera))
+        twin._lidar_pose, twin._gt_lidar_pose = dup(self._lidar_pose), dup(self._gt_lidar_pose)
+        return twin
+
+    def detach(self) -> "Frame":
+        self._lidar_pose.detach()
+        return self
+
+    def __repr__(self):
+        scan = self.lidar_points
+        span = f"{float(scan.get_start_time()):.6f} .. {float(scan.get_end_time()):.6f} s" if len(scan) else "empty"
+        return f"Frame(id={self._id}, {len(scan)} points, {span})"
+
     def get_time(self):
         return self.lidar_points.get_start_time()
+
+    def get_middle_time(self):
+        return self.lidar_points.get_start_time() / 2. + self.lidar_points.get_end_time() / 2.
+
+    def get_scan_duration(self) -> float:
+        return (self.lidar_points.timestamps[-1] - self.lidar_points.timestamps[0]).item()
+
+    def cloud_window(self, scan_duration: float = None, target_points: int = None):
+        """(start, stop, step) of build_point_cloud's slice (frame.py:108-134).  The reference's expressions are applied to the
+        timestamps where they live and kept as tensors until the pair of indices is read: one device -> host read.  A Python
+        scalar meets an fp32 tensor as torch casts it (to the tensor's type), so time_per_scan / 2, which the reference holds as a
+        Python float, is rounded to the timestamps' type before the compares and the sum."""
+        ts = self.lidar_points.timestamps
+        n = len(ts)
+        if n == 0:
+            raise ValueError("build_point_cloud: the scan is empty")
+        start, stop = 0, n
+        if scan_duration is not None:
+            first, last = ts[0], ts[-1]
+            half = ((last - first).double() * float(scan_duration) / 2).to(ts.dtype)      # time_per_scan / 2
+            middle_time = (first + last) / 2
+            rel = ts - middle_time
+            start_index = torch.argmax((rel >= -half).float())
+            final_index = torch.where(last < middle_time + half, torch.full_like(start_index, n), torch.argmax((rel >= half).float()))
+            whole = torch.stack((torch.zeros_like(start_index), torch.full_like(start_index, n)))
+            pair = torch.where(last - first > 1e-3, torch.stack((start_index, final_index)), whole)
+            start, stop = (int(v) for v in pair.cpu())
+        step = 1 if target_points is None else (stop - start) // int(target_points)
+        if step == 0:
+            step = 1
+        return start, stop, step
+
+    def build_point_cloud(self, scan_duration: float = None, target_points: int = None):
+        """The frame's cloud for ICP (frame.py:104-145) as a loner_amd.analysis.lidar_map.PointCloud on the scan's device: the middle
+        scan_duration share of the scan (all of it when None or when the scan is shorter than 1e-3 s), thinned uniformly to about
+        target_points.  The points are the reference's array bit for bit (ops.frame_cloud)."""
+        from .. import ops
+        from ..analysis.lidar_map import PointCloud
+        scan = self.lidar_points
+        if len(scan) == 0:
+            raise ValueError("build_point_cloud: the scan is empty")
+        ops.require_device(scan.ray_directions, scan.distances, scan.timestamps)
+        start, stop, step = self.cloud_window(scan_duration, target_points)
+        if step < 1 or stop < start:
+            raise ValueError(f"build_point_cloud: window [{start}, {stop}) with step {step}: the timestamps must be sorted")
+        return PointCloud(ops.frame_cloud(scan.ray_directions, scan.distances, start, stop, step))
 
     def get_lidar_pose(self) -> Pose:
         return self._lidar_pose

@@ -44,6 +44,21 @@ class Pose:
             mat = _as_f32(transformation_matrix)
         self._mat = mat if free else mat.detach()
 
+    @staticmethod
+    def from_settings(pose_dict: Optional[dict], fixed: bool = True) -> "Pose":
+        """A Pose from a calibration entry {"xyz": [3], "orientation": quaternion [w, x, y, z]} (src/common/pose.py:85-91); None
+        gives the identity (a lidar-only configuration has no lidar_to_camera entry).  The quaternion -> axis-angle map is
+        pytorch3d's published one: angle = 2 atan2(|v|, w), with the small-angle series of sin(angle / 2) / angle."""
+        if pose_dict is None:
+            return Pose(fixed=fixed)
+        xyz = torch.Tensor(pose_dict["xyz"])
+        quat = torch.Tensor(pose_dict["orientation"])
+        norms = torch.linalg.vector_norm(quat[1:])
+        angle = 2 * torch.atan2(norms, quat[0])
+        small = angle.abs() < 1e-6
+        k = torch.where(small, 0.5 - angle * angle / 48, torch.sin(angle / 2) / torch.where(small, torch.ones_like(angle), angle))
+        return Pose(pose_tensor=torch.cat((xyz, quat[1:] / k)), fixed=fixed)
+
     # ---- flags / placement ---------------------------------------------------------------------
     def set_fixed(self, fixed: bool = True) -> None:
         self.get_pose_tensor().requires_grad_(not fixed)

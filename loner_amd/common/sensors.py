@@ -1,5 +1,5 @@
-"""LidarScan: the keyframe point buffer (SoA), mirroring src/common/sensors.py:57-167."""
-from typing import Union
+"""LidarScan: the keyframe point buffer (SoA), mirroring src/common/sensors.py:57-232."""
+from typing import Tuple, Union
 
 import torch
 
@@ -23,6 +23,75 @@ class LidarScan:
 
     def get_end_time(self) -> torch.Tensor:
         return self.timestamps[-1]
+
+    def clear(self) -> "LidarScan":
+        """Empties the scan.  A scan that carried sky rays keeps an (empty) sky tensor; one without stays without."""
+        self.ray_directions, self.distances, self.timestamps = (torch.Tensor() for _ in range(3))
+        self.sky_rays = None if self.sky_rays is None else torch.Tensor()
+        return self
+
+    def remove_points(self, num_points: int) -> "LidarScan":
+        """Drops the num_points oldest points (the scan is time-ordered); sky rays are not points and stay."""
+        tail = slice(num_points, None)
+        self.ray_directions, self.distances, self.timestamps = self.ray_directions[..., tail], self.distances[tail], self.timestamps[tail]
+        return self
+
+    @staticmethod
+    def _appended(held, more):
+        """`more` behind `held` along the point axis; whatever is empty or absent is left out"""
+        return more if held is None or held.numel() == 0 else torch.cat((held, more), dim=-1)
+
+    def add_points(self, ray_directions: torch.Tensor, distances: torch.Tensor, timestamps: torch.Tensor,
+                   sky_rays: torch.Tensor = None) -> "LidarScan":
+        """Appends points (and sky rays, when given) behind the ones held."""
+        self.ray_directions = self._appended(self.ray_directions, ray_directions)
+        self.distances = self._appended(self.distances, distances)
+        self.timestamps = self._appended(self.timestamps, timestamps)
+        if sky_rays is not None:
+            self.sky_rays = self._appended(self.sky_rays, sky_rays)
+        return self
+
+    def merge(self, other: "LidarScan") -> "LidarScan":
+        return self.add_points(other.ray_directions, other.distances, other.timestamps, other.sky_rays)
+
+    def motion_compensate(self, poses: Tuple["Pose", "Pose"], timestamps: Tuple[float, float], target_frame: "Pose",
+                          use_gpu: bool = False) -> None:
+        """Moves every point from the pose interpolated (or extrapolated) at its own timestamp between `poses`, whose times are
+        `timestamps`, into target_frame (sensors.py:176-232), in place on the device the scan lives on (ops.motion_compensate;
+        use_gpu is accepted and ignored).  The per-call constants - the relative axis-angle, the start rotation, both translations
+        and the inverse target - are formed on the host in fp64 from the poses' fp32 matrices; those of them, and of the two pose
+        times, that live on a device come over in one read."""
+        from .. import ops
+        from . import pose_utils as PU
+        if len(self) == 0:
+            raise ValueError("motion_compensate: the scan is empty")
+        ops.require_device(self.ray_directions, self.distances, self.timestamps)
+        dev = self.timestamps.device
+        start_pose, end_pose = poses
+        start_ts, end_ts = timestamps
+        denom = end_ts - start_ts                                  # the caller's own subtraction, in the times' own type
+        parts = [p.get_transformation_matrix().detach().double().reshape(16) for p in (start_pose, end_pose, target_frame)]
+        parts += [t.detach().double().reshape(1) if torch.is_tensor(t) else torch.tensor([float(t)], dtype=torch.float64)
+                  for t in (start_ts, denom)]
+        # what is on the host already stays there; what lives on a device comes over in one read
+        remote = [k for k, t in enumerate(parts) if t.device.type != "cpu"]
+        if remote:
+            fetched = torch.cat([parts[k].to(dev) for k in remote]).cpu()
+            for k, piece in zip(remote, fetched.split([parts[k].numel() for k in remote])):
+                parts[k] = piece
+        host = torch.cat(parts)
+        if not bool(torch.isfinite(host).all()):
+            raise ValueError("motion_compensate: a pose or a pose time is not finite")
+        T_start, T_end, T_target = (host[16 * k:16 * k + 16].reshape(4, 4) for k in range(3))
+        relative_rotation = torch.linalg.inv(T_start[:3, :3]) @ T_end[:3, :3]
+        axis_angle = PU.matrix_to_axis_angle(relative_rotation)
+        T_inv = torch.linalg.inv(T_target)
+        consts = torch.cat([axis_angle, T_start[:3, :3].reshape(9), T_start[:3, 3], T_end[:3, 3], T_inv[:3].reshape(12)])
+        if not self.ray_directions.is_contiguous():
+            self.ray_directions = self.ray_directions.contiguous()
+        if not self.distances.is_contiguous():
+            self.distances = self.distances.contiguous()
+        ops.motion_compensate(self.ray_directions, self.distances, self.timestamps, float(host[48]), float(host[49]), consts.tolist())
 
     def clone(self) -> "LidarScan":
         return LidarScan(self.ray_directions.clone(), self.distances.clone(), self.timestamps.clone(),

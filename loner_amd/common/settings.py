@@ -109,3 +109,31 @@ def default_optimizer_settings(ray_range=(1, 50), log_directory="/tmp/loner_amd_
         "debug": {k: False for k in DEBUG_FLAGS},
         "log_directory": log_directory,
     })
+
+
+def default_tracker_settings(log_directory="/tmp/loner_amd_logs") -> Settings:
+    """= settings.tracker of cfg/defaults.yaml:135-164 (values only) with the debug flags and log_directory the reference's top level
+    adds before it hands the block to Tracker."""
+    return Settings({
+        "synchronization": {"enabled": True, "min_buffer_size": 2, "max_time_delta": 3},
+        "frame_synthesis": {"strategy": None, "sky_removal": None, "frame_decimation_rate_hz": 5, "frame_match_tolerance": 0.01,
+                            "frame_delta_t_sec_tolerance": 0.02, "decimate_on_load": True},
+        "icp": {
+            "scan_duration": 0.9,
+            "schedule": [
+                {"threshold": 1.5, "max_iterations": 10, "relative_fitness": 1.e-8, "relative_rmse": 1.e-8},
+                {"threshold": 0.125, "max_iterations": 10, "relative_fitness": 1.e-8, "relative_rmse": 1.e-8}],
+            "downsample": {"type": "UNIFORM", "target_uniform_point_count": 5000, "voxel_downsample_size": 0.1},
+        },
+        "motion_compensation": {"enabled": True, "use_gpu": True},
+        "compute_sky_rays": False,
+        "debug": {k: False for k in DEBUG_FLAGS},
+        "log_directory": log_directory,
+    })
+
+
+def default_tracking_settings(log_directory="/tmp/loner_amd_logs") -> Settings:
+    """The top-level keys Tracker reads (tracker.py:43-78): tracker, calibration.lidar_to_camera and system.lidar_only, for a
+    lidar-only run."""
+    return Settings({"tracker": default_tracker_settings(log_directory), "calibration": {"lidar_to_camera": None},
+                     "system": {"lidar_only": True}})

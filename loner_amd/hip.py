@@ -21,6 +21,8 @@ LOSS_RAYS_PER_BLOCK = 4      # LNR_LOSS_RAYS_PER_BLOCK
 FRONT_HEADER = 4             # LNR_FRONT_HEADER
 KNN_MAX = 32                 # LNR_KNN_MAX
 ICP_RESULT = 64              # LNR_ICP_RESULT
+MOCOMP_CONSTS = 30           # LNR_MOCOMP_CONSTS
+SKY_MAX_RAYS = 65160         # LNR_SKY_MAX_RAYS
 
 ENCODINGS = {"HashGrid": 0, "Grid": 0, "Frequency": 1}
 ACTIVATIONS = {"None": 0, "ReLU": 1, "Sine": 2, "LeakyReLU": 3, "Exponential": 4, "Sigmoid": 5,
@@ -126,6 +128,10 @@ _SIGNATURES = {
     "lnr_icp_workspace": (C.c_size_t, [C.c_int64]),
     "lnr_icp_point_to_plane": (C.c_int, [P, C.c_int64, P, P, C.c_int64, C.c_double, C.POINTER(C.c_double), C.c_double, C.c_double,
                                          C.c_int32, P, C.c_size_t, P, P, P]),
+    "lnr_frame_cloud": (C.c_int, [P, P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, P, P]),
+    "lnr_motion_compensate": (C.c_int, [P, P, P, C.c_int32, C.c_int64, C.c_double, C.c_double, C.POINTER(C.c_double), P]),
+    "lnr_sky_rays_workspace": (C.c_size_t, []),
+    "lnr_sky_rays": (C.c_int, [P, C.c_int64, P, P, C.c_size_t, P, C.c_int64, P, P]),
     "lnr_points_grad_to_rays": (C.c_int, [P, P, C.c_int32, P, C.c_int32, P, P]),
     "lnr_weights_gt": (C.c_int, [P, P, P, C.c_float, C.c_int32, C.c_int32, C.c_int32, P, P]),
     "lnr_logits_grad": (C.c_int, [P, P, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, P, P]),

@@ -717,6 +717,80 @@ def icp_point_to_plane(grid, target_normals, source, max_distance, init=None, re
             "x": res[46:52].copy(), "system_correspondences": info[5]}
 
 
+# ---------------------------------------------------------------- tracking
+def _scan_soa(directions, distances, what):
+    require_device(directions, distances)
+    if directions.dim() != 2 or directions.shape[0] != 3 or distances.dim() != 1 or distances.shape[0] != directions.shape[1]:
+        raise ValueError(f"{what}: ray_directions [3,n] and distances [n], got {tuple(directions.shape)} and {tuple(distances.shape)}")
+    if directions.dtype != torch.float32 or distances.dtype != torch.float32:
+        raise ValueError(f"{what}: ray_directions and distances must be float32")
+
+
+def frame_cloud(directions, distances, start, stop, step):
+    """Frame.build_point_cloud's array (include/loner_hip.h: lnr_frame_cloud): the fp32 products dir * dist of scan entries
+    start, start + step, ... below stop, widened -> points [m,3] fp64 on the scan's device."""
+    _scan_soa(directions, distances, "frame_cloud")
+    n = distances.shape[0]
+    start, stop, step = int(start), int(stop), int(step)
+    if not (0 <= start and stop <= n and step >= 1):
+        raise ValueError(f"frame_cloud: bad window [{start}, {stop}) step {step} of {n} points")
+    m = len(range(start, stop, step))
+    points = torch.empty(m, 3, device=distances.device, dtype=torch.float64)
+    check(load().lnr_frame_cloud(_ptr(_f32c(directions)), _ptr(_f32c(distances)), n, start, stop, step, _ptr(points), _stream()),
+          "lnr_frame_cloud")
+    return points
+
+
+def motion_compensate(directions, distances, timestamps, t0, denom, consts):
+    """LidarScan.motion_compensate in place on directions [3,n] and distances [n] (include/loner_hip.h: lnr_motion_compensate).
+    timestamps [n] fp32 or fp64; t0 and denom = t1 - t0 as floats; consts: the LNR_MOCOMP_CONSTS fp64 per-call constants."""
+    _scan_soa(directions, distances, "motion_compensate")
+    require_device(timestamps)
+    n = distances.shape[0]
+    if timestamps.shape != (n,) or timestamps.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"motion_compensate: timestamps [n] float32 or float64, got {tuple(timestamps.shape)} {timestamps.dtype}")
+    if not (directions.is_contiguous() and distances.is_contiguous()):
+        raise ValueError("motion_compensate: works in place, ray_directions and distances must be contiguous")
+    consts = [float(x) for x in consts]
+    if len(consts) != hip.MOCOMP_CONSTS:
+        raise ValueError(f"motion_compensate: {hip.MOCOMP_CONSTS} constants, got {len(consts)}")
+    if not all(math.isfinite(x) for x in consts + [float(t0), float(denom)]):
+        raise ValueError("motion_compensate: a pose or a pose time is not finite")
+    c = (C.c_double * hip.MOCOMP_CONSTS)(*consts)
+    check(load().lnr_motion_compensate(_ptr(directions), _ptr(distances), _ptr(timestamps.contiguous()),
+                                       int(timestamps.dtype == torch.float64), n, float(t0), float(denom), c, _stream()),
+          "lnr_motion_compensate")
+
+
+_sky_ws = {}
+
+
+def sky_rays(directions, rotation):
+    """Tracker.compute_sky_rays (include/loner_hip.h: lnr_sky_rays): sensor-frame directions [3,n] fp32 and the pose's rotation [3,3]
+    -> the sky directions [3,m] fp32 (rotated, in row-major pixel order).  One device -> host read (m)."""
+    require_device(directions, rotation)
+    if directions.dim() != 2 or directions.shape[0] != 3 or directions.shape[1] == 0 or directions.dtype != torch.float32:
+        raise ValueError(f"sky_rays: ray_directions float32 [3,n] with n >= 1, got {tuple(directions.shape)} {directions.dtype}")
+    dev = directions.device
+    rot = rotation.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if rot.shape != (3, 3):
+        raise ValueError(f"sky_rays: rotation [3,3], got {tuple(rot.shape)}")
+    lib = load()
+    need = int(lib.lnr_sky_rays_workspace())
+    held = _sky_ws.get(str(dev))                # the workspace and the full-size output are kept per device; the result is copied out
+    if held is None:
+        held = _sky_ws[str(dev)] = (torch.empty(need, device=dev, dtype=torch.uint8),
+                                    torch.empty(3, hip.SKY_MAX_RAYS, device=dev, dtype=torch.float32))
+    ws, sky = held
+    info = torch.empty(8, device=dev, dtype=torch.int32)
+    check(lib.lnr_sky_rays(_ptr(_f32c(directions)), directions.shape[1], _ptr(rot), _ptr(ws), need, _ptr(sky), hip.SKY_MAX_RAYS,
+                           _ptr(info), _stream()), "lnr_sky_rays")
+    info = [int(x) for x in info.cpu()]
+    if info[0]:
+        raise RuntimeError(f"sky_rays: {info[6]} ray directions are not finite")
+    return sky[:, :info[1]].contiguous()
+
+
 def render_backward(sigma, z, rays, g_depth, g_weights, g_opacity, g_variance, noise=None, noise_std=0.0, seed=0,
                     n_rays_dev=None):
     require_device(sigma, z, rays)
