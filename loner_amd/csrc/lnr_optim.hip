@@ -66,10 +66,14 @@ extern "C" int lnr_adam_step(float* params, float* grads, float* exp_avg, float*
 }
 
 // ------------------------------------------------------------------------------------------------
-// occupancy grid step.  A wave walks 64 consecutive samples of a ray; at V=100 about 20 consecutive
+// occupancy grid step.  A wave walks 64 consecutive samples of ONE ray (a ray is cut into ceil(S/64) chunks, the last one
+// padded with idle lanes); at V=100 about 20 consecutive
 // samples fall into the same voxel, and a float atomic costs one L2 transaction per touched 64-byte line
 // per instruction (profiles/r01_scatter_transactions.txt), so each of the 8 corner contributions is first
 // summed over runs of equal voxel index with segmented shuffles and only run heads issue atomics.
+// The chunks are aligned to the ray so that the runs, and with them the rounding of every run's float sum, depend on the
+// sample's place in its ray alone: with the fixed-point accumulator a voxel's total is then independent of the order of the
+// rays for every S (chunks of the flat [n*S] sample list cut the rays at places that moved with the ray's row when S % 64 != 0).
 // The pseudo-gradient is 0 more than `margin` behind the surface, so most runs are skipped altogether.
 // ------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256)
@@ -77,17 +81,16 @@ occ_grid_step_kernel(float* __restrict__ grid, int V, const float* __restrict__ 
                      const float* __restrict__ depth_gt, int n_rays, const int32_t* __restrict__ n_rays_dev, int S, float scale,
                      float lr, float margin, float l_free, float l_occ, long long* __restrict__ grad_acc) {
     const int lane = threadIdx.x & 63;
-    const int64_t total = (int64_t)lnr_live_rays(n_rays, n_rays_dev) * S;
-    const int64_t n_chunks = (total + 63) / 64;
+    const int chunks_per_ray = (S + 63) >> 6;
+    const int64_t n_chunks = (int64_t)lnr_live_rays(n_rays, n_rays_dev) * chunks_per_ray;
     const int64_t wave_id = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
     const float fV = (float)V;
     for (int64_t chunk = wave_id; chunk < n_chunks; chunk += n_waves) {
-        const int64_t m = chunk * 64 + lane;
-        const bool live = m < total;
-        const int64_t mm = live ? m : total - 1;
-        const int ray = (int)(mm / S);
-        const float zv = z[mm];
+        const int ray = (int)(chunk / chunks_per_ray);
+        const int s = (int)(chunk - (int64_t)ray * chunks_per_ray) * 64 + lane;
+        const bool live = s < S;
+        const float zv = z[(int64_t)ray * S + (live ? s : S - 1)];
         const float x = zv * scale - depth_gt[ray] * scale;
         float gval = 0.0f;
         if (-x - margin > 0.0f) gval = l_free;
@@ -99,10 +102,10 @@ occ_grid_step_kernel(float* __restrict__ grid, int V, const float* __restrict__ 
         const float ix = ((px + 1.0f) * fV - 1.0f) * 0.5f, iy = ((py + 1.0f) * fV - 1.0f) * 0.5f, iz = ((pz + 1.0f) * fV - 1.0f) * 0.5f;
         const float x0 = floorf(ix), y0 = floorf(iy), z0 = floorf(iz);
         const float fx = ix - x0, fy = iy - y0, fz = iz - z0;
-        // run structure: consecutive lanes with the same base voxel AND the same ray
+        // run structure: consecutive lanes with the same base voxel (the whole wave is on one ray)
         const int cell = ((int)z0 * 1024 + (int)y0) * 1024 + (int)x0;
-        const int prev_cell = __shfl_up(cell, 1, 64), prev_ray = __shfl_up(ray, 1, 64);
-        const bool head = (lane == 0) || (prev_cell != cell) || (prev_ray != ray);
+        const int prev_cell = __shfl_up(cell, 1, 64);
+        const bool head = (lane == 0) || (prev_cell != cell);
         int seg = head ? 1 : 0;
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(seg, o, 64); if (lane >= o) seg += t; }
@@ -145,9 +148,10 @@ extern "C" int lnr_occ_grid_step(float* grid, int32_t V, const float* rays, cons
                                  const int32_t* n_rays_dev, int32_t n_samples, float scale, float lr, float margin, float l_free,
                                  float l_occ, int64_t* grad_acc, void* stream) {
     LNR_REQUIRE(grid && rays && z && depth_gt && V > 0 && n_rays >= 0 && n_samples > 0, "lnr_occ_grid_step: bad argument");
-    const int64_t total = (int64_t)n_rays * n_samples;
-    if (total == 0) return LNR_OK;
-    int64_t blocks = (total + 255) / 256;
+    // the run key of occ_grid_step_kernel packs the base voxel into 10 bits per axis
+    LNR_REQUIRE(V <= 1023, "lnr_occ_grid_step: a grid of %d voxels per axis is not supported (V <= 1023)", V);
+    if (n_rays == 0) return LNR_OK;
+    int64_t blocks = ((int64_t)n_rays * ((n_samples + 63) / 64) + 3) / 4;          // one wave per 64-sample chunk of a ray
     if (blocks > 256 * 8) blocks = 256 * 8;
     hipLaunchKernelGGL(occ_grid_step_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, grid, V, rays, z, depth_gt, n_rays,
                        n_rays_dev, n_samples, scale, lr, margin, l_free, l_occ, reinterpret_cast<long long*>(grad_acc));

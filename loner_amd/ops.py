@@ -242,6 +242,8 @@ def pose_forward(pose6):
     require_device(pose6)
     p = _f32c(pose6.detach()).reshape(-1, 6)
     T = torch.empty(p.shape[0], 12, device=p.device, dtype=torch.float32)
+    if p.shape[0] == 0:                   # (an empty tensor has no address to hand over)
+        return T
     check(load().lnr_pose_forward(_ptr(p), p.shape[0], _ptr(T), _stream()), "lnr_pose_forward")
     return T
 
@@ -253,6 +255,8 @@ def pose_backward(pose6, d_transforms, mask=None, out=None, accumulate=False, po
     if out is None:
         out = torch.empty_like(p)
         accumulate = False
+    if p.shape[0] == 0:
+        return out
     check(load().lnr_pose_backward(_ptr(p), _ptr(_f32c(d_transforms)), _ptr(mask), p.shape[0], _ptr(out), int(accumulate),
                                    _ptr(poison), int(poison_tag), _stream()), "lnr_pose_backward")
     return out
