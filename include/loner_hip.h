@@ -495,10 +495,6 @@ int lnr_nn_grid_build(const double* targets, int64_t n_targets, double cell_edge
 int lnr_nn_distance(const void* grid, int64_t n_targets, const double* queries, int64_t n_queries, double* distance,
                     double* sq_distance, void* workspace, size_t workspace_bytes, int64_t* counters_dev, void* stream);
 
-/* The device-matrix form of lnr_cloud_append_transformed: transform_dev [12] fp64 in device memory (the top three rows of T, row-major),
- * the same rounding.  ICP moves its working copy of the source with it, reading each round's update where the device computed it. */
-int lnr_cloud_append_transformed_dev(const double* src, int64_t n_points, const double* transform_dev, double* dst, void* stream);
-
 /* ---- normals and point-to-plane ICP (analysis/evaluate_lidar_map.py:23-53) ----------------------------------------------------- */
 #define LNR_KNN_MAX 32          /* the largest knn of lnr_cloud_normals */
 #define LNR_ICP_RESULT 64       /* fp64 entries of lnr_icp_point_to_plane's result */

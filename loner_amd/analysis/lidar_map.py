@@ -95,7 +95,7 @@ class PointCloud:
         (with the same rounding, a zero translation) and covariances become R C R^T."""
         ops.cloud_transform(self.points, T, out=self.points)
         if self.normals is not None or self.covariances is not None:
-            T = np.asarray(T.detach().cpu().numpy() if torch.is_tensor(T) else T, dtype=np.float64)
+            T = ops.affine_f64(T, "transform: T must be a 4x4 affine matrix with bottom row [0, 0, 0, 1]")
             R = np.eye(4)
             R[:3, :3] = T[:3, :3]
             if self.normals is not None:

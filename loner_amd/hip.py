@@ -122,7 +122,6 @@ _SIGNATURES = {
     "lnr_nn_grid_bytes": (C.c_size_t, [C.c_int64]),
     "lnr_nn_grid_build": (C.c_int, [P, C.c_int64, C.c_double, P, C.c_size_t, P, C.c_size_t, P, P]),
     "lnr_nn_distance": (C.c_int, [P, C.c_int64, P, C.c_int64, P, P, P, C.c_size_t, P, P]),
-    "lnr_cloud_append_transformed_dev": (C.c_int, [P, C.c_int64, P, P, P]),
     "lnr_cloud_normals": (C.c_int, [P, C.c_int64, C.c_int32, P, P, P, C.c_size_t, P, P]),
     "lnr_icp_correspondences": (C.c_int, [P, C.c_int64, P, C.c_int64, C.c_double, P, P, P, P]),
     "lnr_icp_workspace": (C.c_size_t, [C.c_int64]),

@@ -578,14 +578,28 @@ def voxel_down_sample(points, voxel_size, count=None):
     return out[:int(info[1])]
 
 
+def affine_f64(T, what, finite=False):
+    """T (a tensor or an array of any float dtype) as a numpy fp64 4x4 whose bottom row is [0, 0, 0, 1] (and finite, when asked);
+    ValueError(f"{what}, got ...") otherwise."""
+    import numpy as np
+    T = np.asarray(T.detach().cpu().numpy() if torch.is_tensor(T) else T, dtype=np.float64)
+    if T.shape != (4, 4) or not np.array_equal(T[3], [0.0, 0.0, 0.0, 1.0]) or (finite and not np.isfinite(T).all()):
+        raise ValueError(f"{what}, got {T.tolist()}")
+    return T
+
+
+def _read_counters(device, call, what):
+    """The int64 [4] counters of a grid query: allocated on `device`, filled by call(pointer), read once -> a host tensor."""
+    counters = torch.empty(4, device=device, dtype=torch.int64)
+    check(call(_ptr(counters)), what)
+    return counters.cpu()
+
+
 def cloud_transform(points, T, out=None):
     """out[i] = T[:3,:3] p_i + T[:3,3] in fp64 without fma (include/loner_hip.h: lnr_cloud_append_transformed).  T: a 4x4 affine
     (tensor or array, any float dtype, widened to fp64); out (optional, [n,3] fp64, may be `points` itself or a slice of a larger
     cloud) receives the result."""
-    import numpy as np
-    T = np.asarray(T.detach().cpu().numpy() if torch.is_tensor(T) else T, dtype=np.float64)
-    if T.shape != (4, 4) or not np.array_equal(T[3], [0.0, 0.0, 0.0, 1.0]):
-        raise ValueError(f"transform: T must be a 4x4 affine matrix with bottom row [0, 0, 0, 1], got {T.tolist()}")
+    T = affine_f64(T, "transform: T must be a 4x4 affine matrix with bottom row [0, 0, 0, 1]")
     pts = _f64_points(points, "transform")
     out = torch.empty_like(pts) if out is None else out
     assert out.dtype == torch.float64 and out.is_contiguous() and out.shape == pts.shape
@@ -629,10 +643,8 @@ class NNGrid:
         dist = torch.empty(m, device=dev, dtype=torch.float64)
         d2 = torch.empty(m, device=dev, dtype=torch.float64) if want_sq else None
         ws, need = _cloud_workspace(m, dev)
-        counters = torch.empty(4, device=dev, dtype=torch.int64)
-        check(load().lnr_nn_distance(_ptr(self.buf), self.n, _ptr(q), m, _ptr(dist), _ptr(d2), _ptr(ws), need, _ptr(counters),
-                                     _stream()), "lnr_nn_distance")
-        c = counters.cpu()
+        c = _read_counters(dev, lambda counters: load().lnr_nn_distance(_ptr(self.buf), self.n, _ptr(q), m, _ptr(dist), _ptr(d2), _ptr(ws),
+                                                                        need, counters, _stream()), "lnr_nn_distance")
         if int(c[1]):
             raise RuntimeError(f"compute_point_cloud_distance: {int(c[1])} queries with non-finite coordinates")
         if stats is not None:
@@ -650,10 +662,8 @@ class NNGrid:
         normals = torch.empty(self.n, 3, device=dev, dtype=torch.float64)
         cov = torch.empty(self.n, 3, 3, device=dev, dtype=torch.float64) if want_covariances else None
         ws, need = _cloud_workspace(self.n, dev)
-        counters = torch.empty(4, device=dev, dtype=torch.int64)
-        check(load().lnr_cloud_normals(_ptr(self.buf), self.n, knn, _ptr(normals), _ptr(cov), _ptr(ws), need, _ptr(counters), _stream()),
-              "lnr_cloud_normals")
-        c = counters.cpu()
+        c = _read_counters(dev, lambda counters: load().lnr_cloud_normals(_ptr(self.buf), self.n, knn, _ptr(normals), _ptr(cov), _ptr(ws),
+                                                                          need, counters, _stream()), "lnr_cloud_normals")
         if int(c[1]):
             raise RuntimeError("normals: the grid is unusable (non-finite targets)")
         if stats is not None:
@@ -696,9 +706,7 @@ def icp_point_to_plane(grid, target_normals, source, max_distance, init=None, re
     r = float(max_distance)
     if not (math.isfinite(r) and r > 0):
         raise ValueError(f"icp_point_to_plane: max_correspondence_distance must be finite and > 0, got {max_distance!r}")
-    T0 = np.eye(4) if init is None else np.asarray(init.detach().cpu().numpy() if torch.is_tensor(init) else init, dtype=np.float64)
-    if T0.shape != (4, 4) or not np.array_equal(T0[3], [0.0, 0.0, 0.0, 1.0]) or not np.isfinite(T0).all():
-        raise ValueError(f"icp_point_to_plane: init must be a finite 4x4 affine matrix, got {T0.tolist()}")
+    T0 = affine_f64(np.eye(4) if init is None else init, "icp_point_to_plane: init must be a finite 4x4 affine matrix", finite=True)
     dev = src.device
     lib = load()
     need = int(lib.lnr_icp_workspace(src.shape[0]))

@@ -52,6 +52,19 @@ def test_covariances_are_bit_identical_to_the_restatement(name):
     print(f"{name}: {len(p)} points, edge {g.edge:.4g}, {stats}")
 
 
+def test_every_point_takes_the_exact_knn_pass():
+    """A cell edge of a tenth of the lattice's spacing: five shells reach at most 0.25 from a query on every axis, so a point finds only
+    itself while unvisited cells remain, and all 324 points go through knn_brute."""
+    p = _clouds()["lattice"]
+    n0, _, _, _ = _gpu_normals(p)
+    n1, C1, g, stats = _gpu_normals(p, cell_edge=0.05)
+    print(f"lattice: {len(p)} points, edge {g.edge:.4g}, dims {g.dims}, {stats}")
+    assert stats["fallback"] == len(p)
+    want = IR.covariance(p, IR.knn(p, 30)[0])
+    assert _same_bits(C1, want), f"{int((C1 != want).any((1, 2)).sum())} of {len(p)} covariances differ"
+    assert _same_bits(n1, n0)
+
+
 @pytest.mark.parametrize("name", list(_clouds()))
 def test_normals_match_the_eigenvector(name):
     p = _clouds()[name]
