@@ -541,6 +541,68 @@ int lnr_icp_point_to_plane(const void* grid, int64_t n_targets, const double* ta
                            double max_distance, const double* init, double relative_fitness, double relative_rmse, int32_t max_iteration,
                            void* workspace, size_t workspace_bytes, double* result_dev, int64_t* info_dev, void* stream);
 
+/* ---- mesh sampling, outlier filter, trajectory transform (analysis/compute_metrics/maps/mesh_to_pcd.py; ------------------------
+ *      examples/fusion_portable/create_lidar_map.py, mask_gt_with_trajectory.py) ------------------------------------------------- */
+/* open3d's TriangleMesh::SamplePointsUniformly (mesh_to_pcd.py:22) with a defined order and counter-based draws.  vertices fp64
+ * [n_vertices,3], triangles int32 [n_triangles,3], n_triangles and n_points within the cloud limit.
+ * Area: with u = v0 - v1 and w = v0 - v2, c = (u_y w_z - u_z w_y, u_z w_x - u_x w_z, u_x w_y - u_y w_x) and
+ * A_t = 0.5 * sqrt((c_x c_x + c_y c_y) + c_z c_z).
+ * Cumulative area C_t, a 64-ary tree of fp64 additions: prefix(a)[t] for t in chunk c = t / 64 is the left-to-right sum
+ * ((a[64c] + a[64c+1]) + ...) + a[t] for c = 0, and prefix(T)[c-1] + (that sum) otherwise, where T[c] is the left-to-right sum of the
+ * whole chunk c (the last chunk may be short) and prefix(T) is formed by the same rule; C = prefix(A), S = C_{F-1}.
+ * Ownership (open3d's stratified rule): n_t = min(n_points, max over u <= t of round((C_u / S) * (double) n_points)), round half away
+ * from zero; triangle t owns the points n_{t-1} <= i < n_t, n_{-1} = 0.  (The running max only matters where C steps down by an ulp
+ * between two chunks; n_{F-1} = n_points.)  A triangle of zero area owns nothing.
+ * Point i: (x, y, z, w) = philox4x32_10 with counter low 64 bits i, high 64 bits 0x4D45534800000000 ("MESH" in the top word; no
+ * other draw of the library has a non-zero top word), key seed; r1 = (double)(((uint64) x << 32 | y) >> 11) * 2^-53 and r2 likewise
+ * from z, w; s = sqrt(r1), a = 1 - s, b = s * (1 - r2), c = s * r2; p = (a v0 + b v1) + c v2 per axis.
+ * points [n_points,3] and triangle_index int32 [n_points] (nullable) depend on (mesh, n_points, seed) only.
+ * workspace: lnr_mesh_sample_workspace(n_triangles) bytes (0 = out of range).  info_dev int64 [8], written by the call: {status, points
+ * written, triangles with a non-finite vertex or an index out of range, S (fp64 bits), 0, 0, 0, 0}; status bit 1: a triangle uses a
+ * non-finite vertex, 2: a vertex index is outside [0, n_vertices), 4: S is not finite; with any bit set nothing is written.  S = 0 or
+ * n_triangles = 0 writes nothing and reports 0 points. */
+size_t lnr_mesh_sample_workspace(int64_t n_triangles);
+int lnr_mesh_sample_points(const double* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles, int64_t n_points,
+                           uint64_t seed, void* workspace, size_t workspace_bytes, double* points, int32_t* triangle_index,
+                           int64_t* info_dev, void* stream);
+
+/* The workspace of the three entries below: lnr_cloud_tools_workspace(n_points) bytes (about 4 n; 0 = n out of range). */
+size_t lnr_cloud_tools_workspace(int64_t n_points);
+
+/* The first half of open3d's PointCloud::RemoveStatisticalOutliers (create_lidar_map.py:134) over the points a grid was built from:
+ * the neighbours of point i are lnr_cloud_normals' (the m = min(nb_neighbors, n) smallest (d2, input index) pairs, i itself included,
+ * by the same shell walk and the same exact pass after 5 shells); mean_distance_i = (((sqrt(d2_0) + sqrt(d2_1)) + ...) in list order,
+ * starting from 0.0) / (double) m.  mean_distance [n] in input order; nb_neighbors in [1, LNR_KNN_MAX].  counters_dev int64 [4] as
+ * lnr_cloud_normals'. */
+int lnr_cloud_knn_mean_distance(const void* grid, int64_t n_points, int32_t nb_neighbors, double* mean_distance, void* workspace,
+                                size_t workspace_bytes, int64_t* counters_dev, void* stream);
+
+/* The second half: result_dev fp64 [4] = {mean, std, threshold, valid}.  valid = n_points when the grid is usable for them (else 0);
+ * mean = (sum of mean_distance_i over mean_distance_i > 0) / valid; std = sqrt((sum of (mean_distance_i - mean)^2 over the same i) /
+ * (valid - 1)); threshold = mean + std_ratio * std.  Either sum is taken in a fixed order: thread j of block b adds its terms i = 256 b
+ * + j, + 256 B, ... (B = min(ceil(n / 256), 2048) blocks) in turn, a block sums its threads by the xor butterfly of each wave and the
+ * four waves left to right, and one workgroup folds the B partials the same way.  A point is kept when mean_distance_i > 0 and
+ * mean_distance_i < threshold (the caller's compare).  valid = 1 gives 0 / 0: a NaN threshold keeps nothing, as open3d's does. */
+int lnr_cloud_outlier_threshold(const void* grid, const double* mean_distance, int64_t n_points, double std_ratio, void* workspace,
+                                size_t workspace_bytes, double* result_dev, void* stream);
+
+/* process_cloud of create_lidar_map.py (:77-111): every point of a scan moved by the trajectory's pose at the point's own time.
+ * points [n,3] (sensor frame) and timestamps [n] (absolute, fp64); the trajectory is n_poses >= 2 device arrays: traj_times [K]
+ * strictly increasing (the caller checks), traj_positions [K,3], traj_rotations [K,9] (row-major) and traj_rotvecs [K-1,3], the
+ * rotation vectors log(R_k^T R_{k+1}).  A point with a non-finite coordinate or time is dropped and counted; else it is dropped as
+ * below range unless sqrt((x x + y y) + z z) > min_range; else as outside the trajectory when tau < T_0 or tau > T_{K-1}.  Otherwise k is
+ * the last index with T_k <= tau, at most K - 2; alpha = (tau - T_k) / (T_{k+1} - T_k); trans_a = P_k,a + alpha * (P_{k+1},a - P_k,a);
+ * w = alpha * w_k per axis, theta = sqrt((w_x w_x + w_y w_y) + w_z w_z); R = R_k when theta < 1e-9, else with e = w / theta,
+ * s = sin(theta), v = 1 - cos(theta) the matrix E = I + s K + v K^2 as lnr_motion_compensate writes it (E_00 = 1 - v * (e_y e_y +
+ * e_z e_z), E_01 = (v * e_x) * e_y - s * e_z, ...) and R_ab = (R_k,a0 E_0b + R_k,a1 E_1b) + R_k,a2 E_2b; out_a = ((R_a0 x + R_a1 y)
+ * + R_a2 z) + trans_a.  scipy's Slerp and interp1d give the same pose up to rounding; the fp64 value above is the definition.
+ * out [n,3] receives the kept points in input order.  info_dev int64 [8], written by the call: {status, kept, below range, outside the
+ * trajectory, non-finite, 0, 0, 0}; status bit 1: a non-finite point or time.  One host read of info_dev gives the count. */
+int lnr_cloud_trajectory_transform(const double* points, const double* timestamps, int64_t n_points, const double* traj_times,
+                                   const double* traj_positions, const double* traj_rotations, const double* traj_rotvecs,
+                                   int64_t n_poses, double min_range, void* workspace, size_t workspace_bytes, double* out,
+                                   int64_t* info_dev, void* stream);
+
 /* ---- tracking (src/common/frame.py:104-145; src/common/sensors.py:176-232; src/tracking/tracker.py:257-297) ----------------- */
 #define LNR_MOCOMP_CONSTS 30      /* fp64 entries of lnr_motion_compensate's consts */
 #define LNR_SKY_MAX_RAYS 65160    /* 181 x 360: the row stride lnr_sky_rays' output needs */

@@ -79,6 +79,24 @@ class PointCloud:
         out.covariances = None if self.covariances is None else self.covariances[::k].contiguous()
         return out
 
+    def remove_statistical_outlier(self, nb_neighbors=20, std_ratio=1.5, cell_edge=None):
+        """open3d's remove_statistical_outlier -> (a new cloud of the kept points in input order, with their normals and covariances;
+        their indices, int64 on the device).  A point is kept when the mean distance to its nb_neighbors nearest points (itself
+        included) is > 0 and below mean + std_ratio * std over the cloud (include/loner_hip.h: lnr_cloud_knn_mean_distance,
+        lnr_cloud_outlier_threshold).  cell_edge: the search grid's (the result does not depend on it)."""
+        if nb_neighbors < 1 or not std_ratio > 0:
+            raise ValueError(f"remove_statistical_outlier: nb_neighbors >= 1 and std_ratio > 0, got {nb_neighbors!r} and {std_ratio!r}")
+        if len(self) == 0:
+            return PointCloud(self.points.clone()), torch.zeros(0, dtype=torch.int64, device=self.points.device)
+        grid = ops.NNGrid(self.points, cell_edge)
+        avg = grid.knn_mean_distance(nb_neighbors)
+        threshold = grid.outlier_threshold(avg, std_ratio)[2]
+        index = ((avg > 0) & (avg < threshold)).nonzero().squeeze(1)
+        out = PointCloud(self.points[index])
+        out.normals = None if self.normals is None else self.normals[index].contiguous()
+        out.covariances = None if self.covariances is None else self.covariances[index].contiguous()
+        return out, index
+
     def __len__(self):
         return int(self.points.shape[0])
 

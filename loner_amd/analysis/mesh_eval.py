@@ -1,0 +1,42 @@
+"""Scoring a mesh against a ground-truth cloud (the reference's analysis/compute_metrics/maps/mesh_to_pcd.py followed by
+evaluate_lidar_map.py::compare_point_clouds), on HIP and without open3d.
+
+mesh_to_point_cloud samples the mesh's surface uniformly (TriangleMesh.sample_points_uniformly: include/loner_hip.h,
+lnr_mesh_sample_points) and voxel-down-samples the result; evaluate_mesh hands that cloud to compare_point_clouds.  Differences from
+the reference, by intent:
+  * the draws are Philox4x32-10 by point index, not open3d's mt19937 sequence: the sampled cloud is a function of (mesh, count, seed)
+    and the same on every run, but it is not open3d's cloud;
+  * the cumulative area is summed as a 64-ary tree, open3d's one addition after the other; the two differ in the last bits, which can
+    move a triangle's share by one point;
+  * the script's unused camera-to-LiDAR constants (T_lc) are not restated.
+"""
+import os
+
+from .lidar_map import compare_point_clouds, write_point_cloud
+from .mesher import TriangleMesh
+
+
+def mesh_to_point_cloud(mesh_or_ply_path, resolution, number_of_points=50_000_000, seed=0, device=None):
+    """mesh_to_pcd.py: number_of_points uniform samples of the mesh, then voxel_down_sample(resolution) -> PointCloud.  Given a path,
+    the mesh is read from the .ply and the cloud is also written to <path without its extension>_sampled.pcd, as the script does."""
+    path = mesh_or_ply_path if isinstance(mesh_or_ply_path, (str, os.PathLike)) else None
+    mesh = TriangleMesh.read_ply(path) if path is not None else mesh_or_ply_path
+    cloud = mesh.sample_points_uniformly(number_of_points, seed=seed, device=device)
+    if len(cloud):
+        cloud = cloud.voxel_down_sample(resolution)
+    print(f"Downsampled from {number_of_points} to {len(cloud)}.")
+    if path is not None:
+        out = f"{os.path.splitext(os.fspath(path))[0]}_sampled.pcd"
+        print(f"Saving to {out}")
+        write_point_cloud(out, cloud)
+    return cloud
+
+
+def evaluate_mesh(mesh, gt_cloud, output_dir, f_score_threshold=0.1, voxel_size=0.05, resolution=None, number_of_points=50_000_000,
+                  seed=0, **compare_kwargs):
+    """Accuracy, completion and F-score of a mesh (a TriangleMesh or a .ply path) against the PointCloud gt_cloud: the mesh is sampled
+    (mesh_to_point_cloud at `resolution`, default voxel_size, with its number_of_points and seed) and scored by compare_point_clouds,
+    whose statistics are returned."""
+    cloud = mesh_to_point_cloud(mesh, voxel_size if resolution is None else resolution, number_of_points, seed,
+                                device=gt_cloud.points.device)
+    return compare_point_clouds(cloud, gt_cloud, output_dir, f_score_threshold, voxel_size, **compare_kwargs)

@@ -59,6 +59,31 @@ class TriangleMesh:
         self.vertex_normals = n / np.where(norm > 0, norm, 1.0)
         return self
 
+    def _device_arrays(self, device):
+        from .lidar_map import _device
+        dev = _device(device)
+        return torch.tensor(self.vertices, device=dev), torch.tensor(self.triangles, device=dev)
+
+    def sample_points_uniformly(self, number_of_points, seed=0, device=None, return_triangles=False):
+        """open3d's sample_points_uniformly on the device (include/loner_hip.h: lnr_mesh_sample_points): a PointCloud of
+        number_of_points points, each triangle owning its area's share of them (the stratified rule), from counter-based draws:
+        the cloud depends on (mesh, number_of_points, seed) only.  return_triangles: also the owning triangle of every point (int32
+        tensor on the device).  A mesh without triangles or area gives an empty cloud; open3d raises there."""
+        from .lidar_map import PointCloud
+        n = int(number_of_points)
+        if n <= 0:
+            raise ValueError(f"sample_points_uniformly: number_of_points must be > 0, got {number_of_points!r}")
+        v, t = self._device_arrays(device)
+        out = ops.mesh_sample_points(v, t, n, seed, want_triangles=return_triangles)
+        return (PointCloud(out[0]), out[1]) if return_triangles else PointCloud(out)
+
+    def get_surface_area(self, device=None):
+        """The sum of the triangle areas in the order the sampler's cumulative area takes (include/loner_hip.h)."""
+        v, t = self._device_arrays(device)
+        info = {}
+        ops.mesh_sample_points(v, t, 0, 0, info=info)
+        return info["area"]
+
     def write_ply(self, path, binary=True):
         """PLY with float64 x y z (+ nx ny nz when computed) and int32 vertex_indices lists."""
         normals = self.has_vertex_normals()

@@ -132,10 +132,12 @@ __host__ __device__ inline Philox4 philox4x32_10(uint64_t counter_lo, uint64_t c
 __host__ __device__ __forceinline__ float lnr_u01(uint32_t bits) {
     return (float)(bits & 0x00FFFFFFu) * (1.0f / 16777216.0f);
 }
-// stream ids keep the three per-iteration draws independent
+// stream ids (the counter's high 64 bits) keep the draws independent.  The window rays take 0x44 + segment (lnr_rays.hip) and
+// 0x44 + (which - LNR_DRAW_RAY_INDEX) (lnr_sampler.hip): small numbers upwards of 0x44
 #define LNR_STREAM_JITTER 0x11ull
 #define LNR_STREAM_PDF 0x22ull
 #define LNR_STREAM_NOISE 0x33ull
+#define LNR_STREAM_MESH 0x4D45534800000000ull   /* "MESH" in the top word: no count of ray segments reaches it */
 
 __device__ __forceinline__ float lnr_rand_uniform(uint64_t seed, uint64_t stream_id, uint64_t ray, uint32_t idx) {
     Philox4 p = philox4x32_10(((uint64_t)idx >> 2) | (ray << 20), stream_id, seed);

@@ -5,9 +5,10 @@
 // with the definitions stated in include/loner_hip.h ("normals and point-to-plane ICP").  This file is compiled with -ffp-contract=off
 // (build.py EXACT): every fp64 expression below rounds operation by operation, as the numpy restatement (tests/icp_restatement.py)
 // does.  The grid, its shell walk and its exact pass are lnr_cloud_grid.h's; ties are ordered by (d2, input index) everywhere.
-//   kNN        one query per thread walks the shells with its k best pairs in a 32-slot list of statically indexed registers (an
-//              unrolled insertion) and stops when the k-th best lies strictly below the bound on every unvisited cell; queries still
-//              open after NN_MAX_SHELL shells take the exact pass
+//   kNN        (lnr_cloud_knn.h, shared with the outlier filter of lnr_cloud_tools.hip) one query per thread walks the shells with its
+//              k best pairs in a 32-slot list of statically indexed registers (an unrolled insertion) and stops when the k-th best
+//              lies strictly below the bound on every unvisited cell; queries still open after NN_MAX_SHELL shells take the exact
+//              pass; what happens to a finished list is the caller's Finish (here NormalsFinish)
 //   normals    the cumulant covariance of the neighbours in list order, then open3d's FastEigen3x3 (the robust closed form): the unit
 //              eigenvector of the smallest eigenvalue, in the same launch
 //   ICP        per round: icp_corr finds each source's nearest target within r and sums its 21 JTJ, 6 JTr, d2 and count terms per
@@ -15,49 +16,11 @@
 //              convergence; icp_solve (one thread) does Eigen's pivoted LDLT, Rz Ry Rx and update @ transformation; the working
 //              source then moves by the update where the device computed it.  No float atomics: two runs are bit-identical.  Every
 //              round is enqueued at once; the state's done word makes later rounds return, and the host reads the result once
-#include "lnr_cloud_grid.h"
+#include "lnr_cloud_knn.h"
 
 namespace {
 
 // ------------------------------------------------------------------------------------------------ k nearest neighbours and normals
-// The k best (d2, input index) of one query, ascending, in statically indexed registers (every loop over the list is unrolled: a
-// runtime-indexed private array would live in scratch).  pos: the sorted grid slot of each entry, for its coordinates.
-struct KnnList {
-    double d[LNR_KNN_MAX];
-    uint32_t id[LNR_KNN_MAX], pos[LNR_KNN_MAX];
-    uint32_t found;
-
-    __device__ inline void clear() {
-#pragma unroll
-        for (int j = 0; j < LNR_KNN_MAX; ++j) { d[j] = INFINITY; id[j] = 0xffffffffu; pos[j] = 0; }
-        found = 0;
-    }
-    // insertion into the sorted list: slot j takes its predecessor, the candidate or itself (top down, so each step reads old values)
-    __device__ inline void insert(double cd, uint32_t cid, uint32_t cpos) {
-        if (!pair_less(cd, cid, d[LNR_KNN_MAX - 1], id[LNR_KNN_MAX - 1])) return;
-        found += found < LNR_KNN_MAX ? 1u : 0u;
-#pragma unroll
-        for (int j = LNR_KNN_MAX - 1; j > 0; --j) {
-            const bool before_prev = pair_less(cd, cid, d[j - 1], id[j - 1]);
-            const bool before_here = pair_less(cd, cid, d[j], id[j]);
-            d[j] = before_prev ? d[j - 1] : (before_here ? cd : d[j]);
-            id[j] = before_prev ? id[j - 1] : (before_here ? cid : id[j]);
-            pos[j] = before_prev ? pos[j - 1] : (before_here ? cpos : pos[j]);
-        }
-        const bool first = pair_less(cd, cid, d[0], id[0]);
-        d[0] = first ? cd : d[0];
-        id[0] = first ? cid : id[0];
-        pos[0] = first ? cpos : pos[0];
-    }
-    // d2 of the k-th entry (INFINITY while fewer than k are known), by selects rather than a runtime index
-    __device__ inline double kth(int k) const {
-        double v = INFINITY;
-#pragma unroll
-        for (int j = 0; j < LNR_KNN_MAX; ++j) v = j == k - 1 ? d[j] : v;
-        return v;
-    }
-};
-
 __device__ inline void cross3(const double a[3], const double b[3], double out[3]) {
     out[0] = a[1] * b[2] - a[2] * b[1];
     out[1] = a[2] * b[0] - a[0] * b[2];
@@ -168,87 +131,42 @@ __device__ inline void normal_of(const double C[3][3], double n[3]) {
     }
 }
 
-// covariance of the first min(k, found) entries from cumulants summed in list order, its normal, both written at the query's input index
-__device__ inline void knn_finish(const GridView& g, const KnnList& L, int k, uint32_t out, double* __restrict__ normals,
-                                  double* __restrict__ cov_out) {
-    const uint32_t m = L.found < (uint32_t)k ? L.found : (uint32_t)k;
-    double C[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
-    if (m >= 3) {
-        double s[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+// lnr_cloud_knn.h's Finish: the covariance of the first min(k, found) entries from cumulants summed in list order, and its normal, both
+// written at the query's input index
+struct NormalsFinish {
+    double* __restrict__ normals;
+    double* __restrict__ cov_out;
+
+    __device__ inline void operator()(const GridView& g, const KnnList& L, int k, uint32_t out) const {
+        const uint32_t m = L.found < (uint32_t)k ? L.found : (uint32_t)k;
+        double C[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+        if (m >= 3) {
+            double s[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-        for (int j = 0; j < LNR_KNN_MAX; ++j) {
-            if ((uint32_t)j < m) {
-                const double* t = g.pts + 3 * (size_t)L.pos[j];
-                const double x = t[0], y = t[1], z = t[2];
-                s[0] = s[0] + x; s[1] = s[1] + y; s[2] = s[2] + z;
-                s[3] = s[3] + x * x; s[4] = s[4] + x * y; s[5] = s[5] + x * z;
-                s[6] = s[6] + y * y; s[7] = s[7] + y * z; s[8] = s[8] + z * z;
+            for (int j = 0; j < LNR_KNN_MAX; ++j) {
+                if ((uint32_t)j < m) {
+                    const double* t = g.pts + 3 * (size_t)L.pos[j];
+                    const double x = t[0], y = t[1], z = t[2];
+                    s[0] = s[0] + x; s[1] = s[1] + y; s[2] = s[2] + z;
+                    s[3] = s[3] + x * x; s[4] = s[4] + x * y; s[5] = s[5] + x * z;
+                    s[6] = s[6] + y * y; s[7] = s[7] + y * z; s[8] = s[8] + z * z;
+                }
             }
+            const double c = (double)m;
+            for (int v = 0; v < 9; ++v) s[v] = s[v] / c;
+            C[0][0] = s[3] - s[0] * s[0]; C[1][1] = s[6] - s[1] * s[1]; C[2][2] = s[8] - s[2] * s[2];
+            C[0][1] = C[1][0] = s[4] - s[0] * s[1];
+            C[0][2] = C[2][0] = s[5] - s[0] * s[2];
+            C[1][2] = C[2][1] = s[7] - s[1] * s[2];
         }
-        const double c = (double)m;
-        for (int v = 0; v < 9; ++v) s[v] = s[v] / c;
-        C[0][0] = s[3] - s[0] * s[0]; C[1][1] = s[6] - s[1] * s[1]; C[2][2] = s[8] - s[2] * s[2];
-        C[0][1] = C[1][0] = s[4] - s[0] * s[1];
-        C[0][2] = C[2][0] = s[5] - s[0] * s[2];
-        C[1][2] = C[2][1] = s[7] - s[1] * s[2];
+        double nv[3];
+        normal_of(C, nv);
+        for (int a = 0; a < 3; ++a) normals[3 * (size_t)out + a] = nv[a];
+        if (cov_out)
+            for (int a = 0; a < 3; ++a)
+                for (int b = 0; b < 3; ++b) cov_out[9 * (size_t)out + 3 * a + b] = C[a][b];
     }
-    double nv[3];
-    normal_of(C, nv);
-    for (int a = 0; a < 3; ++a) normals[3 * (size_t)out + a] = nv[a];
-    if (cov_out)
-        for (int a = 0; a < 3; ++a)
-            for (int b = 0; b < 3; ++b) cov_out[9 * (size_t)out + 3 * a + b] = C[a][b];
-}
-
-// one query per thread: sorted target i (consecutive threads take neighbouring points), output at its input index
-__global__ __launch_bounds__(CL_BLOCK) void knn_normals(GridView g, int k, double* __restrict__ normals, double* __restrict__ cov_out,
-                                                        uint32_t* __restrict__ fallback, unsigned long long* __restrict__ counters) {
-    const uint32_t i = blockIdx.x * CL_BLOCK + threadIdx.x;
-    unsigned long long shells = 0;
-    if (i < g.p->n) {
-        const double* qp = g.pts + 3 * (size_t)i;
-        const ShellQuery s = shell_query(g.p, qp[0], qp[1], qp[2]);
-        KnnList L;
-        L.clear();
-        auto visit = [&](uint32_t j) { L.insert(sq_dist(s.q[0], s.q[1], s.q[2], g.pts + 3 * (size_t)j), g.orig[j], j); };
-        bool done = false;
-        for (int r = 0; r <= NN_MAX_SHELL && !done; ++r) {
-            ++shells;
-            const double lb = shell_visit(g, s, r, visit);
-            done = lb == INFINITY || L.kth(k) < lb;             // strict: an unvisited target at the same d2 could have a lower index
-        }
-        if (done) knn_finish(g, L, k, g.orig[i], normals, cov_out);
-        else fallback[atomicAdd(&counters[0], 1ull)] = i;
-    }
-    shells = wave_sum(shells);
-    if ((threadIdx.x & 63) == 0 && shells) atomicAdd(&counters[2], shells);
-}
-
-// the exact fallback: nn_brute's tile loop (lnr_cloud.hip) with each target's input index beside it
-__global__ __launch_bounds__(CL_BLOCK) void knn_brute(GridView g, int k, const uint32_t* __restrict__ fallback,
-                                                      const unsigned long long* __restrict__ counters, double* __restrict__ normals,
-                                                      double* __restrict__ cov_out) {
-    __shared__ double tile[NN_FB_TILE * 3];
-    __shared__ uint32_t tile_id[NN_FB_TILE];
-    const uint32_t n_fb = (uint32_t)counters[0];
-    if ((uint64_t)blockIdx.x * CL_BLOCK >= n_fb) return;
-    const uint32_t f = blockIdx.x * CL_BLOCK + threadIdx.x;
-    const bool active = f < n_fb;
-    const uint32_t i = active ? fallback[f] : 0u;
-    const double qx = g.pts[3 * (size_t)i], qy = g.pts[3 * (size_t)i + 1], qz = g.pts[3 * (size_t)i + 2];
-    const uint32_t n = g.p->n;
-    KnnList L;
-    L.clear();
-    for (uint32_t t0 = 0; t0 < n; t0 += NN_FB_TILE) {
-        const uint32_t m = n - t0 < NN_FB_TILE ? n - t0 : NN_FB_TILE;
-        __syncthreads();
-        for (uint32_t e = threadIdx.x; e < 3 * m; e += CL_BLOCK) tile[e] = g.pts[3 * (size_t)t0 + e];
-        for (uint32_t e = threadIdx.x; e < m; e += CL_BLOCK) tile_id[e] = g.orig[t0 + e];
-        __syncthreads();
-        for (uint32_t j = 0; j < m; ++j) L.insert(sq_dist(qx, qy, qz, tile + 3 * j), tile_id[j], t0 + j);
-    }
-    if (active) knn_finish(g, L, k, g.orig[i], normals, cov_out);
-}
+};
 
 // ------------------------------------------------------------------------------------------------ point-to-plane ICP
 // Terms of one correspondence's contribution, in this order: JTJ upper triangle row by row (21), JTr (6), d2, count.
@@ -570,11 +488,6 @@ __global__ void icp_end(const IcpState* st, double* result, int64_t* info) {
     info[7] = 0;
 }
 
-// a grid unusable for its own points (a non-finite target, or another count than the call's): counters[1] = 1
-__global__ void grid_status(const CloudParams* __restrict__ p, uint32_t n, unsigned long long* __restrict__ counters) {
-    if (p->status || p->n != n) counters[1] = 1ull;
-}
-
 // ------------------------------------------------------------------------------------------------ host
 uint32_t icp_blocks(int64_t n_source) {
     const uint32_t b = blocks_for(n_source);
@@ -607,10 +520,7 @@ extern "C" int lnr_cloud_normals(const void* grid, int64_t n_points, int32_t knn
     uint32_t* fb = (uint32_t*)workspace;
     unsigned long long* cnt = (unsigned long long*)counters_dev;
     const uint32_t n = (uint32_t)n_points;
-    hipLaunchKernelGGL(knn_normals, dim3(blocks_for(n)), dim3(CL_BLOCK), 0, st, g, (int)knn, normals, covariances, fb, cnt);
-    hipLaunchKernelGGL(knn_brute, dim3(blocks_for(n)), dim3(CL_BLOCK), 0, st, g, (int)knn, (const uint32_t*)fb, (const unsigned long long*)cnt,
-                       normals, covariances);
-    hipLaunchKernelGGL(grid_status, dim3(1), dim3(1), 0, st, g.p, n, cnt);
+    enqueue_knn(g, n, (int)knn, NormalsFinish{normals, covariances}, fb, cnt, st);
     LNR_CHECK_LAUNCH("lnr_cloud_normals");
     return LNR_OK;
 }

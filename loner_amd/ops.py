@@ -670,6 +670,39 @@ class NNGrid:
             stats.update(fallback=int(c[0]), shells=int(c[2]))
         return (normals, cov) if want_covariances else normals
 
+    def knn_mean_distance(self, nb_neighbors=20, stats=None):
+        """The mean distance of every target to its nb_neighbors nearest targets, itself included (include/loner_hip.h:
+        lnr_cloud_knn_mean_distance) -> fp64 [n] in the targets' order; stats as normals'.  One device -> host read."""
+        k = int(nb_neighbors)
+        if not 1 <= k <= hip.KNN_MAX:
+            raise ValueError(f"knn_mean_distance: nb_neighbors must be in [1, {hip.KNN_MAX}], got {nb_neighbors}")
+        dev = self.buf.device
+        avg = torch.empty(self.n, device=dev, dtype=torch.float64)
+        ws, need = _tools_workspace(self.n, dev)
+        c = _read_counters(dev, lambda counters: load().lnr_cloud_knn_mean_distance(_ptr(self.buf), self.n, k, _ptr(avg), _ptr(ws), need,
+                                                                                    counters, _stream()), "lnr_cloud_knn_mean_distance")
+        if int(c[1]):
+            raise RuntimeError("knn_mean_distance: the grid is unusable (non-finite targets)")
+        if stats is not None:
+            stats.update(fallback=int(c[0]), shells=int(c[2]))
+        return avg
+
+    def outlier_threshold(self, mean_distance, std_ratio):
+        """open3d's statistical-outlier threshold over knn_mean_distance's values (include/loner_hip.h: lnr_cloud_outlier_threshold)
+        -> fp64 [4] on the device: {mean, std, threshold, valid}.  No host read."""
+        avg = mean_distance
+        require_device(avg)
+        if avg.dtype != torch.float64 or avg.shape != (self.n,) or not avg.is_contiguous():
+            raise ValueError(f"outlier_threshold: mean_distance fp64 [{self.n}], got {tuple(avg.shape)} {avg.dtype}")
+        ratio = float(std_ratio)
+        if not math.isfinite(ratio):
+            raise ValueError(f"outlier_threshold: std_ratio must be finite, got {std_ratio!r}")
+        ws, need = _tools_workspace(self.n, avg.device)
+        res = torch.empty(4, device=avg.device, dtype=torch.float64)
+        check(load().lnr_cloud_outlier_threshold(_ptr(self.buf), _ptr(avg), self.n, ratio, _ptr(ws), need, _ptr(res), _stream()),
+              "lnr_cloud_outlier_threshold")
+        return res
+
     def correspondences(self, queries, max_distance):
         """-> (index int32 [m]: the nearest target with d2 < max_distance^2, lower index on ties, -1 for none; d2 [m] fp64, +inf for
         none) (include/loner_hip.h: lnr_icp_correspondences)."""
@@ -727,6 +760,101 @@ def icp_point_to_plane(grid, target_normals, source, max_distance, init=None, re
     return {"transformation": res[:16].reshape(4, 4).copy(), "fitness": float(res[16]), "inlier_rmse": float(res[17]),
             "n_correspondences": info[1], "iterations": info[2], "JTJ": JTJ, "JTr": res[39:45].copy(), "sum_d2": float(res[45]),
             "x": res[46:52].copy(), "system_correspondences": info[5]}
+
+
+# ---------------------------------------------------------------- mesh sampling, trajectory transform
+def _tools_workspace(n, device):
+    """(buffer, bytes) for the entries that take lnr_cloud_tools_workspace(n) bytes: a buffer per call (the caching allocator's, so
+    calls on different streams never share one)"""
+    need = int(load().lnr_cloud_tools_workspace(int(n)))
+    if need == 0:
+        raise RuntimeError(f"{n} points, the limit is 2^31 - 4096")
+    return torch.empty(need, device=device, dtype=torch.uint8), need
+
+
+_MESH_STATUS = {1: "a triangle uses a non-finite vertex", 2: "a vertex index is out of range", 4: "the total area is not finite"}
+
+
+def mesh_sample_points(vertices, triangles, n_points, seed=0, want_triangles=False, info=None):
+    """open3d's sample_points_uniformly with a defined order (include/loner_hip.h: lnr_mesh_sample_points): vertices [V,3] (fp64) and
+    triangles [F,3] (int32) on the device -> points [m,3] fp64 (and the owning triangle int32 [m] when asked); m = n_points, or 0 for a
+    mesh without area.  info (a dict, optional) receives {"area", "bad_triangles"}.  Raises RuntimeError on a status bit.  One
+    device -> host read."""
+    require_device(vertices, triangles)
+    v = _f64_points(vertices, "mesh_sample_points")
+    if triangles.dim() != 2 or triangles.shape[1] != 3 or triangles.dtype != torch.int32:
+        raise ValueError(f"mesh_sample_points: triangles int32 [F,3], got {tuple(triangles.shape)} {triangles.dtype}")
+    tri = triangles.contiguous()
+    n, seed = int(n_points), int(seed)
+    if n < 0 or not 0 <= seed < 2 ** 64:
+        raise ValueError(f"mesh_sample_points: n_points >= 0 and a 64-bit seed, got {n_points!r} and {seed!r}")
+    dev = v.device
+    lib = load()
+    need = int(lib.lnr_mesh_sample_workspace(tri.shape[0]))
+    if need == 0:
+        raise RuntimeError(f"mesh_sample_points: {tri.shape[0]} triangles, the limit is 2^31 - 4096")
+    ws = torch.empty(need, device=dev, dtype=torch.uint8)
+    points = torch.empty(n, 3, device=dev, dtype=torch.float64)
+    owner = torch.empty(n, device=dev, dtype=torch.int32) if want_triangles else None
+    info_dev = torch.empty(8, device=dev, dtype=torch.int64)
+    check(lib.lnr_mesh_sample_points(_ptr(v), v.shape[0], _ptr(tri), tri.shape[0], n, seed, _ptr(ws), need, _ptr(points), _ptr(owner),
+                                     _ptr(info_dev), _stream()), "lnr_mesh_sample_points")
+    host = info_dev.cpu()
+    status = int(host[0])
+    if status:
+        raise RuntimeError(f"mesh_sample_points: {int(host[2])} bad triangles: " + ", ".join(m for b, m in _MESH_STATUS.items() if status & b))
+    if info is not None:
+        info.update(area=float(host[3:4].view(torch.float64)[0]), bad_triangles=int(host[2]))
+    m = int(host[1])
+    return (points[:m], owner[:m]) if want_triangles else points[:m]
+
+
+class Trajectory:
+    """A ground-truth trajectory on the device, in the form lnr_cloud_trajectory_transform takes: times [K] (strictly increasing),
+    positions [K,3], rotations [K,3,3] and the rotation vectors log(R_k^T R_k+1) [K-1,3], all fp64 host arrays here."""
+
+    def __init__(self, times, positions, rotations, rotvecs, device):
+        import numpy as np
+        t = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
+        K = t.shape[0]
+        if K < 2:
+            raise ValueError(f"Trajectory: at least 2 poses are needed, got {K}")
+        P = np.ascontiguousarray(positions, dtype=np.float64)
+        R = np.ascontiguousarray(rotations, dtype=np.float64)
+        W = np.ascontiguousarray(rotvecs, dtype=np.float64)
+        if P.shape != (K, 3) or R.shape != (K, 3, 3) or W.shape != (K - 1, 3):
+            raise ValueError(f"Trajectory: positions [{K},3], rotations [{K},3,3] and rotvecs [{K - 1},3], got {P.shape}, {R.shape}, {W.shape}")
+        if not (np.isfinite(t).all() and np.isfinite(P).all() and np.isfinite(R).all() and np.isfinite(W).all()):
+            raise ValueError("Trajectory: a pose or a pose time is not finite")
+        if not (np.diff(t) > 0).all():
+            raise ValueError("Trajectory: the pose times must be strictly increasing")
+        self.n_poses = K
+        self.t0, self.t1 = float(t[0]), float(t[-1])
+        self.times, self.positions, self.rotations, self.rotvecs = (torch.from_numpy(a).to(device) for a in (t, P, R, W))
+
+
+def trajectory_transform(points, timestamps, trajectory, min_range):
+    """Every point moved by the trajectory's pose at its own time (include/loner_hip.h: lnr_cloud_trajectory_transform): points [n,3]
+    (sensor frame), timestamps [n] (absolute, fp64), trajectory a Trajectory on the same device -> (out [n,3] fp64 whose first `kept`
+    rows hold the kept points in input order, info int64 [8] on the device: {status, kept, below range, outside, non-finite})."""
+    pts = _f64_points(points, "trajectory_transform")
+    require_device(timestamps)
+    n = pts.shape[0]
+    if timestamps.shape != (n,):
+        raise ValueError(f"trajectory_transform: timestamps [{n}], got {tuple(timestamps.shape)}")
+    stamps = timestamps.to(torch.float64).contiguous()
+    r = float(min_range)
+    if math.isnan(r):
+        raise ValueError("trajectory_transform: min_range is NaN")
+    dev = pts.device
+    ws, need = _tools_workspace(n, dev)
+    out = torch.empty(n, 3, device=dev, dtype=torch.float64)
+    info = torch.empty(8, device=dev, dtype=torch.int64)
+    tr = trajectory
+    check(load().lnr_cloud_trajectory_transform(_ptr(pts), _ptr(stamps), n, _ptr(tr.times), _ptr(tr.positions), _ptr(tr.rotations),
+                                                _ptr(tr.rotvecs), tr.n_poses, r, _ptr(ws), need, _ptr(out), _ptr(info), _stream()),
+          "lnr_cloud_trajectory_transform")
+    return out, info
 
 
 # ---------------------------------------------------------------- tracking
