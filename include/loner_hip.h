@@ -260,6 +260,19 @@ int lnr_build_window_rays(const float* const* directions, const float* const* di
                           float range_min, float range_max, float scale, const float* shift /*host [3]*/,
                           float* rays, float* depths, uint8_t* keep, void* stream);
 
+/* CameraRayDirections.build_rays (ray_utils.py:175-213) with get_far_val(no_nan=True) (:31-60) for one camera pose: one thread per
+ * ray.  directions [n_pixels,3] are the camera-frame directions of get_ray_directions (:62-125), row-major over the image; index
+ * (device int64 [n_rays], NULL: the pixels 0 .. n_rays-1 in order) names the pixel of each ray; transform: 12 floats = rows of the
+ * camera-to-world [R|t], which is read, never written (the reference shifts its argument in place).  Record, every operation rounded
+ * on its own in fp32: origin (t + shift) / scale (add, then divide); direction (R dir) / |R dir| with the products summed left to
+ * right; view direction = -direction; columns 9, 10 = pixel x = index % width and y = index / width; near = range_min / scale; far =
+ * the cube exit distance of lnr_build_lidar_rays (direction + 1e-15).  Unlike LiDAR rays, far is not capped by the sensor range and
+ * no ray is dropped.  An index outside [0, n_pixels) gives a record of NaNs.  directions, index, transform and rays are device
+ * pointers (the kernel reads the pose on the device); shift is a host array. */
+int lnr_build_camera_rays(const float* directions /*device [n_pixels,3]*/, int64_t n_pixels, const int64_t* index /*device [n_rays] or NULL*/,
+                          int32_t n_rays, int32_t width, const float* transform /*device [12]*/, float range_min, float scale,
+                          const float* shift /*host [3]*/, float* rays /*[n_rays,13]*/, void* stream);
+
 /* tensor_to_transform (pose_utils.py:288-302) for n poses: pose6 [n,6] = [t, axis-angle] -> transforms [n,12]
  * (rows of [R|t]); and its backward d_transforms [n,12] -> d_pose6 [n,6] (mask nullable: 0 = fixed pose;
  * accumulate != 0 adds to d_pose6). */
@@ -384,6 +397,26 @@ int lnr_render_forward(const float* sigma, const float* z, const float* rays, in
                        const int32_t* n_rays_dev, int32_t n_samples,
                        const float* noise, float noise_std, uint64_t seed,
                        float* depth, float* weights, float* opacity, float* variance, void* stream);
+
+/* lnr_render_forward without the [n_rays,n_samples] weights, plus the ray's peak: what the depth renderer reads from
+ * weights_fine / samples_fine (analysis/renderer.py:195-198: samples_fine[argmax(weights_fine)]).  depth, opacity and variance are
+ * lnr_render_forward's bit for bit (same arithmetic, same noise draws).  peak_index (int32) is the sample of maximal weight with
+ * torch.argmax's rules - on equal weights the lowest index, a NaN weight counts as maximal and the lowest NaN wins - and peak_z is
+ * z[ray][peak_index], copied, not computed.  Outputs nullable. */
+int lnr_render_forward_peak(const float* sigma, const float* z, const float* rays, int32_t n_rays,
+                            const int32_t* n_rays_dev, int32_t n_samples,
+                            const float* noise, float noise_std, uint64_t seed,
+                            float* depth, float* opacity, float* variance, float* peak_z, int32_t* peak_index, void* stream);
+
+/* save_depth (analysis/render_utils.py:116-127) per element, values [n] fp32 -> rgba [n,4] uint8 (4-byte aligned):
+ *   v = values * multiplier (fp32; the world cube's scale for raw depths, 1 for metres); NaN -> (0,0,0,0), matplotlib's "bad" colour;
+ *   v >= (float) max_depth -> (0,0,0,255), the reference's mask; otherwise c = clip(v, (float) min_depth, (float) max_depth),
+ *   x = clip((c - (float) min_depth) / (float)(max_depth - min_depth), 0, 1) (the span subtracted in fp64 and rounded once, as Python
+ *   does before torch sees it; subtract and divide rounded on their own in fp32), k = min(floor(256 x), 255) - matplotlib's index
+ *   rule - and the pixel is (table[3k], table[3k+1], table[3k+2], 255).  table: device uint8 [256,3], the colour map already
+ *   truncated to uint8 ((lut * 255).astype(uint8), the reference's last step). */
+int lnr_depth_colormap(const float* values, int64_t n, float multiplier, double min_depth, double max_depth,
+                       const uint8_t* table /*[256,3]*/, uint8_t* rgba /*[n,4]*/, void* stream);
 
 /* Backward of lnr_render_forward for arbitrary upstream gradients (nullable each):
  * g_depth[n], g_weights[n,S], g_opacity[n], g_variance[n]  ->  d_sigma [n,S] and the direct

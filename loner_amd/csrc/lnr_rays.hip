@@ -166,6 +166,52 @@ extern "C" int lnr_build_window_rays(const float* const* directions, const float
     return LNR_OK;
 }
 
+// Camera rays of a pinhole image (CameraRayDirections.build_rays, ray_utils.py:175-213): one thread per ray.  index == NULL: every
+// pixel in order.  The record is the reference's: origin (t + shift) / scale, direction (dir @ R^T) / |.|, its negative, the pixel's
+// x and y, near = range_min / scale and far = the cube exit (get_far_val(no_nan=True): cube_exit above) - not capped by range_max,
+// and no ray is dropped.
+__global__ void build_camera_rays_kernel(const float* __restrict__ directions, int64_t n_pixels, const int64_t* __restrict__ index, int n_rays, int width,
+                                         const float* __restrict__ T, float range_min, float scale, float sx, float sy, float sz,
+                                         float* __restrict__ rays) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_rays) return;
+    const int64_t src = index ? index[i] : (int64_t)i;
+    float* rec = rays + (size_t)i * LNR_RAY_STRIDE;
+    if (src < 0 || src >= n_pixels) {                   // not a pixel of this image: a record of NaNs, nothing read
+#pragma unroll
+        for (int c = 0; c < LNR_RAY_STRIDE; ++c) rec[c] = __int_as_float(0x7FC00000);
+        return;
+    }
+    const float l0 = directions[3 * src], l1 = directions[3 * src + 1], l2 = directions[3 * src + 2];
+    float o[3], d[3], v[3];
+    o[0] = (T[3] + sx) / scale;
+    o[1] = (T[7] + sy) / scale;
+    o[2] = (T[11] + sz) / scale;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) v[r] = T[4 * r] * l0 + T[4 * r + 1] * l1 + T[4 * r + 2] * l2;
+    const float nrm = sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) d[r] = v[r] / nrm;
+    rec[0] = o[0]; rec[1] = o[1]; rec[2] = o[2];
+    rec[3] = d[0]; rec[4] = d[1]; rec[5] = d[2];
+    rec[6] = -d[0]; rec[7] = -d[1]; rec[8] = -d[2];
+    rec[9] = (float)(src % width); rec[10] = (float)(src / width);
+    rec[11] = range_min / scale;
+    rec[12] = cube_exit(o, d, nullptr, nullptr, nullptr);
+}
+
+extern "C" int lnr_build_camera_rays(const float* directions, int64_t n_pixels, const int64_t* index, int32_t n_rays, int32_t width,
+                                     const float* transform, float range_min, float scale, const float* shift, float* rays, void* stream) {
+    LNR_REQUIRE(directions && transform && shift && rays, "lnr_build_camera_rays: null argument");
+    LNR_REQUIRE(n_pixels > 0 && n_rays >= 0 && width > 0 && scale > 0.0f, "lnr_build_camera_rays: bad sizes");
+    LNR_REQUIRE(index != nullptr || (int64_t)n_rays <= n_pixels, "lnr_build_camera_rays: %d rays of an image of %lld pixels", n_rays, (long long)n_pixels);
+    if (n_rays == 0) return LNR_OK;
+    hipLaunchKernelGGL(build_camera_rays_kernel, dim3(lnr_div_up(n_rays, 256)), dim3(256), 0, (hipStream_t)stream, directions, n_pixels, index,
+                       n_rays, width, transform, range_min, scale, shift[0], shift[1], shift[2], rays);
+    LNR_CHECK_LAUNCH("lnr_build_camera_rays");
+    return LNR_OK;
+}
+
 struct SegOrder { int n; int order[LNR_MAX_SEG]; };
 // what lnr_compact_rays_front appends to the compaction (one launch instead of two: a one-keyframe rank's iteration is a chain of
 // ~4.7 us launches around 0.3 ms of real kernels): the loss normalisers of lnr_count_opaque (counts != NULL) or the rank's front record

@@ -1,6 +1,8 @@
 // One ray of volume rendering held by one wave (raw2outputs, src/models/rendering_tcnn.py:71-147): shared by the kernels of
-// lnr_render.hip and the mesher's fused accumulation (lnr_mesh.hip).  Each includer compiles its own copy; see lnr_mesh.hip for why
-// that translation unit is built without SLP vectorisation.
+// lnr_render.hip, the mesher's fused accumulation (lnr_mesh.hip) and the compositing with the peak (lnr_render_peak.hip).  Each of
+// the three includers compiles its own copy, and the three must stay bit-identical: see lnr_mesh.hip and lnr_render_peak.hip for why
+// those two translation units are built without SLP vectorisation, and tests/test_gpu_mesh.py and tests/test_gpu_camera.py for the
+// checks that fail when an edit here contracts differently in one of them.
 #pragma once
 #include "lnr_common.h"
 

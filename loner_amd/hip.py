@@ -94,6 +94,7 @@ _SIGNATURES = {
     "lnr_build_window_rays": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.POINTER(C.c_int64),
                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, P, P, C.c_uint64, P, C.c_float, C.c_float,
                                         C.c_float, C.POINTER(C.c_float), P, P, P, P]),
+    "lnr_build_camera_rays": (C.c_int, [P, C.c_int64, P, C.c_int32, C.c_int32, P, C.c_float, C.c_float, C.POINTER(C.c_float), P, P]),
     "lnr_pose_forward": (C.c_int, [P, C.c_int32, P, P]),
     "lnr_pose_backward": (C.c_int, [P, P, P, C.c_int32, P, C.c_int32, P, C.c_int32, P]),
     "lnr_compact_rays": (C.c_int, [P, P, P, P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, P, P, P, P, P, P]),
@@ -105,6 +106,8 @@ _SIGNATURES = {
                                       P, P, P, P, P]),
     "lnr_sample_rays_uniform": (C.c_int, [P, C.c_int32, P, C.c_int32, C.c_float, P, P, C.c_uint64, P, P]),
     "lnr_render_forward": (C.c_int, [P, P, P, C.c_int32, P, C.c_int32, P, C.c_float, C.c_uint64, P, P, P, P, P]),
+    "lnr_render_forward_peak": (C.c_int, [P, P, P, C.c_int32, P, C.c_int32, P, C.c_float, C.c_uint64, P, P, P, P, P, P]),
+    "lnr_depth_colormap": (C.c_int, [P, C.c_int64, C.c_float, C.c_double, C.c_double, P, P, P]),
     "lnr_render_backward": (C.c_int, [P, P, P, C.c_int32, P, C.c_int32, P, C.c_float, C.c_uint64, P, P, P, P, P, P, P]),
     "lnr_render_ftb_gather": (C.c_int, [P, P, C.c_int32, P, P, C.c_int32, C.c_int32, C.c_int32, P, P, P, P]),
     "lnr_render_ftb_composite": (C.c_int, [P, P, P, C.c_int32, P, P, C.c_int32, C.c_int32, C.c_int32, P, C.c_float, C.c_uint64, P, P, P, P, P, C.c_int32, P]),

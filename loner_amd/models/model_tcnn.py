@@ -53,11 +53,13 @@ class Model(nn.Module):
         r = self.cfg.render
         return (r.N_samples_test, 0.) if testing else (r.N_samples_train, r.perturb)
 
-    def _render_no_grad(self, rays, ray_sampler, n_samples, perturb, want_weights):
+    def _render_no_grad(self, rays, ray_sampler, n_samples, perturb, want_weights, want_peak=False):
         """Rendering without autograd (Model.forward under no_grad / for inputs that need no gradient, render_depth): the whole
         batch goes through sampler -> density forward -> compositing in launches of _POINTS_PER_LAUNCH samples, whatever
         cfg.render.chunk says (the reference's chunk loop, model_tcnn.py:81-101, bounds ITS memory; results do not depend on
         it).  Nothing is kept for a backward pass: forward-only workspace, no [N,S] weights unless asked for.
+        want_peak: composite with ops.render_forward_peak instead - the result gains "peak_z", the depth of each ray's sample of
+        maximal weight, and has no weights.
         Parity hook: a `draws` object on the sampler is consumed chunk by chunk in the reference's order (per chunk: sampler
         draws, then the density noise), so recorded reference draws replay bit for bit."""
         rays = rays.detach().float().contiguous()
@@ -80,7 +82,7 @@ class Model(nn.Module):
             cat = lambda xs: torch.cat(xs).to(rays.device) if xs else None
             pre = (cat(u1), cat(u2), cat(nz))
         step = max(64, self._POINTS_PER_LAUNCH // int(n_samples))
-        out = {"depth": [], "opacity": [], "variance": [], "weights": [], "z": []}
+        out = {"depth": [], "opacity": [], "variance": [], "weights": [], "z": [], "peak_z": []}
         # Several launches and the in-kernel generator: the sampler of launch i + 1 runs on a second stream beside the density forward of
         # launch i (whose waves spend most of their cycles waiting for table lines: the sampler's sort fills them) - 2.3 of a scan's 31.7 ms
         # hidden.  Same kernels, same arguments, and the host generator is asked for its seeds in the same order as before
@@ -125,10 +127,15 @@ class Model(nn.Module):
                 z = ray_sampler.get_samples(r, n_samples, perturb, **kw)
                 seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if (noise is None and noise_std > 0) else 0
             sigma = ops.density_forward(net.spec, net.params.detach(), rays=r, z=z, forward_only=True)
-            depth, weights, opacity, variance = ops.render_forward(sigma, z, r, noise=noise, noise_std=noise_std, seed=seed,
-                                                                   want_weights=want_weights)
-            for k, v in (("depth", depth), ("opacity", opacity), ("variance", variance), ("weights", weights), ("z", z)):
-                if v is not None and (k != "z" or self.cfg.render.retraw):
+            peak_z = None
+            if want_peak:
+                depth, opacity, variance, peak_z, _ = ops.render_forward_peak(sigma, z, r, noise=noise, noise_std=noise_std, seed=seed)
+                weights = None
+            else:
+                depth, weights, opacity, variance = ops.render_forward(sigma, z, r, noise=noise, noise_std=noise_std, seed=seed,
+                                                                       want_weights=want_weights)
+            for k, v in (("depth", depth), ("opacity", opacity), ("variance", variance), ("weights", weights), ("z", z), ("peak_z", peak_z)):
+                if v is not None and (k != "z" or (self.cfg.render.retraw and not want_peak)):
                     out[k].append(v)
         self.nerf_model.warn_if_clipped(rays.device)
         return {k: (v[0] if len(v) == 1 else torch.cat(v, 0)) for k, v in out.items() if v}
@@ -221,6 +228,19 @@ class Model(nn.Module):
         if front_to_back and n_samples % self._FTB_BLOCK == 0 and n_samples > self._FTB_BLOCK:
             return self._render_depth_front_to_back(rays, ray_sampler, n_samples, perturb)
         return self._render_no_grad(rays, ray_sampler, n_samples, perturb, want_weights=False)["depth"]
+
+    @torch.no_grad()
+    def render_depth_peak(self, rays, ray_sampler, testing=True):
+        """-> (depth [n], peak_z [n]): the rendered depth and, per ray, the depth of the sample of maximal weight - what the depth
+        renderer takes from forward(testing=True)'s weights_fine and samples_fine (analysis/renderer.py:195-198 of the reference:
+        samples_fine[argmax(weights_fine)]) without either [n,S] array being kept.  _render_no_grad's loop: after the same
+        torch.manual_seed both are what forward(testing=True) gives, bit for bit.  World-cube units."""
+        n_samples, perturb = self._sample_counts(testing)
+        if rays.shape[0] == 0:
+            empty = torch.empty(0, device=rays.device, dtype=torch.float32)
+            return empty, empty.clone()
+        r = self._render_no_grad(rays, ray_sampler, n_samples, perturb, want_weights=False, want_peak=True)
+        return r["depth"], r["peak_z"]
 
     _FTB_BLOCK = 256          # samples per block along the ray (lnr_render_ftb_composite: one wave per ray, four samples per lane)
     _FTB_RAYS = 16384         # rays per chunk: a block of a chunk is one density-forward launch of at most 2^22 samples

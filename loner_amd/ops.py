@@ -198,6 +198,23 @@ def build_lidar_rays(directions, distances, index, transform12, ray_range, scale
     return rays, depths, keep
 
 
+def build_camera_rays(directions, index, width, transform12, range_min, scale, shift):
+    """-> rays [n,13] of a pinhole image (lnr_build_camera_rays).  directions [n_pixels,3] fp32 on the device; index: int64 pixel
+    indices on the device, or None for every pixel in order."""
+    require_device(directions, index, transform12)
+    directions, transform12 = _f32c(directions), _f32c(transform12)
+    assert directions.dim() == 2 and directions.shape[1] == 3 and transform12.numel() == 12
+    n_pixels = directions.shape[0]
+    if index is not None:
+        index = index.to(torch.int64).contiguous()
+    n = n_pixels if index is None else index.shape[0]
+    rays = torch.empty(n, hip.RAY_STRIDE, device=directions.device, dtype=torch.float32)
+    sh = (C.c_float * 3)(float(shift[0]), float(shift[1]), float(shift[2]))
+    check(load().lnr_build_camera_rays(_ptr(directions), n_pixels, _ptr(index), n, int(width), _ptr(transform12), float(range_min),
+                                       float(scale), sh, _ptr(rays), _stream()), "lnr_build_camera_rays")
+    return rays
+
+
 class WindowTables:
     """Host-side per-segment tables of a keyframe window for lnr_build_window_rays (built once per window)."""
 
@@ -427,6 +444,36 @@ def render_forward(sigma, z, rays, noise=None, noise_std=0.0, seed=0, n_rays_dev
                                     float(noise_std), int(seed), _ptr(depth), _ptr(weights), _ptr(opacity), _ptr(variance),
                                     _stream()), "lnr_render_forward")
     return depth, weights, opacity, variance
+
+
+def render_forward_peak(sigma, z, rays, noise=None, noise_std=0.0, seed=0, n_rays_dev=None):
+    """-> (depth, opacity, variance, peak_z, peak_index int32): render_forward's depth, opacity and variance bit for bit, and per ray
+    the sample of maximal weight (torch.argmax's rules) with its depth - no [n, S] weights (lnr_render_forward_peak)."""
+    require_device(sigma, z, rays, noise)
+    sigma, z, rays = _f32c(sigma), _f32c(z), _f32c(rays)
+    n, s = z.shape
+    dev = z.device
+    depth = torch.zeros(n, device=dev); opacity = torch.zeros(n, device=dev); variance = torch.zeros(n, device=dev)
+    peak_z = torch.zeros(n, device=dev)
+    peak_index = torch.zeros(n, device=dev, dtype=torch.int32)
+    check(load().lnr_render_forward_peak(_ptr(sigma), _ptr(z), _ptr(rays), n, _ptr(n_rays_dev), s, _ptr(_f32c(noise)),
+                                         float(noise_std), int(seed), _ptr(depth), _ptr(opacity), _ptr(variance), _ptr(peak_z),
+                                         _ptr(peak_index), _stream()), "lnr_render_forward_peak")
+    return depth, opacity, variance, peak_z, peak_index
+
+
+def depth_colormap(values, table, multiplier=1.0, min_depth=1.0, max_depth=50.0):
+    """fp32 values of any shape -> uint8 [..., 4] RGBA (lnr_depth_colormap: the reference's save_depth per element).  table: uint8
+    [256,3] on the device."""
+    require_device(values, table)
+    values = _f32c(values)
+    assert table.dtype == torch.uint8 and table.is_contiguous() and tuple(table.shape) == (256, 3)
+    if not float(max_depth) > float(min_depth):
+        raise ValueError(f"depth_colormap: max_depth must exceed min_depth, got {min_depth!r} and {max_depth!r}")
+    rgba = torch.empty(tuple(values.shape) + (4,), device=values.device, dtype=torch.uint8)
+    check(load().lnr_depth_colormap(_ptr(values), values.numel(), float(multiplier), float(min_depth), float(max_depth), _ptr(table),
+                                    _ptr(rgba), _stream()), "lnr_depth_colormap")
+    return rgba
 
 
 class MeshLattice:
