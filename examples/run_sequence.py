@@ -1,0 +1,74 @@
+"""Run LiDAR SLAM on a folder of scans.
+
+    python examples/run_sequence.py <folder> [--gt poses_tum.txt] [--out ~/LonerSLAM/outputs] [--name run] [--ray-range 1 50]
+
+<folder> holds one `.npy` file per scan, [N,4] columns x, y, z, t (t: per-point time, local to the scan or global, seconds or
+nanoseconds), read in sorted name order, and `stamps.txt` with one scan time in seconds per line.  With --gt (a TUM file: ts x y z qx
+qy qz qw) every scan gets the ground-truth pose nearest in time, the world cube is computed from the ground truth and the estimated
+trajectory is scored against it; without it the cube comes from system.world_cube.trajectory_bounding_box.  The log directory holds
+the checkpoints, the four trajectory files and the configuration, as the analysis tools of this package expect them."""
+import argparse
+import glob
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from loner_amd.analysis.trajectory import ape, associate                     # noqa: E402
+from loner_amd.common.pose import Pose                                       # noqa: E402
+from loner_amd.common.pose_utils import build_poses_from_df, read_tum        # noqa: E402
+from loner_amd.common.sensors import build_scan_from_points                  # noqa: E402
+from loner_amd.common.settings import default_settings                       # noqa: E402
+from loner_amd.loner import Loner                                            # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("folder")
+    ap.add_argument("--gt")
+    ap.add_argument("--out", default="~/LonerSLAM/outputs")
+    ap.add_argument("--name", default=None)
+    ap.add_argument("--ray-range", type=float, nargs=2, default=(1.0, 50.0))
+    ap.add_argument("--log-level", default="STANDARD", choices=("DISABLED", "STANDARD", "VERBOSE"))
+    args = ap.parse_args()
+
+    files = sorted(glob.glob(os.path.join(args.folder, "*.npy")))
+    stamps = np.loadtxt(os.path.join(args.folder, "stamps.txt"), dtype=np.float64, ndmin=1)
+    if len(files) == 0 or len(files) != len(stamps):
+        raise SystemExit(f"{args.folder}: {len(files)} scans and {len(stamps)} stamps")
+
+    settings = default_settings(args.out, args.ray_range)
+    settings["system"]["single_threaded"] = True
+    settings["mapper"]["log_level"] = args.log_level
+    gt_poses, gt_of_scan = None, None
+    if args.gt:
+        rows = read_tum(args.gt)
+        gt_poses, _ = build_poses_from_df(rows, zero_origin=False)
+        scan_idx, gt_idx = associate(stamps, rows[:, 0], t_max_diff=np.inf)
+        gt_of_scan = dict(zip(scan_idx.tolist(), gt_idx.tolist()))
+
+    loner = Loner(settings)
+    loner.initialize(None, gt_poses, None, list(args.ray_range), None, args.folder, experiment_name=args.name,
+                     traj_bounding_box=None if args.gt else settings["system"]["world_cube"]["trajectory_bounding_box"])
+    loner.start()
+    fov = settings.system.lidar_fov
+    for k, (path, stamp) in enumerate(zip(files, stamps)):
+        points = np.load(path)
+        if points.ndim != 2 or points.shape[1] != 4:
+            raise SystemExit(f"{path}: expected [N,4] (x, y, z, t), got {points.shape}")
+        scan, _ = build_scan_from_points(points[:, :3].astype(np.float32), points[:, 3], float(stamp), fov=fov)
+        gt_pose = Pose(gt_poses[gt_of_scan[k]].clone()) if gt_of_scan is not None and k in gt_of_scan else None
+        loner.process_lidar(scan, gt_pose)
+    loner.stop()
+    log = loner.get_log_directory()
+    print(f"log directory: {log}")
+    if args.gt:
+        score = ape(os.path.join(log, "trajectory", "estimated_trajectory.txt"), args.gt)
+        print("APE (aligned, m): " + ", ".join(f"{k} {score[k]:.4f}" for k in ("rmse", "mean", "median", "std", "min", "max")))
+
+
+if __name__ == "__main__":
+    main()

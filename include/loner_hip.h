@@ -672,6 +672,43 @@ size_t lnr_sky_rays_workspace(void);
 int lnr_sky_rays(const float* ray_directions, int64_t n_points, const float* rotation, void* workspace, size_t workspace_bytes,
                  float* sky, int64_t sky_stride, int32_t* info_dev, void* stream);
 
+/* ---- scan ingestion (examples/run_loner.py:59-157) --------------------------------------------------------------------------- */
+#define LNR_SCAN_MAX_FOV_SEGMENTS 8
+#define LNR_SCAN_TIME_NONE 0          /* no per-point times: every time is the stamp */
+#define LNR_SCAN_TIME_GIVEN 1         /* point_times [n] fp32 */
+#define LNR_SCAN_TIME_RECOMPUTE 2     /* (i % 2048) / 2048 * 0.1 of the original index i */
+/* bits of info_dev[1]: the branches the timestamp heuristics took */
+#define LNR_SCAN_NANOSECONDS 1        /* max |t| > 1e7: scaled by 1e-9 */
+#define LNR_SCAN_NEGATIVE_START 2     /* t[first] < -0.001: t[first] subtracted */
+#define LNR_SCAN_LOCAL 4              /* t[first] < 1e-2: the stamp added */
+#define LNR_SCAN_GLOBAL 8             /* otherwise: rebased to the stamp */
+#define LNR_SCAN_CONSTANT 16          /* t[last] - t[first] < 1e-3 (or no times): every time is the stamp */
+#define LNR_SCAN_NO_TIMES 32          /* LNR_SCAN_TIME_NONE */
+
+/* build_scan_from_msg of run_loner.py (:59-157) on the device: xyz [n,3] fp32 (and point_times [n] fp32) become the time-ordered scan
+ * ray_directions [3,M], distances [M], timestamps [M] and order [M] int64, the original index of every output point.
+ *  1. FOV.  If fov_enabled: theta = atan2f(y, x) in degrees (times the fp32 constant 180/pi), plus 360 where negative; a point passes
+ *     if lo <= theta <= hi for any of the n_fov_segments <= LNR_SCAN_MAX_FOV_SEGMENTS segments (fov_segments host fp32 [n,2], degrees).
+ *  2. Range.  dist = sqrtf(fmaf(z, z, fmaf(y, y, x*x))), what torch.Tensor.norm(dim=1) gives on a CPU build; the order is fixed here,
+ *     not left to the compiler.  A point is kept if it passed the FOV test and dist > min_range; a NaN coordinate drops it.
+ *  3. Times, on the kept points in input order, every operation in fp32; stamp is the scan's time as fp32.  LNR_SCAN_TIME_NONE: every
+ *     time is stamp.  LNR_SCAN_TIME_RECOMPUTE: t = (i % 2048) / 2048 * 0.1 of the ORIGINAL index i; LNR_SCAN_TIME_GIVEN: t = point_times.
+ *     Then, with first / last the first / last kept point:  if max |t| > 1e7: t *= 1e-9;  if t[first] < -0.001: t -= t[first] (on
+ *     every call; the reference does it on its first call only, under its warn-once flag);  if t[first] < 1e-2: t += stamp, else
+ *     t = (t - t[first]) + stamp;  if t[last] - t[first] < 1e-3: every time is stamp.
+ *  4. Order.  Stable ascending sort by time, ties (-0 and +0 among them) keep input order; directions = xyz / dist (IEEE fp32
+ *     division); everything gathered by the sort.
+ * ray_directions is written with row stride M, so the caller allocates 3 n floats and views the first 3 M as [3,M].  workspace:
+ * lnr_scan_from_points_workspace(n) bytes (about 28 n; 0 = n out of range).  All launches go to `stream`, nothing waits on the host.
+ * info_dev int64 [8], written by the call: {M, LNR_SCAN_* bits, kept points whose input time is not finite, adjacent output times out
+ * of order (0 unless a time is not finite), digit passes the sort ran, first kept index, last kept index, 0}.  One host read of
+ * info_dev gives M; the caller treats M == 0 and a non-finite time as errors. */
+size_t lnr_scan_from_points_workspace(int64_t n_points);
+int lnr_scan_from_points(const float* xyz, const float* point_times /*nullable*/, int64_t n_points, int32_t time_mode, float stamp,
+                         int32_t fov_enabled, const float* fov_segments /*host, nullable*/, int32_t n_fov_segments, float min_range,
+                         void* workspace, size_t workspace_bytes, float* ray_directions, float* distances, float* timestamps,
+                         int64_t* order, int64_t* info_dev, void* stream);
+
 /* ---- loss ------------------------------------------------------------------------------------------ */
 /* get_weights_gt (losses.py:29-51); eps_ray [n] per-ray or NULL -> eps_scalar. */
 int lnr_weights_gt(const float* s /*[n,S] metres*/, const float* g /*[n] metres*/, const float* eps_ray,

@@ -137,3 +137,62 @@ def build_poses_from_df(df, zero_origin=False):
         start_inv = torch.vstack((start_inv, torch.tensor([0, 0, 0, 1.0], dtype=torch.float64)))
         poses = start_inv.unsqueeze(0) @ poses
     return poses.float(), ts
+
+
+def matrix_to_quaternion(R: torch.Tensor) -> torch.Tensor:
+    """[n,3,3] -> [n,4] unit quaternions (w, x, y, z) with w >= 0, each from the largest of its four candidate components (the
+    well-conditioned branch), in the matrices' type"""
+    m = R.reshape(-1, 3, 3)
+    t = m[:, 0, 0] + m[:, 1, 1] + m[:, 2, 2]
+    cand = torch.stack([1 + t, 1 + 2 * m[:, 0, 0] - t, 1 + 2 * m[:, 1, 1] - t, 1 + 2 * m[:, 2, 2] - t], dim=1)
+    rows = torch.stack([
+        torch.stack([cand[:, 0], m[:, 2, 1] - m[:, 1, 2], m[:, 0, 2] - m[:, 2, 0], m[:, 1, 0] - m[:, 0, 1]], dim=1),
+        torch.stack([m[:, 2, 1] - m[:, 1, 2], cand[:, 1], m[:, 0, 1] + m[:, 1, 0], m[:, 0, 2] + m[:, 2, 0]], dim=1),
+        torch.stack([m[:, 0, 2] - m[:, 2, 0], m[:, 0, 1] + m[:, 1, 0], cand[:, 2], m[:, 1, 2] + m[:, 2, 1]], dim=1),
+        torch.stack([m[:, 1, 0] - m[:, 0, 1], m[:, 0, 2] + m[:, 2, 0], m[:, 1, 2] + m[:, 2, 1], cand[:, 3]], dim=1)], dim=1)
+    q = rows[torch.arange(m.shape[0]), torch.argmax(cand, dim=1)]
+    q = q / torch.linalg.vector_norm(q, dim=1, keepdim=True)
+    return torch.where(q[:, :1] < 0, -q, q)
+
+
+def dump_trajectory_to_tum(transformation_matrices: torch.Tensor, timestamps: torch.Tensor, output_file: str) -> None:
+    """[n,4,4] poses and [n] stamps -> a TUM file: one row `ts x y z qx qy qz qw` per pose, %.10f, space separated
+    (pose_utils.py:308-318)."""
+    T = transformation_matrices.detach().cpu().reshape(-1, 4, 4)
+    quat = matrix_to_quaternion(T[:, :3, :3])
+    rows = torch.hstack([timestamps.detach().cpu().reshape(-1, 1).to(T.dtype), T[:, :3, 3], quat[:, 1:4], quat[:, 0:1]])
+    np.savetxt(output_file, rows.numpy(), delimiter=" ", fmt="%.10f")
+
+
+def compute_world_cube(camera_to_lidar, intrinsic_mats, image_sizes, lidar_poses, ray_range, padding=0.1, traj_bounding_box=None) -> WorldCube:
+    """The cube every ray of the run fits in (pose_utils.py:159-260), lidar only: the axis-aligned box around the sensor positions and,
+    for every pose, the eight corners (+-d, +-d, +-d) of the sensor's reach d = ray_range[1] in the sensor's frame.  shift is minus
+    the box's centre; scale_factor is the box's diagonal / (2 sqrt 3) (the half edge of the cube with that diagonal), widened by
+    `padding`.  lidar_poses [n,4,4] are taken relative to the first (poses @ inv(poses[0]), as the reference writes it); without
+    poses, traj_bounding_box {'x': [lo, hi], 'y': ..., 'z': ...} gives eight identity-rotation poses at its corners.  A
+    camera_to_lidar raises: the colour path is not implemented here."""
+    if not 0 <= padding < 1:
+        raise ValueError(f"compute_world_cube: padding must lie in [0, 1), got {padding}")
+    if camera_to_lidar is not None:
+        raise NotImplementedError("compute_world_cube: the camera branch (view frustums) is not implemented; pass camera_to_lidar=None")
+    if lidar_poses is None and traj_bounding_box is None:
+        raise ValueError("compute_world_cube: lidar_poses or traj_bounding_box is needed")
+    if lidar_poses is None:
+        print("Computing world cube using supplied trajectory bounding box")
+        axes = [torch.tensor([float(v) for v in traj_bounding_box[a]]) for a in ("x", "y", "z")]
+        corners = torch.stack(torch.meshgrid(axes, indexing="ij"), dim=-1).reshape(-1, 3)
+        poses = torch.eye(4).tile((8, 1, 1))
+        poses[:, :3, 3] = corners
+    else:
+        print("Computing world cube with groundtruth poses")
+        poses = torch.as_tensor(lidar_poses).float()
+        poses = poses @ torch.linalg.inv(poses[0])
+    reach = float(ray_range[1])
+    signs = torch.tensor([[sx, sy, sz, 1.0] for sz in (-1, 1) for sx in (-1, 1) for sy in (-1, 1)])
+    signs[:, :3] *= reach
+    corners = (poses[:, :3, :] @ signs.T).transpose(1, 2).reshape(-1, 3)
+    points = torch.cat([corners, poses[:, :3, 3]])
+    lo, hi = points.min(dim=0)[0], points.max(dim=0)[0]
+    origin = lo + (hi - lo) / 2
+    scale_factor = (torch.linalg.norm(hi - lo) / (2 * torch.sqrt(torch.Tensor([3])))) * (1 + padding)
+    return WorldCube(scale_factor, -origin)

@@ -1,6 +1,8 @@
-"""LidarScan: the keyframe point buffer (SoA), mirroring src/common/sensors.py:57-232."""
+"""LidarScan: the keyframe point buffer (SoA), mirroring src/common/sensors.py:57-232, and build_scan_from_points, which makes one
+from a raw point array on the device (examples/run_loner.py:59-157)."""
 from typing import Tuple, Union
 
+import numpy as np
 import torch
 
 
@@ -106,3 +108,72 @@ class LidarScan:
     def get_sky_scan(self, distance: float) -> "LidarScan":
         sky = self.sky_rays
         return LidarScan(sky, torch.full_like(sky[0], float(distance)), torch.full_like(sky[0], float(self.timestamps[-1])))
+
+
+# the reference's warn-once switches (run_loner.py:55-56): each message is printed for the first scan that takes its branch
+_WARN_MOCOMP_ONCE = True
+_WARN_LIDAR_TIMES_ONCE = True
+
+
+def _on_device(a, device, dtype):
+    """`a` (tensor or array) as a contiguous tensor of `dtype` on `device`: cast on the side it lives on, uploaded once"""
+    t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+    return t.to(dtype).to(device).contiguous()
+
+
+def build_scan_from_points(xyz, point_times, stamp: float, fov=None, min_range: float = 0.3, recompute_timestamps: bool = False,
+                           device=None) -> Tuple[LidarScan, torch.Tensor]:
+    """A raw point array -> (LidarScan on the device, order): run_loner.py's build_scan_from_msg without ROS, on the GPU
+    (include/loner_hip.h, "scan ingestion", is the definition).
+
+    xyz [N,3] fp32; point_times [N] of any real dtype (cast to fp32), or None; stamp the scan's time in seconds; fov None or an
+    object with `enabled` and `range`, a list of at most 8 [lo, hi] degree segments.  Host inputs are uploaded once, device inputs
+    are used in place (device: where to work; default the inputs' device, or the current GPU for host inputs).  order int64 [M] is the
+    original index of every point of the scan, for carrying intensity or ring along.
+
+    Unlike the reference the negative-start correction applies on every call, ties in time keep input order, and a scan with no
+    point left or with a non-finite time on a kept point raises ValueError.  The scan is time-ordered: `scan.time_sorted` is True,
+    read from the same status words as the count."""
+    from .. import ops
+    global _WARN_MOCOMP_ONCE, _WARN_LIDAR_TIMES_ONCE
+    shape = tuple(xyz.shape)
+    if len(shape) != 2 or shape[1] != 3:
+        raise ValueError(f"build_scan_from_points: xyz [N,3], got {shape}")
+    if point_times is not None and tuple(point_times.shape) != (shape[0],):
+        raise ValueError(f"build_scan_from_points: point_times [{shape[0]}], got {tuple(point_times.shape)}")
+    segments = None
+    if fov is not None and fov.enabled:
+        segments = [(float(s[0]), float(s[1])) for s in fov.range]
+        if len(segments) > 8:
+            raise ValueError(f"build_scan_from_points: {len(segments)} FOV segments, at most 8")
+    if device is None:
+        device = xyz.device if torch.is_tensor(xyz) and xyz.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    xyz_d = _on_device(xyz, device, torch.float32)
+    times_d = None if point_times is None else _on_device(point_times, device, torch.float32)
+    dirs, dist, times, order, info = ops.scan_from_points(xyz_d, times_d, stamp, segments, min_range, recompute_timestamps)
+    m, flags, nonfinite, unsorted = info[:4]
+    if m == 0:
+        raise ValueError(f"build_scan_from_points: none of the {shape[0]} points passed the FOV and range tests")
+    if nonfinite:
+        raise ValueError(f"build_scan_from_points: {nonfinite} kept points have a non-finite time")
+    from .. import hip
+    if flags & hip.SCAN_NO_TIMES:
+        if _WARN_MOCOMP_ONCE:
+            print("Warning: LiDAR Data has No Associated Timestamps. Motion compensation is useless.")
+            _WARN_MOCOMP_ONCE = False
+    else:
+        if _WARN_LIDAR_TIMES_ONCE:
+            if flags & hip.SCAN_NANOSECONDS:
+                print("Timestamps look to be in nanoseconds. Scaling")
+            if flags & hip.SCAN_NEGATIVE_START:
+                print("Timestamps negative (velodyne?). Correcting")
+            print("Assuming LiDAR timestamps within a scan are local, and start at 0" if flags & hip.SCAN_LOCAL
+                  else "Assuming lidar timestamps within a scan are global.")
+            _WARN_LIDAR_TIMES_ONCE = False
+        if flags & hip.SCAN_CONSTANT and _WARN_MOCOMP_ONCE:
+            print("Warning: Timestamps in LiDAR data aren't unique. Motion compensation is useless")
+            _WARN_MOCOMP_ONCE = False
+    scan = LidarScan(dirs, dist, times)
+    scan.time_sorted = unsorted == 0
+    scan.ingest_flags = flags
+    return scan, order

@@ -137,3 +137,40 @@ def default_tracking_settings(log_directory="/tmp/loner_amd_logs") -> Settings:
     lidar-only run."""
     return Settings({"tracker": default_tracker_settings(log_directory), "calibration": {"lidar_to_camera": None},
                      "system": {"lidar_only": True}})
+
+
+def default_keyframe_manager_settings() -> dict:
+    """= mapper.keyframe_manager of cfg/defaults.yaml:46-60"""
+    return {
+        "keyframe_selection": {"strategy": "TEMPORAL", "temporal": {"time_diff_seconds": 3},
+                               "motion": {"translation_threshold_m": 0.5, "rotation_threshold_deg": 22.5}},
+        "window_selection": {"strategy": "HYBRID", "hybrid_settings": {"num_recent_frames": 1}, "window_size": 8},
+    }
+
+
+def default_settings(log_dir_prefix="~/LonerSLAM/outputs/", ray_range=(1, 50)) -> Settings:
+    """The whole tree Loner reads, with the values of cfg/defaults.yaml: system, mapper (with keyframe_manager and optimizer),
+    tracker, calibration and debug.flags.  The per-run keys (log_directory, experiment_name, the debug blocks of mapper and tracker)
+    are filled in by Loner.start()."""
+    optimizer = dict(default_optimizer_settings(ray_range))
+    tracker = dict(default_tracker_settings())
+    for block in (optimizer, tracker):
+        for key in ("debug", "log_directory"):
+            block.pop(key)
+    synchronization = {"enabled": True, "min_buffer_size": 2, "max_time_delta": 3}
+    return Settings({
+        "calibration": {"lidar_to_camera": {"xyz": [0, 0, 0], "orientation": [0, 0, 0, 1]},
+                        "camera_intrinsic": {"k": None, "distortion": None, "new_k": None, "width": None, "height": None}},
+        "debug": {"global_enabled": True, "flags": {k: False for k in DEBUG_FLAGS}},
+        "mapper": {"device": 0, "data_prep_on_cpu": True, "log_level": "DISABLED", "keyframe_manager": default_keyframe_manager_settings(),
+                   "optimizer": optimizer},
+        "system": {"single_threaded": False, "log_dir_prefix": log_dir_prefix, "lidar_only": True, "sky_segmentation": False,
+                   "image_scale_factor": 0.5, "synchronization": dict(synchronization),
+                   "world_cube": {"compute_from_groundtruth": True,
+                                  "trajectory_bounding_box": {"x": [-10, 10], "y": [-10, 10], "z": [-10, 10]}},
+                   "lidar_fov": {"enabled": False, "range": [[0, 235], [305, 360]]},
+                   "lidar_timestamps_relative_to_start": True,
+                   "ros_names": {"camera": "stereo/frame_left", "lidar": "os_cloud_node/points", "camera_suffix": "image_raw",
+                                 "topic_prefix": ""}},
+        "tracker": dict(tracker, synchronization=dict(synchronization)),
+    })

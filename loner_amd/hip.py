@@ -23,6 +23,9 @@ KNN_MAX = 32                 # LNR_KNN_MAX
 ICP_RESULT = 64              # LNR_ICP_RESULT
 MOCOMP_CONSTS = 30           # LNR_MOCOMP_CONSTS
 SKY_MAX_RAYS = 65160         # LNR_SKY_MAX_RAYS
+SCAN_MAX_FOV_SEGMENTS = 8    # LNR_SCAN_MAX_FOV_SEGMENTS
+SCAN_TIME_NONE, SCAN_TIME_GIVEN, SCAN_TIME_RECOMPUTE = 0, 1, 2       # LNR_SCAN_TIME_*
+SCAN_NANOSECONDS, SCAN_NEGATIVE_START, SCAN_LOCAL, SCAN_GLOBAL, SCAN_CONSTANT, SCAN_NO_TIMES = 1, 2, 4, 8, 16, 32     # LNR_SCAN_* flag bits
 
 ENCODINGS = {"HashGrid": 0, "Grid": 0, "Frequency": 1}
 ACTIVATIONS = {"None": 0, "ReLU": 1, "Sine": 2, "LeakyReLU": 3, "Exponential": 4, "Sigmoid": 5,
@@ -140,6 +143,9 @@ _SIGNATURES = {
     "lnr_motion_compensate": (C.c_int, [P, P, P, C.c_int32, C.c_int64, C.c_double, C.c_double, C.POINTER(C.c_double), P]),
     "lnr_sky_rays_workspace": (C.c_size_t, []),
     "lnr_sky_rays": (C.c_int, [P, C.c_int64, P, P, C.c_size_t, P, C.c_int64, P, P]),
+    "lnr_scan_from_points_workspace": (C.c_size_t, [C.c_int64]),
+    "lnr_scan_from_points": (C.c_int, [P, P, C.c_int64, C.c_int32, C.c_float, C.c_int32, C.POINTER(C.c_float), C.c_int32, C.c_float,
+                                       P, C.c_size_t, P, P, P, P, P, P]),
     "lnr_points_grad_to_rays": (C.c_int, [P, P, C.c_int32, P, C.c_int32, P, P]),
     "lnr_weights_gt": (C.c_int, [P, P, P, C.c_float, C.c_int32, C.c_int32, C.c_int32, P, P]),
     "lnr_logits_grad": (C.c_int, [P, P, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, P, P]),

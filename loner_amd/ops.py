@@ -904,6 +904,52 @@ def trajectory_transform(points, timestamps, trajectory, min_range):
     return out, info
 
 
+# ---------------------------------------------------------------- scan ingestion
+_scan_ws = {}
+
+
+def scan_from_points(xyz, point_times, stamp, fov_segments=None, min_range=0.3, recompute_timestamps=False):
+    """build_scan_from_msg on the device (include/loner_hip.h: lnr_scan_from_points).  xyz [n,3] fp32 and point_times ([n] fp32, or
+    None) on the device; fov_segments None (FOV test off) or a list of at most 8 (lo, hi) degree pairs -> (ray_directions [3,M],
+    distances [M], timestamps [M], order [M] int64, info): the time-ordered scan, the original index of its points, and the call's
+    eight status words as Python ints.  One device -> host read (info); M == 0 and non-finite times are the caller's to refuse."""
+    require_device(xyz, point_times)
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.dtype != torch.float32:
+        raise ValueError(f"scan_from_points: xyz float32 [n,3], got {tuple(xyz.shape)} {xyz.dtype}")
+    n = xyz.shape[0]
+    if point_times is not None and (point_times.shape != (n,) or point_times.dtype != torch.float32):
+        raise ValueError(f"scan_from_points: point_times float32 [{n}], got {tuple(point_times.shape)} {point_times.dtype}")
+    segs = [] if fov_segments is None else [(float(lo), float(hi)) for lo, hi in fov_segments]
+    if len(segs) > hip.SCAN_MAX_FOV_SEGMENTS:
+        raise ValueError(f"scan_from_points: {len(segs)} FOV segments, at most {hip.SCAN_MAX_FOV_SEGMENTS}")
+    stamp, min_range = float(stamp), float(min_range)
+    if not math.isfinite(stamp) or math.isnan(min_range):
+        raise ValueError(f"scan_from_points: stamp must be finite and min_range a number, got {stamp!r} and {min_range!r}")
+    mode = hip.SCAN_TIME_NONE if point_times is None else hip.SCAN_TIME_RECOMPUTE if recompute_timestamps else hip.SCAN_TIME_GIVEN
+    lib = load()
+    dev = xyz.device
+    need = int(lib.lnr_scan_from_points_workspace(n))
+    if need == 0:
+        raise RuntimeError(f"scan_from_points: {n} points, the limit per call is 2^31 - 4096")
+    ws = _scan_ws.get(str(dev))
+    if ws is None or ws.numel() < need:
+        _scan_ws.pop(str(dev), None)
+        ws = _scan_ws[str(dev)] = torch.empty(need, device=dev, dtype=torch.uint8)
+    dirs = torch.empty(3 * n, device=dev, dtype=torch.float32)
+    dist = torch.empty(n, device=dev, dtype=torch.float32)
+    times = torch.empty(n, device=dev, dtype=torch.float32)
+    order = torch.empty(n, device=dev, dtype=torch.int64)
+    info = torch.empty(8, device=dev, dtype=torch.int64)
+    flat = (C.c_float * max(2 * len(segs), 1))(*[v for s in segs for v in s])
+    times_in = None if mode != hip.SCAN_TIME_GIVEN else point_times.contiguous()
+    check(lib.lnr_scan_from_points(_ptr(xyz.contiguous()), _ptr(times_in), n, mode, stamp, int(fov_segments is not None), flat, len(segs),
+                                   min_range, _ptr(ws), need, _ptr(dirs), _ptr(dist), _ptr(times), _ptr(order), _ptr(info), _stream()),
+          "lnr_scan_from_points")
+    info = [int(v) for v in info.cpu()]
+    m = info[0]
+    return dirs[:3 * m].view(3, m), dist[:m], times[:m], order[:m], info
+
+
 # ---------------------------------------------------------------- tracking
 def _scan_soa(directions, distances, what):
     require_device(directions, distances)
