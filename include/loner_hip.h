@@ -636,6 +636,53 @@ int lnr_cloud_trajectory_transform(const double* points, const double* timestamp
                                    int64_t n_poses, double min_range, void* workspace, size_t workspace_bytes, double* out,
                                    int64_t* info_dev, void* stream);
 
+/* ---- mesh tools (what a user of open3d's TriangleMesh calls between Mesher.get_mesh and a score or a viewer) -------------------- */
+/* vertices fp64 [n_vertices,3], triangles int32 [n_triangles,3]; n_vertices <= 2^31 - 1 and 3 n_triangles <= 2^31 - 4096 (the sort's
+ * limit).  Every fp64 expression rounds operation by operation (no fma), square roots and divides are IEEE; no float is added by an
+ * atomic, so every output is a function of the mesh and two runs give the same bits.  Each entry writes info_dev int64 [4] =
+ * {status, a, b, 0} (a and b as stated per entry); status bit 1: a vertex index lies outside [0, n_vertices), 2: a cluster id lies
+ * outside [0, n_clusters).  With a bit set the other outputs are not to be used; no such index is dereferenced.
+ * workspace: lnr_mesh_tools_workspace(n_vertices, n_triangles) bytes (about 88 per triangle and 4 per vertex; 0 = out of range).
+ * Only lnr_mesh_select uses the per-vertex part: the other entries also take the size for n_vertices = 0. */
+size_t lnr_mesh_tools_workspace(int64_t n_vertices, int64_t n_triangles);
+
+/* open3d's TriangleMesh::ClusterConnectedTriangles.  Two triangles are adjacent when they share an edge: the unordered pair (min, max)
+ * of two consecutive corners (0-1, 1-2, 2-0), also when the two are equal.  An edge of three or more triangles links them all; a shared
+ * vertex links nothing.  Clusters are the connected components, numbered by ascending smallest triangle index (open3d's breadth-first
+ * walk opens a cluster at the first unvisited triangle).  triangle_clusters int32 [n_triangles]; cluster_n_triangles int32
+ * [n_triangles], of which the first C entries are the clusters' triangle counts and the rest 0; info a = C.  Only the triangles are
+ * read: no vertex array is needed. */
+int lnr_mesh_connected_triangles(const int32_t* triangles, int64_t n_triangles, int64_t n_vertices, void* workspace,
+                                 size_t workspace_bytes, int32_t* triangle_clusters, int32_t* cluster_n_triangles, int64_t* info_dev,
+                                 void* stream);
+
+/* The third output of ClusterConnectedTriangles: cluster_area fp64 [n_clusters], for any labelling triangle_clusters int32
+ * [n_triangles] with values in [0, n_clusters).  A_t is lnr_mesh_sample_points' area.  The order of the sum: the areas of cluster c's
+ * triangles in ascending triangle index form a list; while the list is longer than one, every group of 64 consecutive entries (the last
+ * may be shorter) is replaced by its left-to-right sum ((a_0 + a_1) + a_2) + ...; the entry left is cluster_area[c].  A cluster
+ * without a triangle has area 0. */
+int lnr_mesh_cluster_area(const double* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles,
+                          const int32_t* triangle_clusters, int64_t n_clusters, void* workspace, size_t workspace_bytes,
+                          double* cluster_area, int64_t* info_dev, void* stream);
+
+/* The compaction behind open3d's RemoveTrianglesByMask, RemoveVerticesByMask, RemoveUnreferencedVertices, RemoveDegenerateTriangles and
+ * Crop.  triangle_keep uint8 [n_triangles] and vertex_keep uint8 [n_vertices] (either nullable: keep all; non-zero keeps).  A triangle
+ * survives when it is kept, its corners are in range and all three are kept vertices.  A vertex survives when it is kept and, with
+ * drop_unreferenced != 0, a surviving triangle uses it.  Survivors keep their relative order: a new index is the number of survivors
+ * before.  triangles_out int32 [n_triangles,3] receives the surviving triangles with their corners re-indexed, vertex_map int32
+ * [n_vertices] every vertex's new index or -1; info a = surviving vertices, b = surviving triangles. */
+int lnr_mesh_select(const int32_t* triangles, int64_t n_triangles, int64_t n_vertices, const uint8_t* triangle_keep,
+                    const uint8_t* vertex_keep, int32_t drop_unreferenced, void* workspace, size_t workspace_bytes, int32_t* triangles_out,
+                    int32_t* vertex_map, int64_t* info_dev, void* stream);
+
+/* open3d's TriangleMesh::ComputeVertexNormals as TriangleMesh.compute_vertex_normals (analysis/mesher.py) computes it, bit for bit.
+ * Face normal of triangle t: with a = v1 - v0 and b = v2 - v0, f_t = (a_y b_z - a_z b_y, a_z b_x - a_x b_z, a_x b_y - a_y b_x).
+ * Vertex i: s = 0.0, then s = s + f_t for every corner (k, t) with triangles[t][k] = i in ascending (k, t) order (numpy's three
+ * np.add.at passes); norm = sqrt((s_x s_x + s_y s_y) + s_z s_z); normals[i] = s / norm, or s / 1.0 where norm > 0 does not hold.  A
+ * vertex without a triangle gets zeros.  normals fp64 [n_vertices,3]. */
+int lnr_mesh_vertex_normals(const double* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles, void* workspace,
+                            size_t workspace_bytes, double* normals, int64_t* info_dev, void* stream);
+
 /* ---- tracking (src/common/frame.py:104-145; src/common/sensors.py:176-232; src/tracking/tracker.py:257-297) ----------------- */
 #define LNR_MOCOMP_CONSTS 30      /* fp64 entries of lnr_motion_compensate's consts */
 #define LNR_SKY_MAX_RAYS 65160    /* 181 x 360: the row stride lnr_sky_rays' output needs */

@@ -33,10 +33,15 @@ def mesh_to_point_cloud(mesh_or_ply_path, resolution, number_of_points=50_000_00
 
 
 def evaluate_mesh(mesh, gt_cloud, output_dir, f_score_threshold=0.1, voxel_size=0.05, resolution=None, number_of_points=50_000_000,
-                  seed=0, **compare_kwargs):
+                  seed=0, min_component_triangles=None, **compare_kwargs):
     """Accuracy, completion and F-score of a mesh (a TriangleMesh or a .ply path) against the PointCloud gt_cloud: the mesh is sampled
     (mesh_to_point_cloud at `resolution`, default voxel_size, with its number_of_points and seed) and scored by compare_point_clouds,
-    whose statistics are returned."""
+    whose statistics are returned.  min_component_triangles = k: a copy of the mesh without its connected components of fewer than k
+    triangles (TriangleMesh.remove_small_components) is scored; the caller's mesh and file stay as they are."""
+    if min_component_triangles is not None:
+        given = TriangleMesh.read_ply(mesh) if isinstance(mesh, (str, os.PathLike)) else mesh
+        mesh = TriangleMesh(given.vertices, given.triangles)
+        mesh.remove_small_components(min_triangles=min_component_triangles, device=gt_cloud.points.device)
     cloud = mesh_to_point_cloud(mesh, voxel_size if resolution is None else resolution, number_of_points, seed,
                                 device=gt_cloud.points.device)
     return compare_point_clouds(cloud, gt_cloud, output_dir, f_score_threshold, voxel_size, **compare_kwargs)

@@ -37,6 +37,22 @@ def build_lidar_scan(lidar_intrinsics, device=0):
     return LidarScan(xyz.T, torch.ones_like(x).flatten(), torch.zeros_like(x).flatten()).to(device)
 
 
+def select_components(sizes, min_triangles=None, keep_largest=None, areas=None, min_area=None):
+    """The clusters TriangleMesh.remove_small_components keeps, a bool array [C], from their triangle counts (and areas)."""
+    sizes = np.asarray(sizes, dtype=np.int64)
+    keep = np.ones(sizes.shape[0], dtype=bool)
+    if min_triangles is not None:
+        keep &= sizes >= int(min_triangles)
+    if min_area is not None:
+        keep &= np.asarray(areas, dtype=np.float64) >= float(min_area)
+    if keep_largest is not None:
+        order = np.argsort(-sizes, kind="stable")               # most triangles first; a tie goes to the lower cluster id
+        order = order[keep[order]][:int(keep_largest)]
+        keep = np.zeros_like(keep)
+        keep[order] = True
+    return keep
+
+
 class TriangleMesh:
     """vertices float64 [V,3] (world frame, metres), triangles int32 [F,3]; what the reference's script uses of open3d's mesh."""
 
@@ -48,8 +64,13 @@ class TriangleMesh:
     def has_vertex_normals(self):
         return self.vertex_normals.shape[0] == self.vertices.shape[0] and self.vertices.shape[0] > 0
 
-    def compute_vertex_normals(self):
-        """Area-weighted sum of the adjacent triangles' normals, normalised (triangles face lower weights: out of the surface)."""
+    def compute_vertex_normals(self, device=None):
+        """Area-weighted sum of the adjacent triangles' normals, normalised (triangles face lower weights: out of the surface).
+        device given: the same bytes from the device (include/loner_hip.h: lnr_mesh_vertex_normals); None: numpy on the host."""
+        if device is not None:
+            v, t = self._device_arrays(device)
+            self.vertex_normals = ops.mesh_vertex_normals(v, t).cpu().numpy()
+            return self
         v, t = self.vertices, self.triangles.astype(np.int64)
         fn = np.cross(v[t[:, 1]] - v[t[:, 0]], v[t[:, 2]] - v[t[:, 0]])
         n = np.zeros_like(v)
@@ -63,6 +84,85 @@ class TriangleMesh:
         from .lidar_map import _device
         dev = _device(device)
         return torch.tensor(self.vertices, device=dev), torch.tensor(self.triangles, device=dev)
+
+    # ------------------------------------------------------------ clean-up (include/loner_hip.h, "mesh tools")
+    def cluster_connected_triangles(self, device=None):
+        """open3d's cluster_connected_triangles: (triangle_clusters int32 [F], cluster_n_triangles int32 [C], cluster_area float64 [C])
+        as numpy arrays.  Triangles sharing an edge are connected; clusters are numbered by their smallest triangle."""
+        v, t = self._device_arrays(device)
+        clusters, sizes = ops.mesh_connected_triangles(t, v.shape[0])
+        area = ops.mesh_cluster_area(v, t, clusters, sizes.shape[0])
+        return clusters.cpu().numpy(), sizes.cpu().numpy(), area.cpu().numpy()
+
+    def _mask(self, mask, n, what):
+        m = np.asarray(mask)
+        if m.shape != (n,) or not (m.dtype == np.bool_ or np.issubdtype(m.dtype, np.integer)):
+            raise ValueError(f"{what}: a bool mask of shape ({n},), got {m.dtype} {m.shape}")
+        return m.astype(bool)
+
+    def _select(self, triangle_keep=None, vertex_keep=None, drop_unreferenced=False, device=None):
+        """lnr_mesh_select applied in place: the surviving triangles re-indexed, vertices and normals compacted in their order"""
+        from .lidar_map import _device
+        dev = _device(device)
+        up = lambda m: None if m is None else torch.from_numpy(np.ascontiguousarray(m, dtype=np.uint8)).to(dev)
+        tris, vmap, n_v = ops.mesh_select(torch.from_numpy(self.triangles).to(dev), self.vertices.shape[0], up(triangle_keep),
+                                          up(vertex_keep), drop_unreferenced)
+        kept = vmap.cpu().numpy() >= 0
+        assert int(kept.sum()) == n_v
+        normals = self.has_vertex_normals()
+        self.triangles = np.ascontiguousarray(tris.cpu().numpy())
+        if normals:
+            self.vertex_normals = np.ascontiguousarray(self.vertex_normals[kept])
+        self.vertices = np.ascontiguousarray(self.vertices[kept])
+        return self
+
+    def remove_triangles_by_mask(self, mask, device=None):
+        """open3d's remove_triangles_by_mask: drops the triangles whose mask entry is set.  In place; returns self."""
+        return self._select(triangle_keep=~self._mask(mask, self.triangles.shape[0], "remove_triangles_by_mask"), device=device)
+
+    def remove_vertices_by_mask(self, mask, device=None):
+        """open3d's remove_vertices_by_mask: drops the vertices whose mask entry is set and the triangles that use one.  In place."""
+        return self._select(vertex_keep=~self._mask(mask, self.vertices.shape[0], "remove_vertices_by_mask"), device=device)
+
+    def remove_unreferenced_vertices(self, device=None):
+        """open3d's remove_unreferenced_vertices: drops the vertices no triangle uses.  In place; returns self."""
+        return self._select(drop_unreferenced=True, device=device)
+
+    def remove_degenerate_triangles(self, device=None):
+        """open3d's remove_degenerate_triangles: drops the triangles with a repeated vertex index.  In place; returns self."""
+        t = self.triangles
+        return self._select(triangle_keep=(t[:, 0] != t[:, 1]) & (t[:, 1] != t[:, 2]) & (t[:, 2] != t[:, 0]), device=device)
+
+    def crop(self, min_bound, max_bound, device=None):
+        """open3d's crop with an axis-aligned box: a new mesh of the vertices inside the closed box [min_bound, max_bound] and the
+        triangles whose three vertices are inside."""
+        lo, hi = np.asarray(min_bound, dtype=np.float64), np.asarray(max_bound, dtype=np.float64)
+        if lo.shape != (3,) or hi.shape != (3,) or not (lo <= hi).all():
+            raise ValueError(f"crop: min_bound <= max_bound, three numbers each, got {min_bound!r} and {max_bound!r}")
+        out = TriangleMesh(self.vertices, self.triangles)
+        out.vertex_normals = self.vertex_normals.copy()
+        return out._select(vertex_keep=((self.vertices >= lo) & (self.vertices <= hi)).all(1), device=device)
+
+    def remove_small_components(self, min_triangles=None, min_area=None, keep_largest=None, device=None):
+        """Drops the connected components (cluster_connected_triangles) with fewer than min_triangles triangles or less than min_area
+        area, then, with keep_largest = k, all but the k remaining ones with the most triangles (ties: the lower cluster id), and the
+        vertices left without a triangle.  In place; returns the number of triangles removed."""
+        if min_triangles is None and min_area is None and keep_largest is None:
+            raise ValueError("remove_small_components: give min_triangles, min_area or keep_largest")
+        if min_triangles is not None and (int(min_triangles) != min_triangles or min_triangles < 0):
+            raise ValueError(f"remove_small_components: min_triangles must be an integer >= 0, got {min_triangles!r}")
+        if min_area is not None and not float(min_area) >= 0.0:
+            raise ValueError(f"remove_small_components: min_area must be >= 0, got {min_area!r}")
+        if keep_largest is not None and (int(keep_largest) != keep_largest or keep_largest < 1):
+            raise ValueError(f"remove_small_components: keep_largest must be an integer >= 1, got {keep_largest!r}")
+        v, t = self._device_arrays(device)
+        clusters, sizes = ops.mesh_connected_triangles(t, v.shape[0])
+        keep = select_components(sizes.cpu().numpy(), min_triangles, keep_largest,
+                                 ops.mesh_cluster_area(v, t, clusters, sizes.shape[0]).cpu().numpy() if min_area is not None else None,
+                                 min_area)
+        before = self.triangles.shape[0]
+        self._select(triangle_keep=keep[clusters.cpu().numpy()], drop_unreferenced=True, device=device)
+        return before - self.triangles.shape[0]
 
     def sample_points_uniformly(self, number_of_points, seed=0, device=None, return_triangles=False):
         """open3d's sample_points_uniformly on the device (include/loner_hip.h: lnr_mesh_sample_points): a PointCloud of
@@ -183,8 +283,12 @@ class Mesher(object):
         volume = results.view(ny, nx, nz).permute(1, 0, 2).contiguous()
         return volume, grid["xyz"]
 
-    def get_mesh(self, device, ray_sampler, skip_step=15, var_threshold=None):
-        """TriangleMesh in world coordinates (metres), or None when no surface crosses level_set (mesher.py:103-225)."""
+    def get_mesh(self, device, ray_sampler, skip_step=15, var_threshold=None, min_component_triangles=None):
+        """TriangleMesh in world coordinates (metres), or None when no surface crosses level_set (mesher.py:103-225).
+        min_component_triangles = k: connected components of fewer than k triangles are dropped on the device before the download
+        (the mesh get_mesh() followed by remove_small_components(min_triangles=k) gives)."""
+        if min_component_triangles is not None and (int(min_component_triangles) != min_component_triangles or min_component_triangles < 0):
+            raise ValueError(f"get_mesh: min_component_triangles must be an integer >= 0, got {min_component_triangles!r}")
         with torch.no_grad():
             volume, xyz = self.get_volume(device, ray_sampler, skip_step, var_threshold)
             spacing = (xyz[0][2] - xyz[0][1], xyz[1][2] - xyz[1][1], xyz[2][2] - xyz[2][1])
@@ -192,6 +296,11 @@ class Mesher(object):
             if faces.shape[0] == 0:
                 print('marching_cubes error. Possibly no surface extracted from the level set.')
                 return None
+            if min_component_triangles is not None:
+                clusters, sizes = ops.mesh_connected_triangles(faces, verts.shape[0])
+                faces, vertex_map, _ = ops.mesh_select(faces, verts.shape[0], triangle_keep=(sizes >= int(min_component_triangles))[clusters.long()],
+                                                       drop_unreferenced=True)
+                verts = verts[vertex_map >= 0]
             # convert back to world coordinates (mesher.py:214-219), in float64 as numpy does it there
             vertices = verts.cpu().numpy() + np.array([xyz[0][0], xyz[1][0], xyz[2][0]])
             vertices *= self.world_cube_scale_factor

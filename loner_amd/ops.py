@@ -856,6 +856,112 @@ def mesh_sample_points(vertices, triangles, n_points, seed=0, want_triangles=Fal
     return (points[:m], owner[:m]) if want_triangles else points[:m]
 
 
+# ---------------------------------------------------------------- mesh tools
+_MESH_TOOLS_STATUS = {1: "a vertex index is out of range", 2: "a cluster id is out of range"}
+
+
+def _mesh_triangles(triangles, what):
+    require_device(triangles)
+    if triangles.dim() != 2 or triangles.shape[1] != 3 or triangles.dtype != torch.int32:
+        raise ValueError(f"{what}: triangles int32 [F,3], got {tuple(triangles.shape)} {triangles.dtype}")
+    return triangles.contiguous()
+
+
+def _mesh_tools_workspace(what, n_vertices, n_triangles, device):
+    need = int(load().lnr_mesh_tools_workspace(int(n_vertices), int(n_triangles)))
+    if need == 0:
+        raise RuntimeError(f"{what}: {n_vertices} vertices and {n_triangles} triangles, the limits are 2^31 - 1 vertices and "
+                           "3 * triangles <= 2^31 - 4096")
+    return torch.empty(need, device=device, dtype=torch.uint8), need
+
+
+def _mesh_tools_info(what, info_dev):
+    """the one device -> host read of a mesh-tools call: (a, b) of its info words; RuntimeError on a status bit"""
+    host = info_dev.cpu()
+    status = int(host[0])
+    if status:
+        raise RuntimeError(f"{what}: " + ", ".join(m for b, m in _MESH_TOOLS_STATUS.items() if status & b))
+    return int(host[1]), int(host[2])
+
+
+def mesh_connected_triangles(triangles, n_vertices):
+    """open3d's cluster_connected_triangles without the areas (include/loner_hip.h: lnr_mesh_connected_triangles): triangles [F,3]
+    int32 on the device, indices in [0, n_vertices) -> (triangle_clusters int32 [F], cluster_n_triangles int32 [C]) on the device,
+    clusters numbered by their smallest triangle.  Raises RuntimeError on an index out of range.  One device -> host read (C)."""
+    tri = _mesh_triangles(triangles, "mesh_connected_triangles")
+    f, dev = tri.shape[0], tri.device
+    ws, need = _mesh_tools_workspace("mesh_connected_triangles", 0, f, dev)
+    if not 0 <= int(n_vertices) < 2 ** 31:
+        raise RuntimeError(f"mesh_connected_triangles: {n_vertices} vertices, the limit is 2^31 - 1")
+    clusters = torch.empty(f, device=dev, dtype=torch.int32)
+    sizes = torch.empty(f, device=dev, dtype=torch.int32)
+    info = torch.empty(4, device=dev, dtype=torch.int64)
+    check(load().lnr_mesh_connected_triangles(_ptr(tri), f, int(n_vertices), _ptr(ws), need, _ptr(clusters), _ptr(sizes), _ptr(info),
+                                              _stream()), "lnr_mesh_connected_triangles")
+    c, _ = _mesh_tools_info("mesh_connected_triangles", info)
+    return clusters, sizes[:c]
+
+
+def mesh_cluster_area(vertices, triangles, triangle_clusters, n_clusters):
+    """The summed triangle area of every cluster in a fixed order (include/loner_hip.h: lnr_mesh_cluster_area) -> fp64 [n_clusters]
+    on the device.  Raises RuntimeError on a vertex index or a cluster id out of range.  One device -> host read (the status)."""
+    v = _f64_points(vertices, "mesh_cluster_area")
+    tri = _mesh_triangles(triangles, "mesh_cluster_area")
+    require_device(triangle_clusters)
+    f, c, dev = tri.shape[0], int(n_clusters), tri.device
+    if triangle_clusters.dtype != torch.int32 or tuple(triangle_clusters.shape) != (f,) or not 0 <= c <= f:
+        raise ValueError(f"mesh_cluster_area: triangle_clusters int32 [{f}] and 0 <= n_clusters <= {f}, got "
+                         f"{tuple(triangle_clusters.shape)} {triangle_clusters.dtype} and {n_clusters!r}")
+    ws, need = _mesh_tools_workspace("mesh_cluster_area", 0, f, dev)
+    area = torch.empty(c, device=dev, dtype=torch.float64)
+    info = torch.empty(4, device=dev, dtype=torch.int64)
+    check(load().lnr_mesh_cluster_area(_ptr(v), v.shape[0], _ptr(tri), f, _ptr(triangle_clusters.contiguous()), c, _ptr(ws), need,
+                                       _ptr(area), _ptr(info), _stream()), "lnr_mesh_cluster_area")
+    _mesh_tools_info("mesh_cluster_area", info)
+    return area
+
+
+def _keep_mask(mask, n, what):
+    if mask is None:
+        return None
+    require_device(mask)
+    if mask.dtype not in (torch.bool, torch.uint8) or tuple(mask.shape) != (n,):
+        raise ValueError(f"mesh_select: {what} bool or uint8 [{n}], got {tuple(mask.shape)} {mask.dtype}")
+    return mask.to(torch.uint8).contiguous()
+
+
+def mesh_select(triangles, n_vertices, triangle_keep=None, vertex_keep=None, drop_unreferenced=False):
+    """The compaction behind the mesh filters (include/loner_hip.h: lnr_mesh_select): triangles [F,3] int32, optional keep masks
+    (bool or uint8) per triangle and per vertex -> (the surviving triangles [F',3] int32 re-indexed, vertex_map int32 [V] with the
+    new index or -1, the number of surviving vertices).  Raises RuntimeError on an index out of range.  One device -> host read."""
+    tri = _mesh_triangles(triangles, "mesh_select")
+    f, v, dev = tri.shape[0], int(n_vertices), tri.device
+    tk, vk = _keep_mask(triangle_keep, f, "triangle_keep"), _keep_mask(vertex_keep, v, "vertex_keep")
+    ws, need = _mesh_tools_workspace("mesh_select", v, f, dev)
+    out = torch.empty(f, 3, device=dev, dtype=torch.int32)
+    vmap = torch.empty(v, device=dev, dtype=torch.int32)
+    info = torch.empty(4, device=dev, dtype=torch.int64)
+    check(load().lnr_mesh_select(_ptr(tri), f, v, _ptr(tk), _ptr(vk), 1 if drop_unreferenced else 0, _ptr(ws), need, _ptr(out),
+                                 _ptr(vmap), _ptr(info), _stream()), "lnr_mesh_select")
+    n_v, n_f = _mesh_tools_info("mesh_select", info)
+    return out[:n_f], vmap, n_v
+
+
+def mesh_vertex_normals(vertices, triangles):
+    """TriangleMesh.compute_vertex_normals on the device, bit for bit (include/loner_hip.h: lnr_mesh_vertex_normals) -> fp64 [V,3].
+    Raises RuntimeError on an index out of range.  One device -> host read (the status)."""
+    v = _f64_points(vertices, "mesh_vertex_normals")
+    tri = _mesh_triangles(triangles, "mesh_vertex_normals")
+    f, dev = tri.shape[0], tri.device
+    ws, need = _mesh_tools_workspace("mesh_vertex_normals", 0, f, dev)
+    normals = torch.empty(v.shape[0], 3, device=dev, dtype=torch.float64)
+    info = torch.empty(4, device=dev, dtype=torch.int64)
+    check(load().lnr_mesh_vertex_normals(_ptr(v), v.shape[0], _ptr(tri), f, _ptr(ws), need, _ptr(normals), _ptr(info), _stream()),
+          "lnr_mesh_vertex_normals")
+    _mesh_tools_info("mesh_vertex_normals", info)
+    return normals
+
+
 class Trajectory:
     """A ground-truth trajectory on the device, in the form lnr_cloud_trajectory_transform takes: times [K] (strictly increasing),
     positions [K,3], rotations [K,3,3] and the rotation vectors log(R_k^T R_k+1) [K-1,3], all fp64 host arrays here."""
