@@ -683,6 +683,64 @@ int lnr_mesh_select(const int32_t* triangles, int64_t n_triangles, int64_t n_ver
 int lnr_mesh_vertex_normals(const double* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles, void* workspace,
                             size_t workspace_bytes, double* normals, int64_t* info_dev, void* stream);
 
+/* ---- mesh simplification and smoothing (open3d's SimplifyVertexClustering, RemoveDuplicatedTriangles and FilterSmooth*) ---------- */
+/* The conventions of "mesh tools": vertices fp64 [n_vertices,3], triangles int32 [n_triangles,3]; every fp64 expression rounds
+ * operation by operation (no fma), square roots and divides are IEEE; no float is added by an atomic, so every output is a function of
+ * the inputs only and two runs give the same bits.  Each entry writes info_dev int64 [4] = {status, a, b, 0} (a and b as stated per
+ * entry).  An index out of range sets a status bit and is never dereferenced; with a bit set the other outputs are not to be used.
+ * Where open3d leaves an order unspecified (it iterates unordered_sets), the order stated here is the definition.
+ * Limits: n_vertices <= 2^31 - 1 (lnr_mesh_vertex_clusters: 2^31 - 4096, the sort's limit) and 6 n_triangles <= 2^31 - 4096.
+ * workspace: lnr_mesh_filters_workspace(n_vertices, n_triangles) bytes (about 28 per vertex or 168 per triangle, whichever is more;
+ * 0 = out of range).  lnr_mesh_vertex_clusters uses the per-vertex part only (n_triangles = 0 suffices), lnr_mesh_unique_triangles and
+ * lnr_mesh_vertex_adjacency the per-triangle part only (n_vertices = 0 suffices); lnr_mesh_smooth takes none. */
+size_t lnr_mesh_filters_workspace(int64_t n_vertices, int64_t n_triangles);
+
+/* The vertex half of open3d's TriangleMesh::SimplifyVertexClustering(voxel_size, Average).  voxel_size finite and > 0.  lo_a = min_a -
+ * 0.5 v over the vertices; a vertex's voxel is floor((p_a - lo_a) / v) per axis; the key, the "voxel_size is too small" rule and the
+ * "key wider than 64 bits" rule are lnr_voxel_down_sample's.  Clusters are numbered by first occurrence (open3d's rule): cluster c is
+ * the c-th distinct voxel met when walking the vertices in index order.  vertex_cluster int32 [n_vertices]; cluster_vertices fp64
+ * [n_vertices,3], of which the first m rows are used: row c is the sum of the cluster's vertices in ascending vertex index, started
+ * at 0.0, divided by (double) count.  info a = m, b = the number of non-finite vertices; status bit 1: a non-finite vertex (nothing
+ * else is valid), 2: voxel_size too small, 4: key wider than 64 bits. */
+int lnr_mesh_vertex_clusters(const double* vertices, int64_t n_vertices, double voxel_size, void* workspace, size_t workspace_bytes,
+                             int32_t* vertex_cluster, double* cluster_vertices, int64_t* info_dev, void* stream);
+
+/* open3d's TriangleMesh::RemoveDuplicatedTriangles as a mask, and the triangle half of SimplifyVertexClustering.  vertex_map int32
+ * [n_vertices] (nullable: the identity, and n_mapped = n_vertices) with values in [0, n_mapped), n_mapped <= 2^31 - 1.  The three
+ * corners are mapped to (t0, t1, t2) and rotated cyclically by open3d's rule: with t0 <= t1, (t0, t1, t2) when t0 <= t2, else
+ * (t2, t0, t1); otherwise (t1, t2, t0) when t1 <= t2, else (t2, t0, t1).  The orientation is kept: a triangle and its mirror image
+ * are different classes.  canonical int32 [n_triangles,3] receives the rotated triple.  triangle_keep uint8 [n_triangles] is 1 for
+ * the triangle with the lowest index among those with the same canonical triple and 0 for the others; with drop_degenerate != 0 it is
+ * 1 only where, in addition, the three mapped indices are pairwise different.  Correct for every index below 2^31 - 1 (the triple is
+ * ordered by two stable sorts, not packed into one key).  info a = the number of ones in triangle_keep, b = the triangles whose mapped
+ * indices are not pairwise different (whatever drop_degenerate is); status bit 1: a corner lies outside [0, n_vertices) or a mapped
+ * value outside [0, n_mapped). */
+int lnr_mesh_unique_triangles(const int32_t* triangles, int64_t n_triangles, int64_t n_vertices, const int32_t* vertex_map,
+                              int64_t n_mapped, int32_t drop_degenerate, void* workspace, size_t workspace_bytes, int32_t* canonical,
+                              uint8_t* triangle_keep, int64_t* info_dev, void* stream);
+
+/* The adjacency list open3d's FilterSmooth* build, as a CSR: j is a neighbour of i when some triangle has both as consecutive corners
+ * (0-1, 1-2, 2-0, either direction).  A pair (i, i) from a repeated index is left out, on purpose: open3d makes such a vertex its own
+ * neighbour, which pins it with weight 1e12.  row_start int32 [n_vertices + 1] and neighbours int32 [6 n_triangles], of which
+ * row_start[n_vertices] entries are used: row i is neighbours[row_start[i] .. row_start[i + 1]), each distinct neighbour once, ascending.
+ * info a = row_start[n_vertices]; status bit 1: a corner lies outside [0, n_vertices) (that triangle contributes nothing). */
+int lnr_mesh_vertex_adjacency(const int32_t* triangles, int64_t n_triangles, int64_t n_vertices, void* workspace, size_t workspace_bytes,
+                              int32_t* row_start, int32_t* neighbours, int64_t* info_dev, void* stream);
+
+/* n_steps >= 0 smoothing steps over vertices [n_vertices,3] with the adjacency (row_start [n_vertices + 1], neighbours
+ * [n_neighbours]) of lnr_mesh_vertex_adjacency and scratch fp64 [n_vertices,3].  The steps ping-pong between the two arrays on the
+ * device with no host synchronisation, and the result always ends in vertices; n_steps = 0 leaves its bytes untouched.  Every step
+ * reads the positions p of the step before.  Step s (from 0) uses the factor f = lambda when s is even, mu when s is odd; both finite.
+ * kind 0 (open3d's FilterSmoothSimple; f unused): S = p_i, then S = S + p_j for the neighbours j of i in ascending order;
+ * out = S / (double)(1 + n_i).
+ * kind 1 (FilterSmoothLaplacian, weights by inverse distance; Taubin is 2 k steps with lambda > 0 > mu): W = 0.0 and S = 0.0, then
+ * per neighbour j in ascending order, with d = p_i - p_j: dist = sqrt((d_x d_x + d_y d_y) + d_z d_z), w = 1 / (dist + 1e-12),
+ * W = W + w, S_a = S_a + w * p_j,a; then out_a = p_i,a + f * (S_a / W - p_i,a).
+ * A vertex without neighbours keeps its position in both kinds (open3d divides 0 by 0 there).  info a = b = 0; status bit 1: a row
+ * outside 0 <= row_start[i] <= row_start[i + 1] <= n_neighbours or a neighbour outside [0, n_vertices); that vertex stays where it is. */
+int lnr_mesh_smooth(double* vertices, double* scratch, int64_t n_vertices, const int32_t* row_start, const int32_t* neighbours,
+                    int64_t n_neighbours, int32_t kind, int32_t n_steps, double lambda, double mu, int64_t* info_dev, void* stream);
+
 /* ---- tracking (src/common/frame.py:104-145; src/common/sensors.py:176-232; src/tracking/tracker.py:257-297) ----------------- */
 #define LNR_MOCOMP_CONSTS 30      /* fp64 entries of lnr_motion_compensate's consts */
 #define LNR_SKY_MAX_RAYS 65160    /* 181 x 360: the row stride lnr_sky_rays' output needs */

@@ -53,6 +53,20 @@ def select_components(sizes, min_triangles=None, keep_largest=None, areas=None, 
     return keep
 
 
+def _simplify_on_device(vertices, triangles, voxel_size):
+    """TriangleMesh.simplify_vertex_clustering on device tensors -> (vertices fp64 [m,3], triangles int32 [F',3])"""
+    cluster, means = ops.mesh_vertex_clusters(vertices, voxel_size)
+    canonical, keep, _, _ = ops.mesh_unique_triangles(triangles, vertices.shape[0], vertex_map=cluster, n_mapped=means.shape[0],
+                                                      drop_degenerate=True)
+    return means, ops.mesh_select(canonical, means.shape[0], triangle_keep=keep)[0]
+
+
+def _smooth_on_device(vertices, triangles, n_steps, kind="laplacian", lambda_filter=0.5, mu=-0.53):
+    """The TriangleMesh.filter_smooth_* calls on device tensors (the defaults: Taubin's factors) -> vertices fp64 [V,3]"""
+    row_start, neighbours = ops.mesh_vertex_adjacency(triangles, vertices.shape[0])
+    return ops.mesh_smooth(vertices, row_start, neighbours, n_steps, kind, lambda_filter, mu)
+
+
 class TriangleMesh:
     """vertices float64 [V,3] (world frame, metres), triangles int32 [F,3]; what the reference's script uses of open3d's mesh."""
 
@@ -163,6 +177,50 @@ class TriangleMesh:
         before = self.triangles.shape[0]
         self._select(triangle_keep=keep[clusters.cpu().numpy()], drop_unreferenced=True, device=device)
         return before - self.triangles.shape[0]
+
+    # ------------------------------------------------------------ simplification and smoothing (include/loner_hip.h)
+    def simplify_vertex_clustering(self, voxel_size, device=None):
+        """open3d's simplify_vertex_clustering with averaging: a new mesh whose vertices are the means of the vertices sharing a
+        voxel of edge voxel_size, in the order the voxels are first met, and whose triangles are the distinct non-degenerate ones
+        left after the merge, each rotated to open3d's canonical corner order, in the order of their first input triangle.  No
+        vertex normals: recompute them."""
+        s = float(voxel_size)
+        if not (np.isfinite(s) and s > 0):
+            raise ValueError(f"simplify_vertex_clustering: voxel_size must be finite and > 0, got {voxel_size!r}")
+        v, t = self._device_arrays(device)
+        v, t = _simplify_on_device(v, t, s)
+        return TriangleMesh(v.cpu().numpy(), t.cpu().numpy())
+
+    def remove_duplicated_triangles(self, device=None):
+        """open3d's remove_duplicated_triangles: of the triangles with the same corners in the same cyclic order the first stays;
+        order, corner order and vertex normals are kept, degenerate triangles are treated like any other.  In place; returns self."""
+        from .lidar_map import _device
+        t = torch.from_numpy(self.triangles).to(_device(device))
+        _, keep, _, _ = ops.mesh_unique_triangles(t, self.vertices.shape[0])
+        self.triangles = np.ascontiguousarray(self.triangles[keep.cpu().numpy().astype(bool)])
+        return self
+
+    def _smoothed(self, what, kind, number_of_iterations, steps_per_iteration, lambda_filter, mu, device):
+        if int(number_of_iterations) != number_of_iterations or number_of_iterations < 0:
+            raise ValueError(f"{what}: number_of_iterations must be an integer >= 0, got {number_of_iterations!r}")
+        v, t = self._device_arrays(device)
+        out = _smooth_on_device(v, t, steps_per_iteration * int(number_of_iterations), kind, lambda_filter, mu)
+        return TriangleMesh(out.cpu().numpy(), self.triangles)
+
+    def filter_smooth_simple(self, number_of_iterations=1, device=None):
+        """open3d's filter_smooth_simple: every vertex becomes the mean of itself and its neighbours, number_of_iterations times.
+        A new mesh with the same triangles and no vertex normals."""
+        return self._smoothed("filter_smooth_simple", "simple", number_of_iterations, 1, 0.0, None, device)
+
+    def filter_smooth_laplacian(self, number_of_iterations=1, lambda_filter=0.5, device=None):
+        """open3d's filter_smooth_laplacian (inverse-distance weights): v + lambda_filter * (weighted mean of the neighbours - v),
+        number_of_iterations times.  A new mesh with the same triangles and no vertex normals."""
+        return self._smoothed("filter_smooth_laplacian", "laplacian", number_of_iterations, 1, lambda_filter, None, device)
+
+    def filter_smooth_taubin(self, number_of_iterations=1, lambda_filter=0.5, mu=-0.53, device=None):
+        """open3d's filter_smooth_taubin: per iteration one Laplacian step with lambda_filter and one with mu, which keeps the
+        volume a plain Laplacian filter loses.  A new mesh with the same triangles and no vertex normals."""
+        return self._smoothed("filter_smooth_taubin", "laplacian", number_of_iterations, 2, lambda_filter, mu, device)
 
     def sample_points_uniformly(self, number_of_points, seed=0, device=None, return_triangles=False):
         """open3d's sample_points_uniformly on the device (include/loner_hip.h: lnr_mesh_sample_points): a PointCloud of
@@ -283,10 +341,18 @@ class Mesher(object):
         volume = results.view(ny, nx, nz).permute(1, 0, 2).contiguous()
         return volume, grid["xyz"]
 
-    def get_mesh(self, device, ray_sampler, skip_step=15, var_threshold=None, min_component_triangles=None):
+    def get_mesh(self, device, ray_sampler, skip_step=15, var_threshold=None, min_component_triangles=None, smooth_iterations=None,
+                 simplify_voxel_size=None):
         """TriangleMesh in world coordinates (metres), or None when no surface crosses level_set (mesher.py:103-225).
         min_component_triangles = k: connected components of fewer than k triangles are dropped on the device before the download
-        (the mesh get_mesh() followed by remove_small_components(min_triangles=k) gives)."""
+        (the mesh get_mesh() followed by remove_small_components(min_triangles=k) gives).
+        smooth_iterations = n, simplify_voxel_size = s (metres): after that filter the mesh is converted to metres, smoothed and
+        simplified on the device and downloaded once; the result is, bit for bit, get_mesh() followed by filter_smooth_taubin(n)
+        and simplify_vertex_clustering(s)."""
+        if smooth_iterations is not None and (int(smooth_iterations) != smooth_iterations or smooth_iterations < 0):
+            raise ValueError(f"get_mesh: smooth_iterations must be an integer >= 0, got {smooth_iterations!r}")
+        if simplify_voxel_size is not None and not (np.isfinite(float(simplify_voxel_size)) and float(simplify_voxel_size) > 0):
+            raise ValueError(f"get_mesh: simplify_voxel_size must be finite and > 0, got {simplify_voxel_size!r}")
         if min_component_triangles is not None and (int(min_component_triangles) != min_component_triangles or min_component_triangles < 0):
             raise ValueError(f"get_mesh: min_component_triangles must be an integer >= 0, got {min_component_triangles!r}")
         with torch.no_grad():
@@ -301,6 +367,16 @@ class Mesher(object):
                 faces, vertex_map, _ = ops.mesh_select(faces, verts.shape[0], triangle_keep=(sizes >= int(min_component_triangles))[clusters.long()],
                                                        drop_unreferenced=True)
                 verts = verts[vertex_map >= 0]
+            if smooth_iterations is not None or simplify_voxel_size is not None:
+                # the conversion below, on the device: the same three fp64 operations per coordinate in the same order
+                vertices = verts.to(torch.float64) + torch.tensor([xyz[0][0], xyz[1][0], xyz[2][0]], device=verts.device, dtype=torch.float64)
+                vertices *= torch.tensor(self.world_cube_scale_factor, device=verts.device).to(torch.float64)
+                vertices -= torch.tensor(self.world_cube_shift, device=verts.device).to(torch.float64)
+                if smooth_iterations is not None:
+                    vertices = _smooth_on_device(vertices, faces, 2 * int(smooth_iterations))
+                if simplify_voxel_size is not None:
+                    vertices, faces = _simplify_on_device(vertices, faces, float(simplify_voxel_size))
+                return TriangleMesh(vertices.cpu().numpy(), faces.cpu().numpy())
             # convert back to world coordinates (mesher.py:214-219), in float64 as numpy does it there
             vertices = verts.cpu().numpy() + np.array([xyz[0][0], xyz[1][0], xyz[2][0]])
             vertices *= self.world_cube_scale_factor

@@ -144,6 +144,11 @@ _SIGNATURES = {
     "lnr_mesh_cluster_area": (C.c_int, [P, C.c_int64, P, C.c_int64, P, C.c_int64, P, C.c_size_t, P, P, P]),
     "lnr_mesh_select": (C.c_int, [P, C.c_int64, C.c_int64, P, P, C.c_int32, P, C.c_size_t, P, P, P, P]),
     "lnr_mesh_vertex_normals": (C.c_int, [P, C.c_int64, P, C.c_int64, P, C.c_size_t, P, P, P]),
+    "lnr_mesh_filters_workspace": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "lnr_mesh_vertex_clusters": (C.c_int, [P, C.c_int64, C.c_double, P, C.c_size_t, P, P, P, P]),
+    "lnr_mesh_unique_triangles": (C.c_int, [P, C.c_int64, C.c_int64, P, C.c_int64, C.c_int32, P, C.c_size_t, P, P, P, P]),
+    "lnr_mesh_vertex_adjacency": (C.c_int, [P, C.c_int64, C.c_int64, P, C.c_size_t, P, P, P, P]),
+    "lnr_mesh_smooth": (C.c_int, [P, P, C.c_int64, P, P, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, P, P]),
     "lnr_frame_cloud": (C.c_int, [P, P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, P, P]),
     "lnr_motion_compensate": (C.c_int, [P, P, P, C.c_int32, C.c_int64, C.c_double, C.c_double, C.POINTER(C.c_double), P]),
     "lnr_sky_rays_workspace": (C.c_size_t, []),

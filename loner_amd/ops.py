@@ -875,12 +875,12 @@ def _mesh_tools_workspace(what, n_vertices, n_triangles, device):
     return torch.empty(need, device=device, dtype=torch.uint8), need
 
 
-def _mesh_tools_info(what, info_dev):
+def _mesh_tools_info(what, info_dev, messages=_MESH_TOOLS_STATUS):
     """the one device -> host read of a mesh-tools call: (a, b) of its info words; RuntimeError on a status bit"""
     host = info_dev.cpu()
     status = int(host[0])
     if status:
-        raise RuntimeError(f"{what}: " + ", ".join(m for b, m in _MESH_TOOLS_STATUS.items() if status & b))
+        raise RuntimeError(f"{what}: " + ", ".join(m for b, m in messages.items() if status & b))
     return int(host[1]), int(host[2])
 
 
@@ -960,6 +960,125 @@ def mesh_vertex_normals(vertices, triangles):
           "lnr_mesh_vertex_normals")
     _mesh_tools_info("mesh_vertex_normals", info)
     return normals
+
+
+_MESH_FILTERS_STATUS = {1: "an index is out of range"}
+
+
+def _mesh_filters_workspace(what, n_vertices, n_triangles, device):
+    need = int(load().lnr_mesh_filters_workspace(int(n_vertices), int(n_triangles)))
+    if need == 0:
+        raise RuntimeError(f"{what}: {n_vertices} vertices and {n_triangles} triangles, the limits are 2^31 - 4096 vertices and "
+                           "6 * triangles <= 2^31 - 4096")
+    return torch.empty(need, device=device, dtype=torch.uint8), need
+
+
+def _vertex_count(n_vertices, what):
+    v = int(n_vertices)
+    if v != n_vertices or not 0 <= v < 2 ** 31:
+        raise ValueError(f"{what}: n_vertices must be an integer in [0, 2^31 - 1], got {n_vertices!r}")
+    return v
+
+
+def mesh_vertex_clusters(vertices, voxel_size):
+    """The vertex half of open3d's simplify_vertex_clustering with averaging (include/loner_hip.h: lnr_mesh_vertex_clusters):
+    vertices [V,3] (fp64) -> (vertex_cluster int32 [V], cluster_vertices fp64 [m,3]) on the device, clusters numbered by first
+    occurrence.  Raises ValueError for a voxel_size that is not finite and > 0, RuntimeError on a non-finite vertex, a voxel_size
+    that is too small or a key wider than 64 bits.  One device -> host read (the status and m)."""
+    s = float(voxel_size)
+    if not (math.isfinite(s) and s > 0):
+        raise ValueError(f"mesh_vertex_clusters: voxel_size must be finite and > 0, got {voxel_size!r}")
+    v = _f64_points(vertices, "mesh_vertex_clusters")
+    n, dev = v.shape[0], v.device
+    ws, need = _mesh_filters_workspace("mesh_vertex_clusters", n, 0, dev)
+    cluster = torch.empty(n, device=dev, dtype=torch.int32)
+    means = torch.empty(n, 3, device=dev, dtype=torch.float64)
+    info = torch.empty(4, device=dev, dtype=torch.int64)
+    check(load().lnr_mesh_vertex_clusters(_ptr(v), n, s, _ptr(ws), need, _ptr(cluster), _ptr(means), _ptr(info), _stream()),
+          "lnr_mesh_vertex_clusters")
+    host = info.cpu()
+    if int(host[0]) & 1:
+        raise RuntimeError(f"mesh_vertex_clusters: {int(host[2])} vertices with non-finite coordinates")
+    _cloud_status("mesh_vertex_clusters", host)
+    return cluster, means[:int(host[1])]
+
+
+def mesh_unique_triangles(triangles, n_vertices, vertex_map=None, n_mapped=None, drop_degenerate=False):
+    """open3d's remove_duplicated_triangles as a mask (include/loner_hip.h: lnr_mesh_unique_triangles): triangles [F,3] int32,
+    optional vertex_map int32 [n_vertices] with values in [0, n_mapped) -> (canonical int32 [F,3], the mapped corners rotated by
+    open3d's rule; triangle_keep uint8 [F], 1 for the first triangle of each canonical triple, with drop_degenerate only where its
+    three indices differ; the number kept; the number of degenerate triangles).  Raises RuntimeError on an index or a mapped value
+    out of range.  One device -> host read."""
+    tri = _mesh_triangles(triangles, "mesh_unique_triangles")
+    f, dev = tri.shape[0], tri.device
+    v = _vertex_count(n_vertices, "mesh_unique_triangles")
+    if vertex_map is None:
+        if n_mapped is not None and int(n_mapped) != v:
+            raise ValueError(f"mesh_unique_triangles: n_mapped is n_vertices without a vertex_map, got {n_mapped!r}")
+        m = v
+    else:
+        require_device(vertex_map)
+        if vertex_map.dtype != torch.int32 or tuple(vertex_map.shape) != (v,) or n_mapped is None or not 0 <= int(n_mapped) < 2 ** 31:
+            raise ValueError(f"mesh_unique_triangles: vertex_map int32 [{v}] and n_mapped in [0, 2^31 - 1], got "
+                             f"{tuple(vertex_map.shape)} {vertex_map.dtype} and {n_mapped!r}")
+        vertex_map, m = vertex_map.contiguous(), int(n_mapped)
+    ws, need = _mesh_filters_workspace("mesh_unique_triangles", 0, f, dev)
+    canonical = torch.empty(f, 3, device=dev, dtype=torch.int32)
+    keep = torch.empty(f, device=dev, dtype=torch.uint8)
+    info = torch.empty(4, device=dev, dtype=torch.int64)
+    check(load().lnr_mesh_unique_triangles(_ptr(tri), f, v, _ptr(vertex_map), m, 1 if drop_degenerate else 0, _ptr(ws), need,
+                                           _ptr(canonical), _ptr(keep), _ptr(info), _stream()), "lnr_mesh_unique_triangles")
+    n_kept, n_degenerate = _mesh_tools_info("mesh_unique_triangles", info, _MESH_FILTERS_STATUS)
+    return canonical, keep, n_kept, n_degenerate
+
+
+def mesh_vertex_adjacency(triangles, n_vertices):
+    """Every vertex's distinct neighbours as a CSR (include/loner_hip.h: lnr_mesh_vertex_adjacency): triangles [F,3] int32 ->
+    (row_start int32 [V+1], neighbours int32 [row_start[V]]) on the device, each row ascending, a vertex never its own neighbour.
+    Raises RuntimeError on an index out of range.  One device -> host read (the status and the number of neighbours)."""
+    tri = _mesh_triangles(triangles, "mesh_vertex_adjacency")
+    f, dev = tri.shape[0], tri.device
+    v = _vertex_count(n_vertices, "mesh_vertex_adjacency")
+    ws, need = _mesh_filters_workspace("mesh_vertex_adjacency", 0, f, dev)
+    row_start = torch.empty(v + 1, device=dev, dtype=torch.int32)
+    neighbours = torch.empty(6 * f, device=dev, dtype=torch.int32)
+    info = torch.empty(4, device=dev, dtype=torch.int64)
+    check(load().lnr_mesh_vertex_adjacency(_ptr(tri), f, v, _ptr(ws), need, _ptr(row_start), _ptr(neighbours), _ptr(info), _stream()),
+          "lnr_mesh_vertex_adjacency")
+    n, _ = _mesh_tools_info("mesh_vertex_adjacency", info, _MESH_FILTERS_STATUS)
+    return row_start, neighbours[:n]
+
+
+MESH_SMOOTH_KINDS = {"simple": 0, "laplacian": 1}
+
+
+def mesh_smooth(vertices, row_start, neighbours, n_steps, kind="laplacian", lambda_filter=0.5, mu=None):
+    """n_steps smoothing steps on the device (include/loner_hip.h: lnr_mesh_smooth): vertices [V,3] (fp64), the adjacency of
+    mesh_vertex_adjacency, kind "simple" or "laplacian"; step s uses lambda_filter when s is even and mu (default: lambda_filter)
+    when s is odd, so Taubin's k iterations are 2 k Laplacian steps with mu < 0 -> a new fp64 [V,3] tensor; the input is not
+    changed.  Raises RuntimeError on an adjacency entry out of range.  One device -> host read (the status)."""
+    if kind not in MESH_SMOOTH_KINDS:
+        raise ValueError(f"mesh_smooth: kind must be one of {sorted(MESH_SMOOTH_KINDS)}, got {kind!r}")
+    steps = int(n_steps)
+    if steps != n_steps or not 0 <= steps < 2 ** 31:
+        raise ValueError(f"mesh_smooth: n_steps must be an integer >= 0, got {n_steps!r}")
+    lam = float(lambda_filter)
+    m = lam if mu is None else float(mu)
+    if not (math.isfinite(lam) and math.isfinite(m)):
+        raise ValueError(f"mesh_smooth: the factors must be finite, got {lambda_filter!r} and {mu!r}")
+    v = _f64_points(vertices, "mesh_smooth").clone()
+    require_device(row_start, neighbours)
+    n, dev = v.shape[0], v.device
+    if row_start.dtype != torch.int32 or tuple(row_start.shape) != (n + 1,) or neighbours.dtype != torch.int32 or neighbours.dim() != 1:
+        raise ValueError(f"mesh_smooth: row_start int32 [{n + 1}] and neighbours int32 [n], got {tuple(row_start.shape)} "
+                         f"{row_start.dtype} and {tuple(neighbours.shape)} {neighbours.dtype}")
+    row_start, neighbours = row_start.contiguous(), neighbours.contiguous()
+    scratch = torch.empty_like(v)
+    info = torch.empty(4, device=dev, dtype=torch.int64)
+    check(load().lnr_mesh_smooth(_ptr(v), _ptr(scratch), n, _ptr(row_start), _ptr(neighbours), neighbours.shape[0],
+                                 MESH_SMOOTH_KINDS[kind], steps, lam, m, _ptr(info), _stream()), "lnr_mesh_smooth")
+    _mesh_tools_info("mesh_smooth", info, _MESH_FILTERS_STATUS)
+    return v
 
 
 class Trajectory:
