@@ -741,6 +741,72 @@ int lnr_mesh_vertex_adjacency(const int32_t* triangles, int64_t n_triangles, int
 int lnr_mesh_smooth(double* vertices, double* scratch, int64_t n_vertices, const int32_t* row_start, const int32_t* neighbours,
                     int64_t n_neighbours, int32_t kind, int32_t n_steps, double lambda, double mu, int64_t* info_dev, void* stream);
 
+/* ---- ray casting (open3d's t.geometry.RaycastingScene, and the rays of a LiDAR that moves while it sweeps) ------------------------ */
+/* The conventions of "mesh tools": vertices fp64 [n_vertices,3], triangles int32 [n_triangles,3], n_vertices <= 2^31 - 1 and
+ * n_triangles <= 2^31 - 4096 (the sort's limit); every fp64 expression rounds operation by operation (no fma), square roots and divides
+ * are IEEE; no float is added by an atomic, so every output is a function of the inputs only and two runs give the same bits.  Each
+ * entry writes info_dev int64 [LNR_RAYCAST_INFO]; an index out of range sets a status bit and is never dereferenced; no entry reads
+ * anything back to the host.
+ *
+ * The hit of a ray (o, d) on a triangle (A, B, C) is the watertight rule of Woop, Benthin and Wald (2013) in fp64:
+ *   kz = the axis of largest |d|, the lowest axis on ties; kx = (kz + 1) % 3, ky = (kx + 1) % 3, the two swapped when d[kz] < 0;
+ *   Sx = d[kx] / d[kz], Sy = d[ky] / d[kz], Sz = 1 / d[kz];
+ *   with A, B, C taken relative to o (A = A - o per axis): Ax = A[kx] - Sx * A[kz], Ay = A[ky] - Sy * A[kz], likewise for B and C;
+ *   U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax;
+ *   a miss when (U < 0 || V < 0 || W < 0) && (U > 0 || V > 0 || W > 0), or when det = (U + V) + W is 0;
+ *   t = ((U * (Sz * A[kz]) + V * (Sz * B[kz])) + W * (Sz * C[kz])) / det, accepted when t_min <= t <= t_max; no back-face culling;
+ *   the barycentrics are (u, v) = (U / det, V / det): the hit point is u A + v B + (1 - u - v) C (open3d's pair weighs B and C).
+ * The result of a ray is the accepted hit with the smallest t, the smallest triangle index among equal t; a miss is t = +inf, id -1,
+ * uv 0.  A ray with a non-finite component or a direction of all zeros is a miss and is counted; a triangle with a non-finite vertex
+ * is left out and counted.  This is the whole definition: the tree only decides which triangles a ray is tested against, and its box
+ * test is padded (by 2^-36 of the largest slab distance of the box, and the same share of the box's offset on an axis the ray does not
+ * move along) so that it keeps every box whose triangle the rule above accepts; a node is dropped only when its padded entry distance
+ * is strictly greater than the best t so far. */
+#define LNR_RAYCAST_INFO 8
+#define LNR_BVH_STACK 96            /* words of traversal stack per ray; a tree is at most 63 + 31 levels deep (code bits + tie bits) */
+
+/* An opaque device BVH over (vertices, triangles): lnr_bvh_bytes(n_triangles) bytes (about 190 per triangle), built with a workspace
+ * of lnr_bvh_workspace(n_triangles) bytes (about 26 per triangle); either is 0 when n_triangles is out of range.  The build: the
+ * 63-bit Morton code of every usable triangle's box centre over the box of those centres (an axis without extent contributes 0), the
+ * stable (uint64, uint32) radix sort, Karras' (2012) radix tree with the sorted position breaking ties between equal codes, and the
+ * boxes fitted in LNR_BVH_STACK launches: a node takes its children's boxes only when an earlier launch wrote them.  A triangle with
+ * a non-finite vertex or an index outside [0, n_vertices) is left out of the tree.  The buffer holds copies of the corners: the mesh
+ * may be freed.  info_dev: {status, triangles in the tree, triangles with a non-finite vertex, triangles with an index out of range,
+ * depth (the longest root-to-leaf path in edges; always < LNR_BVH_STACK), nodes, 0, 0}; status bit 1: an index out of range, 2: the
+ * tree is deeper than the stack (cannot happen with 63-bit codes and 2^31 triangles; checked all the same).  With a bit set
+ * lnr_cast_rays reports misses only and repeats the bit. */
+size_t lnr_bvh_workspace(int64_t n_triangles);
+size_t lnr_bvh_bytes(int64_t n_triangles);
+int lnr_bvh_build(const double* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles, void* workspace,
+                  size_t workspace_bytes, void* bvh, size_t bvh_bytes, int64_t* info_dev, void* stream);
+
+/* open3d's RaycastingScene::CastRays with a window.  bvh from lnr_bvh_build with the same n_triangles; rays fp64 [n_rays,6] = (ox, oy,
+ * oz, dx, dy, dz), the direction of any length (t is in units of it); t_min, t_max not NaN.  t_hit fp64 [n_rays], primitive_ids int32
+ * [n_rays] (the index into the triangles given to the build), primitive_uvs fp64 [n_rays,2] (nullable).  One ray per lane, the near
+ * child first; a ray stops after 2 x nodes visits (a damaged tree ends the kernel).  info_dev: {status, hits, rays that are not finite
+ * or have a zero direction, node visits over all rays, rays stopped by the visit cap, triangles the build left out, depth, 0};
+ * status bits 1 and 2 as the build's, 4: the visit cap was reached, 8: a stack column was full (its entry was dropped, never written
+ * out of bounds). */
+int lnr_cast_rays(const void* bvh, int64_t n_triangles, const double* rays, int64_t n_rays, double t_min, double t_max, double* t_hit,
+                  int32_t* primitive_ids, double* primitive_uvs, int64_t* info_dev, void* stream);
+
+/* The rays of a sensor that moves while it sweeps: the inverse of lnr_cloud_trajectory_transform.  directions fp32 [3,n_rays] in the
+ * sensor frame (a scan's layout), timestamps fp64 [n_rays] (absolute), the trajectory arrays as lnr_cloud_trajectory_transform takes
+ * them.  The pose at tau is that entry's, word for word: k the last index with T_k <= tau, at most K - 2; alpha = (tau - T_k) /
+ * (T_{k+1} - T_k); trans_a = P_k,a + alpha * (P_{k+1},a - P_k,a); w = alpha * w_k per axis, theta = sqrt((w_x w_x + w_y w_y) + w_z
+ * w_z); R = R_k when theta < 1e-9, else R_k E with E and the product as stated there.  Only the sine and cosine in E are pinned down
+ * further, so that a restatement gives the same bits on any host (a library's sine is good to an ulp, and which ulp differs between
+ * libraries; these are within 2 ulps): k = floor(theta * 0.6366197723675814 + 0.5), r = (theta - k * 1.5707963267948966) - k *
+ * 6.123233995736766e-17, z = r * r; p_s = p_c = 1.0, then for j = 10 down to 1: p_s = 1.0 - (z * p_s) / (2j (2j + 1)) and p_c = 1.0 -
+ * (z * p_c) / ((2j - 1) 2j); S = r * p_s, C = p_c; (sin, cos) = (S, C), (C, -S), (-S, -C), (-C, S) for k mod 4 = 0, 1, 2, 3.
+ * rays fp64 [n_rays,6]: origin = trans, direction_a
+ * = (R_a0 x + R_a1 y) + R_a2 z with (x, y, z) the direction widened to fp64.  A ray whose time lies outside [T_0, T_{K-1}] or whose
+ * direction or time is not finite is six NaNs (lnr_cast_rays then reports a miss) and is counted.  info_dev: {status, rays written,
+ * outside the trajectory, non-finite, 0, 0, 0, 0}; status bit 1: a non-finite direction or time. */
+int lnr_trajectory_rays(const float* directions, const double* timestamps, int64_t n_rays, const double* traj_times,
+                        const double* traj_positions, const double* traj_rotations, const double* traj_rotvecs, int64_t n_poses,
+                        double* rays, int64_t* info_dev, void* stream);
+
 /* ---- tracking (src/common/frame.py:104-145; src/common/sensors.py:176-232; src/tracking/tracker.py:257-297) ----------------- */
 #define LNR_MOCOMP_CONSTS 30      /* fp64 entries of lnr_motion_compensate's consts */
 #define LNR_SKY_MAX_RAYS 65160    /* 181 x 360: the row stride lnr_sky_rays' output needs */

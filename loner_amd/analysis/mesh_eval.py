@@ -45,3 +45,44 @@ def evaluate_mesh(mesh, gt_cloud, output_dir, f_score_threshold=0.1, voxel_size=
     cloud = mesh_to_point_cloud(mesh, voxel_size if resolution is None else resolution, number_of_points, seed,
                                 device=gt_cloud.points.device)
     return compare_point_clouds(cloud, gt_cloud, output_dir, f_score_threshold, voxel_size, **compare_kwargs)
+
+
+def mesh_depth_l1(est_scene, gt_scene, poses, directions, ray_range):
+    """The "Depth L1" of the mesh-based SLAM literature: both meshes (RaycastingScenes, analysis/raycast.py) are seen from the same
+    poses along the same rays, and the depths are compared.  poses: 4x4 sensor-to-world transforms (Poses, tensors or arrays);
+    directions [3,n] in the sensor frame (a scan's layout; depth is t times the direction's length); ray_range = (min, max) metres.
+    A ray returns when it hits with min <= depth <= max.  -> {"depth_l1": the mean |depth_est - depth_gt| over the rays both meshes
+    return (NaN when there is none), "n_rays", "n_valid", "est_miss_ratio", "gt_miss_ratio": the share of all rays each mesh does not
+    return}.  The sum runs in fp64 on the device (torch); one host read."""
+    import torch
+    lo, hi = (float(x) for x in ray_range)
+    if not (lo >= 0 and hi > lo):
+        raise ValueError(f"mesh_depth_l1: ray_range must be 0 <= min < max, got {ray_range!r}")
+    d = torch.as_tensor(directions)
+    if d.dim() != 2 or d.shape[0] != 3:
+        raise ValueError(f"mesh_depth_l1: directions [3,n], got {tuple(d.shape)}")
+    if len(poses) == 0:
+        raise ValueError("mesh_depth_l1: at least one pose is needed")
+    if est_scene.device != gt_scene.device:
+        raise ValueError(f"mesh_depth_l1: the scenes live on {est_scene.device} and {gt_scene.device}")
+    dev = gt_scene.device
+    d = d.to(device=dev, dtype=torch.float64).T
+    rays = []
+    for pose in poses:
+        T = pose.get_transformation_matrix() if hasattr(pose, "get_transformation_matrix") else torch.as_tensor(pose)
+        T = T.detach().to(device=dev, dtype=torch.float64)
+        if tuple(T.shape) != (4, 4):
+            raise ValueError(f"mesh_depth_l1: a pose must be a 4x4 transform, got {tuple(T.shape)}")
+        world = (d[:, 0:1] * T[:3, 0] + d[:, 1:2] * T[:3, 1]) + d[:, 2:3] * T[:3, 2]
+        rays.append(torch.cat([T[:3, 3].expand_as(world), world], dim=1))
+    rays = torch.cat(rays).contiguous()
+    length = torch.linalg.norm(rays[:, 3:], dim=1)
+    depth = [scene.cast_rays(rays)["t_hit"] * length for scene in (est_scene, gt_scene)]
+    back = [(x >= lo) & (x <= hi) for x in depth]
+    both = back[0] & back[1]
+    diff = torch.where(both, (depth[0] - depth[1]).abs(), torch.zeros_like(length))
+    n = rays.shape[0]
+    out = torch.stack([diff.sum(), both.sum().double(), back[0].sum().double(), back[1].sum().double()]).cpu()
+    n_valid = int(out[1])
+    return {"depth_l1": float(out[0]) / n_valid if n_valid else float("nan"), "n_rays": n, "n_valid": n_valid,
+            "est_miss_ratio": (1.0 - float(out[2]) / n) if n else 0.0, "gt_miss_ratio": (1.0 - float(out[3]) / n) if n else 0.0}

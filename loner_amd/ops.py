@@ -1129,6 +1129,101 @@ def trajectory_transform(points, timestamps, trajectory, min_range):
     return out, info
 
 
+# ---------------------------------------------------------------- ray casting
+_BVH_STATUS = {1: "a vertex index is out of range", 2: "the tree is deeper than the traversal stack"}
+_CAST_STATUS = {**_BVH_STATUS, 4: "a ray reached the visit cap", 8: "a traversal stack was full"}
+
+
+class BVH:
+    """The device BVH over a triangle mesh (include/loner_hip.h: lnr_bvh_build), reusable for any number of ray batches: vertices
+    [V,3] (fp64) and triangles [F,3] int32 on the device.  The buffer holds its own copy of the corners.  .n_triangles (F),
+    .n_in_tree, .n_nonfinite (triangles left out for a non-finite vertex), .depth, .n_nodes: what the build reports (one host read).
+    Raises RuntimeError on a vertex index out of range."""
+
+    def __init__(self, vertices, triangles):
+        v = _f64_points(vertices, "BVH")
+        tri = _mesh_triangles(triangles, "BVH")
+        if tri.device != v.device:
+            raise ValueError(f"BVH: vertices on {v.device}, triangles on {tri.device}")
+        f, dev = tri.shape[0], v.device
+        lib = load()
+        need, nbytes = int(lib.lnr_bvh_workspace(f)), int(lib.lnr_bvh_bytes(f))
+        if need == 0 or nbytes == 0:
+            raise RuntimeError(f"BVH: {f} triangles, the limit is 2^31 - 4096")
+        self.n_triangles = f
+        self.buf = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+        ws = torch.empty(need, device=dev, dtype=torch.uint8)
+        info = torch.empty(hip.RAYCAST_INFO, device=dev, dtype=torch.int64)
+        check(lib.lnr_bvh_build(_ptr(v), v.shape[0], _ptr(tri), f, _ptr(ws), need, _ptr(self.buf), nbytes, _ptr(info), _stream()),
+              "lnr_bvh_build")
+        host = info.cpu()
+        status = int(host[0])
+        if status:
+            raise RuntimeError(f"BVH: {int(host[3])} triangles with an index out of range: " +
+                               ", ".join(m for b, m in _BVH_STATUS.items() if status & b))
+        self.n_in_tree, self.n_nonfinite, self.depth, self.n_nodes = int(host[1]), int(host[2]), int(host[4]), int(host[5])
+
+    @property
+    def device(self):
+        return self.buf.device
+
+
+def cast_rays(bvh, rays, t_min=0.0, t_max=math.inf, want_uvs=True, stats=None):
+    """open3d's RaycastingScene.cast_rays with a window (include/loner_hip.h: lnr_cast_rays): rays [n,6] (ox oy oz dx dy dz) on the
+    BVH's device -> (t_hit fp64 [n], +inf on a miss; primitive_ids int32 [n], -1 on a miss; primitive_uvs fp64 [n,2] or None).
+    stats (a dict, optional) receives {"hits", "invalid_rays", "node_visits", "capped_rays", "excluded_triangles", "depth"} at the
+    price of one device -> host read, which then also raises RuntimeError on a status bit; without it nothing is read back."""
+    if not isinstance(bvh, BVH):
+        raise ValueError(f"cast_rays: bvh must be an ops.BVH, got {type(bvh).__name__}")
+    require_device(rays)
+    if rays.dim() != 2 or rays.shape[1] != 6:
+        raise ValueError(f"cast_rays: rays [n,6], got {tuple(rays.shape)}")
+    lo, hi = float(t_min), float(t_max)
+    if math.isnan(lo) or math.isnan(hi):
+        raise ValueError(f"cast_rays: t_min and t_max must be numbers, got {t_min!r} and {t_max!r}")
+    if rays.device != bvh.device:
+        raise ValueError(f"cast_rays: rays on {rays.device}, the BVH on {bvh.device}")
+    r = rays.to(torch.float64).contiguous()
+    n, dev = r.shape[0], r.device
+    t_hit = torch.empty(n, device=dev, dtype=torch.float64)
+    ids = torch.empty(n, device=dev, dtype=torch.int32)
+    uvs = torch.empty(n, 2, device=dev, dtype=torch.float64) if want_uvs else None
+    info = torch.empty(hip.RAYCAST_INFO, device=dev, dtype=torch.int64)
+    check(load().lnr_cast_rays(_ptr(bvh.buf), bvh.n_triangles, _ptr(r), n, lo, hi, _ptr(t_hit), _ptr(ids), _ptr(uvs), _ptr(info),
+                               _stream()), "lnr_cast_rays")
+    if stats is not None:
+        host = info.cpu()
+        status = int(host[0])
+        if status:
+            raise RuntimeError("cast_rays: " + ", ".join(m for b, m in _CAST_STATUS.items() if status & b))
+        stats.update(hits=int(host[1]), invalid_rays=int(host[2]), node_visits=int(host[3]), capped_rays=int(host[4]),
+                     excluded_triangles=int(host[5]), depth=int(host[6]))
+    return t_hit, ids, uvs
+
+
+def trajectory_rays(directions, timestamps, trajectory):
+    """The rays of a sensor that moves while it sweeps (include/loner_hip.h: lnr_trajectory_rays): directions [3,n] fp32 in the sensor
+    frame, timestamps [n] (absolute, widened to fp64), trajectory a Trajectory on the same device -> (rays fp64 [n,6], NaN where the
+    time lies outside the trajectory or an input is not finite; info int64 [8] on the device: {status, rays, outside, non-finite})."""
+    require_device(directions, timestamps)
+    if directions.dim() != 2 or directions.shape[0] != 3 or directions.dtype != torch.float32:
+        raise ValueError(f"trajectory_rays: directions fp32 [3,n], got {tuple(directions.shape)} {directions.dtype}")
+    n = directions.shape[1]
+    if tuple(timestamps.shape) != (n,):
+        raise ValueError(f"trajectory_rays: timestamps [{n}], got {tuple(timestamps.shape)}")
+    if not isinstance(trajectory, Trajectory):
+        raise ValueError(f"trajectory_rays: trajectory must be an ops.Trajectory, got {type(trajectory).__name__}")
+    d = directions.contiguous()
+    stamps = timestamps.to(torch.float64).contiguous()
+    dev = d.device
+    rays = torch.empty(n, 6, device=dev, dtype=torch.float64)
+    info = torch.empty(hip.RAYCAST_INFO, device=dev, dtype=torch.int64)
+    tr = trajectory
+    check(load().lnr_trajectory_rays(_ptr(d), _ptr(stamps), n, _ptr(tr.times), _ptr(tr.positions), _ptr(tr.rotations), _ptr(tr.rotvecs),
+                                     tr.n_poses, _ptr(rays), _ptr(info), _stream()), "lnr_trajectory_rays")
+    return rays, info
+
+
 # ---------------------------------------------------------------- scan ingestion
 _scan_ws = {}
 
