@@ -511,9 +511,12 @@ static Layout make_layout(const LnrNetSpec* spec, int64_t n_points, const Densit
 }
 
 // flag LNR_BWD_REPORT_REGIONS: how full the record regions ran (diagnostic for sizing RegionPlan; synchronises the stream)
-static void report_regions(const LnrNetSpec* spec, const Layout& L, const RegionPlan& plan, const int* counts, const float* dfeat, int64_t n_points, hipStream_t st) {
+static void report_regions(const LnrNetSpec* spec, const Layout& L, const RegionPlan& plan, const int* counts, const int* ovf_flag, int epoch, const float* dfeat,
+                           int64_t n_points, hipStream_t st) {
     std::vector<int> h((size_t)spec->n_levels * L.maxo * L.bpg);
-    if (hipStreamSynchronize(st) != hipSuccess || hipMemcpy(h.data(), counts, h.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return;
+    int used[LNR_MAX_LEVELS] = {};          // ovf_flag[l] == epoch: this call sent records of level l to the overflow accumulators
+    if (hipStreamSynchronize(st) != hipSuccess || hipMemcpy(h.data(), counts, h.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(used, ovf_flag, sizeof(used), hipMemcpyDeviceToHost) != hipSuccess) return;
     for (int l = 0; l < spec->n_levels; ++l) {
         const int rec = plan.xp[l] ? 12 : 8, cap = (int)(plan.bytes[l] / rec);
         long long sum = 0, over = 0; int mx = 0;
@@ -532,8 +535,8 @@ static void report_regions(const LnrNetSpec* spec, const Layout& L, const Region
                 fprintf(stderr, "[lnr regions] level %2d: %lld of %lld samples have d_feature != 0, in %lld runs\n", l, nz, (long long)n_points, runs);
             }
         }
-        fprintf(stderr, "[lnr regions] level %2d: %d-B records, capacity %d, mean %.1f, max %d, overflowed %lld of %lld\n", l, rec, cap,
-                (double)sum / ((double)span * L.bpg), mx, over, sum);
+        fprintf(stderr, "[lnr regions] level %2d: %d-B records, capacity %d, mean %.1f, max %d, overflowed %lld of %lld, overflow accumulators %s, %d reduce workgroups per owner\n",
+                l, rec, cap, (double)sum / ((double)span * L.bpg), mx, over, sum, used[l] == epoch ? "used" : "unused", (int)plan.split[l]);
     }
 }
 
@@ -938,7 +941,7 @@ extern "C" int lnr_density_backward(const LnrNetSpec* spec, const float* params,
             int64_t live = cap;
             int32_t nr = 0;
             if (n_rays_dev && hipStreamSynchronize(st) == hipSuccess && hipMemcpy(&nr, n_rays_dev, sizeof(nr), hipMemcpyDeviceToHost) == hipSuccess) live = (int64_t)nr * n_samples;
-            report_regions(spec, L, rplan, counts, dfeat, live, st);
+            report_regions(spec, L, rplan, counts, ovf_flag, epoch, dfeat, live, st);
         }
     }
     if (hash && L.nown > 0) {          // also with cap_rec == 0 (all-atomic test path): it folds in the overflow accumulators

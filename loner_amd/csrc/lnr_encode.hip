@@ -380,10 +380,12 @@ __device__ __forceinline__ void row_run_sum_n(float (&v)[N], const RunMul& m) {
 // run masks of one 16-lane row: which lanes share the cell of their left neighbour
 __device__ __forceinline__ void cell_runs(const Cell& c, int lane, bool& head, RunMask& run) {
     const int c16 = lane & 15;
-    const int k1 = (int)(c.b[0] | (c.b[1] << 16)), k2 = (int)c.b[2];
+    // (all 32 bits of all three cells: packing x | y << 16 made every cell below the cube's x = -1 face - x = 0xFFFFFFFF - equal to its
+    // neighbour's whatever their y, and samples of different cells were summed into one record)
+    const int k0 = (int)c.b[0], k1 = (int)c.b[1], k2 = (int)c.b[2];
     // the DPP reads must run with all lanes active: evaluate them before (not inside) any short-circuit logic
-    const int p1 = row_up_i<1>(k1), p2 = row_up_i<1>(k2);
-    head = (c16 == 0) | (p1 != k1) | (p2 != k2);
+    const int p0 = row_up_i<1>(k0), p1 = row_up_i<1>(k1), p2 = row_up_i<1>(k2);
+    head = (c16 == 0) | (p0 != k0) | (p1 != k1) | (p2 != k2);
     int seg = head ? 1 : 0;
     int t;
     t = row_up_i<1>(seg); if (c16 >= 1) seg += t;
@@ -509,6 +511,16 @@ __device__ __forceinline__ void xpair_overflow(long long* ovf_level, uint32_t fi
     atomicAdd(o + fi1_in_level + 1, (unsigned long long)q[3]);
 }
 
+// t of an x-pair: the trailing one bits of the cell's x; 12 and more mean "two single-corner records" (encode_backward_kernel).  The 32
+// cells around x = 0 are sent that way too, whatever their t: only there - positions below 16 in magnitude - does the fraction carry more
+// than the 19 significant bits a record's 28-bit fx keeps (from 16 on a float32 position has at most 19 bits behind the point), and
+// rounding fx to 2^-21 leaves the x corner of a cell with 1 - fx < 1/16 an error beyond the 2^-18 of a record's values; a single-corner
+// record carries the float32 product (1 - fx) a instead.  With this fx is exact in every x-pair record.
+__device__ __forceinline__ uint32_t xpair_trailing_ones(uint32_t bx) {
+    const uint32_t t = (uint32_t)__builtin_ctz(~bx);
+    return (bx + 16u) < 32u ? 12u : t;
+}
+
 #ifdef LNR_PHASE_TIMING
 __device__ unsigned long long lnr_phase_cycles[2 * LNR_N_PHASES];          // [8-byte record levels | x-pair levels]
 #endif
@@ -632,7 +644,7 @@ encode_backward_kernel(const LnrNetSpec spec, const float* __restrict__ table, c
             for (int k = 0; k < 8; ++k) rrank[k] = -1;
             uint32_t xt = 0u;                       // x-pair levels: trailing one bits of the cell's x (e(x+1) = e(x) ^ (2^(t+1) - 1))
             if (wave_any && xp) {
-                xt = (uint32_t)__builtin_ctz(~c.b[0]);
+                xt = xpair_trailing_ones(c.b[0]);
                 const float wy[2] = {1.0f - c.frac[1], c.frac[1]}, wz[2] = {1.0f - c.frac[2], c.frac[2]};
 #pragma unroll
                 for (int k2 = 0; k2 < 4; ++k2) {
@@ -966,7 +978,7 @@ encode_backward_binned_kernel(const LnrNetSpec spec, const float* __restrict__ t
             // (measured: the rank atomics cost 0.11 of the x-pair levels' 0.54 ms when each was waited for in turn).
             constexpr uint32_t NO_SLOT = 0xFFFFFFFFu;
             if (wave_any && xp) {
-                const uint32_t xt = (uint32_t)__builtin_ctz(~c.b[0]);
+                const uint32_t xt = xpair_trailing_ones(c.b[0]);
                 const float wy[2] = {1.0f - c.frac[1], c.frac[1]}, wz[2] = {1.0f - c.frac[2], c.frac[2]};
                 float a0[4], a1[4];
                 uint32_t at[4];

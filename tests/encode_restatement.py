@@ -1,0 +1,527 @@
+"""Dtype-generic restatement of the multiresolution hash-grid encoding and of its two gradients, PER LEVEL, and an integer restatement
+of the table-gradient record formats (loner_amd/csrc/lnr_density_api.h: lnr_pack26, lnr_pack_pair, lnr_pack_xpair, lnr_to_fix,
+lnr_xpair_fix) - the reference of tests/test_gpu_encode.py.
+
+Plain torch / numpy, no import of oracle/ and no call into the library: tests/test_encode_host.py ties the float32 run to
+oracle.network.encode_hashgrid, the float64 gradients to autograd through the oracle and to central differences of `level_features`.
+
+ONE RULE.  The cell and the fraction of a sample belong to the function's float32 definition: unit coordinate rn(rn(p + 1) / 2),
+position fma(x, scale, 0.5) rounded ONCE to float32, cell = floor, fraction = position - cell (exact).  At scale 2^19 that rounding is
+2^-6 of a cell, so a float64 evaluation of the position is another function.  `locate` therefore always works in float32, and the
+"float64 run" continues from its cell and fraction in float64: weights, products, sums, and the d/dx term with its `scale` factor.
+The float32 run of the same code is the noise yardstick (tail_restatement.block_err / bound).
+
+Cells are unsigned 32-bit numbers (tiny-cuda-nn's `(uint32_t)(int)floor(pos)`): a point below the cube's near faces has cells that
+wrap, on dense-indexed levels too (oracle/network.py indexes those with signed 64-bit cells and differs there)."""
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from tests.tail_restatement import F32_EPS, Ledger, block_err, block_max, bound, elementwise_rel     # noqa: F401 (re-exported)
+
+PRIME_Y = 2654435761
+PRIME_Z = 805459861
+M32 = 0xFFFFFFFF
+
+SLICE_FLOATS = 8192               # LNR_SLICE_SHIFT = 13: floats of one owner slice
+XPAIR_SCALE_MIN = 3000.0          # LNR_XPAIR_SCALE_MIN: hashed power-of-two levels from this scale up take x-pair records
+COMBINE_SCALE_MAX = 3000.0        # LNR_COMBINE_SCALE_MAX: levels below it are run-length combined along the rays
+FIX_BITS = 42                     # LNR_FIX_SCALE = 2^42
+
+
+# ---------------------------------------------------------------- the grid
+@dataclass
+class Level:
+    scale: float          # a float32 value
+    res: int
+    size: int             # entries
+    offset: int           # entries, from the start of the table
+    hashed: bool
+
+
+@dataclass
+class Grid:
+    n_features: int
+    levels: list
+
+    @property
+    def n_entries(self):
+        return sum(lv.size for lv in self.levels)
+
+
+def make_grid(enc):
+    """tiny-cuda-nn's HashGrid geometry from its config dict: scale = base * growth^l - 1 in float32, res = ceil(scale) + 1, dense while
+    res^3 (rounded up to 8) fits 2^log2_hashmap_size, hashed above"""
+    F = int(enc.get("n_features_per_level", 2))
+    cap = 1 << int(enc.get("log2_hashmap_size", 19))
+    base, growth = np.float32(enc.get("base_resolution", 16)), np.float32(enc.get("per_level_scale", 2.0))
+    levels, off = [], 0
+    for l in range(int(enc.get("n_levels", 16))):
+        scale = float(np.float32(np.exp2(np.float32(l) * np.log2(growth)) * base - np.float32(1.0)))
+        res = int(np.ceil(scale)) + 1
+        size = min((res ** 3 + 7) // 8 * 8, cap)
+        levels.append(Level(scale, res, size, off, res ** 3 > size))
+        off += size
+    return Grid(F, levels)
+
+
+def uses_xpairs(grid, l):
+    """lnr_level_can_use_xpairs: F == 2, hashed, power-of-two size, scale >= 3000, the level starts on an owner-slice boundary"""
+    lv = grid.levels[l]
+    return (grid.n_features == 2 and lv.hashed and lv.size & (lv.size - 1) == 0 and lv.scale >= XPAIR_SCALE_MIN
+            and (lv.offset * 2) % SLICE_FLOATS == 0)
+
+
+# ---------------------------------------------------------------- float32 definition of cell and fraction
+def world_points(rays, z):
+    """p = o + d z with product and sum rounded separately (float32): rays [n,13], z [n,S] -> [n,S,3]"""
+    assert rays.dtype == torch.float32 and z.dtype == torch.float32
+    return rays[:, None, 0:3] + rays[:, None, 3:6] * z[:, :, None]
+
+
+def unit_coordinates(p):
+    assert p.dtype == torch.float32
+    return (p + 1.0) * 0.5
+
+
+def locate(lv, p):
+    """world points [n,3] float32 -> (cell int64 [n,3], signed; fraction float32 [n,3]) on one level"""
+    x = unit_coordinates(p)
+    pos = (x.double() * lv.scale + 0.5).float()       # fp32 x fp32 is exact in fp64 and so is adding 0.5: one rounding = fmaf
+    cell = torch.floor(pos)
+    return cell.long(), pos - cell
+
+
+def corner_entries(lv, cell):
+    """entry inside the level of each of the 8 corners (bit 0 = +x, 1 = +y, 2 = +z): int64 [n,8], cells taken modulo 2^32"""
+    out = []
+    for k in range(8):
+        cx, cy, cz = (cell[:, 0] + (k & 1)) & M32, (cell[:, 1] + ((k >> 1) & 1)) & M32, (cell[:, 2] + ((k >> 2) & 1)) & M32
+        if lv.hashed:
+            idx = cx ^ ((cy * PRIME_Y) & M32) ^ ((cz * PRIME_Z) & M32)
+        else:
+            idx = (cx + ((cy * lv.res) & M32) + ((cz * (lv.res * lv.res)) & M32)) & M32
+        out.append(idx % lv.size)
+    return torch.stack(out, dim=1)
+
+
+def corner_weights(frac):
+    """[n,3] -> [n,8], associated (wx wy) wz like oracle/network.py"""
+    one = 1 - frac
+    cols = []
+    for k in range(8):
+        wx = frac[:, 0] if k & 1 else one[:, 0]
+        wy = frac[:, 1] if k & 2 else one[:, 1]
+        wz = frac[:, 2] if k & 4 else one[:, 2]
+        cols.append(wx * wy * wz)
+    return torch.stack(cols, dim=1)
+
+
+def level_features(lv, table_l, entries, frac):
+    """table_l [size,F], entries [n,8], frac [n,3] in table_l's dtype -> [n,F]; corners added in order 0..7"""
+    w = corner_weights(frac)
+    acc = torch.zeros(frac.shape[0], table_l.shape[1], dtype=table_l.dtype)
+    for k in range(8):
+        acc = acc + w[:, k, None] * table_l[entries[:, k]]
+    return acc
+
+
+def level_input_grad(lv, table_l, entries, frac, g):
+    """d(sum_f g_f feature_f)/d(world point) [n,3]: per axis the corner differences along it, interpolated along the other two,
+    times scale (position per unit coordinate) times 1/2 (unit coordinate per world coordinate)"""
+    dot = (table_l[entries] * g[:, None, :]).sum(dim=2)                       # [n,8]
+    one = 1 - frac
+    out = []
+    for axis in range(3):
+        u, v = [a for a in range(3) if a != axis]
+        total = torch.zeros_like(dot[:, 0])
+        for k in range(8):
+            if (k >> axis) & 1:
+                continue
+            wu = frac[:, u] if (k >> u) & 1 else one[:, u]
+            wv = frac[:, v] if (k >> v) & 1 else one[:, v]
+            total = total + (dot[:, k | (1 << axis)] - dot[:, k]) * (wu * wv)
+        out.append(total * lv.scale * 0.5)
+    return torch.stack(out, dim=1)
+
+
+def level_table_grad(lv, F, entries, frac, g):
+    """-> (gradient [size,F], A = sum of |contribution| [size,F], n = number of non-zero contributions [size,F]) in g's dtype"""
+    w = corner_weights(frac)
+    grad = torch.zeros(lv.size, F, dtype=g.dtype)
+    mag, cnt = torch.zeros_like(grad), torch.zeros_like(grad)
+    for k in range(8):
+        c = w[:, k, None] * g
+        grad.index_add_(0, entries[:, k], c)
+        mag.index_add_(0, entries[:, k], c.abs())
+        cnt.index_add_(0, entries[:, k], (c != 0).to(g.dtype))
+    return grad, mag, cnt
+
+
+def table_of(grid, table_flat, l):
+    lv = grid.levels[l]
+    F = grid.n_features
+    return table_flat[lv.offset * F:(lv.offset + lv.size) * F].reshape(lv.size, F)
+
+
+def encode(grid, table_flat, p, dtype, d_feat=None, live=None):
+    """The whole encoding in `dtype` from its float32 cells: table_flat [n_entries * F], p [n,3] float32 world points,
+    d_feat [n, L*F] (optional, any dtype), live [n] bool (optional: the other points contribute nothing) ->
+    dict of per-level lists: feat [n,F]; and with d_feat: tgrad / A / cnt [size,F], dpts [n,3]"""
+    F = grid.n_features
+    out = dict(feat=[], tgrad=[], A=[], cnt=[], dpts=[])
+    table_flat = table_flat.to(dtype)
+    for l, lv in enumerate(grid.levels):
+        cell, frac32 = locate(lv, p)
+        entries, frac, tab = corner_entries(lv, cell), frac32.to(dtype), table_of(grid, table_flat, l)
+        out["feat"].append(level_features(lv, tab, entries, frac))
+        if d_feat is not None:
+            g = d_feat[:, l * F:(l + 1) * F].to(dtype)
+            if live is not None:
+                g = g * live[:, None].to(dtype)
+            t, a, c = level_table_grad(lv, F, entries, frac, g)
+            out["tgrad"].append(t); out["A"].append(a); out["cnt"].append(c)
+            out["dpts"].append(level_input_grad(lv, tab, entries, frac, g))
+    return out
+
+
+def ray_sums(dpts, z):
+    """d_pts [n,S,3], z [n,S] -> [n,6]: origin columns sum_s g, direction columns sum_s z g"""
+    return torch.cat([dpts.sum(dim=1), (z[..., None].to(dpts.dtype) * dpts).sum(dim=1)], dim=1)
+
+
+# ---------------------------------------------------------------- selector networks: sigma = sum_j c_j feature_j, exactly
+def selector_params(mlp_shapes, n_mlp, coeff, relu):
+    """MLP part of a parameter vector ([out,in] row-major matrices, first layer first, 16 output rows of which row 0 is sigma) that makes
+    a one-hidden-layer network compute sigma = sum_j coeff[j] feature_j.  relu=False (activation None): neuron 0 carries the sum.
+    relu=True: neuron 0 carries s and neuron 1 carries -s, sigma = relu(s) - relu(-s) = s."""
+    assert len(mlp_shapes) == 2
+    (H, in_dim), (_, H2) = mlp_shapes
+    w1, w2 = torch.zeros(H, in_dim), torch.zeros(16, H2)
+    w1[0, :len(coeff)] = torch.as_tensor(coeff, dtype=torch.float32)
+    w2[0, 0] = 1.0
+    if relu:
+        w1[1] = -w1[0]
+        w2[0, 1] = -1.0
+    out = torch.cat([w1.reshape(-1), w2.reshape(-1)])
+    assert out.numel() == n_mlp
+    return out
+
+
+def all_level_coefficients(n):
+    """2^-(j mod 8): every d_feature plane is an exact power-of-two multiple of d_sigma"""
+    return [2.0 ** -(j % 8) for j in range(n)]
+
+
+# ---------------------------------------------------------------- crafted points
+def trailing_ones(x):
+    x, t = int(x) & M32, 0                 # (cells are unsigned 32-bit numbers: -1 has 32 trailing ones)
+    while x & 1:
+        x >>= 1; t += 1
+    return t
+
+
+def _neighbour_floats(w, span):
+    """the float32 numbers up to `span` steps on either side of w, as points [2 span + 1, 3] with y = z = 0"""
+    bits = np.array([w], np.float32).view(np.int32)[0]
+    cand = (bits + np.arange(-span, span + 1, dtype=np.int64)).astype(np.int32).view(np.float32)
+    return cand, torch.from_numpy(np.stack([cand, np.zeros_like(cand), np.zeros_like(cand)], axis=1).copy())
+
+
+def _search_world(lv, cell_x, want, span=20000):
+    """a float32 world coordinate whose float32-defined cell on `lv` is cell_x and whose fraction satisfies want(frac) (a bool mask),
+    searched among the `span` floats on either side of the cell's lower edge; None if there is none"""
+    cand, p = _neighbour_floats(2.0 * ((cell_x - 0.5) / lv.scale) - 1.0, span)
+    cell, frac = locate(lv, p)
+    hits = torch.nonzero((cell[:, 0] == cell_x) & want(frac[:, 0]))[:, 0]
+    return float(cand[int(hits[0])]) if hits.numel() else None
+
+
+T_CLASSES = (0, 5, 11, 12, 13, 15, 16)          # 16 stands for ">= 16"
+
+
+def t_class(t):
+    return 16 if t >= 16 else t
+
+
+def crafted_points(grid, seed=0, outside=True):
+    """Points (float32 world coordinates [n,3]) aimed at the x-pair levels of `grid`, and a list of (row, level, what) notes.
+    Per level of resolution > 4096 and per t in {0, 5, 11, 12, 13, 15, all bits of the level}: four x cells with exactly t trailing one
+    bits, random y, z and random fractions; per such level x fractions of exactly 0 and the largest fraction a float32 world coordinate
+    reaches in cells 0..7 (the only cells whose positions are fine enough to come within 2^-21 of 1); then points exactly on each of
+    the six faces and, with `outside`, up to 35 % beyond each of them."""
+    gen = torch.Generator().manual_seed(seed)
+    rows, notes = [], []
+    rnd = lambda: float(torch.rand(1, generator=gen, dtype=torch.float64))
+    for l, lv in enumerate(grid.levels):
+        if not (uses_xpairs(grid, l) and lv.res > 4096):
+            continue
+        bits = lv.res.bit_length() - 1
+        for t in (0, 5, 11, 12, 13, 15, bits):
+            if t > bits:
+                continue
+            for rep in range(4):
+                if t == bits:
+                    cx = lv.res - 1
+                else:
+                    high = int(rnd() * (lv.res >> (t + 1)))
+                    cx = (high << (t + 1)) | ((1 << t) - 1)
+                # the last cell of a level ends at position res - 1/2: fractions below 1/2 only
+                frac = (0.05 + 0.4 * rnd()) if cx == lv.res - 1 else (0.05 + 0.9 * rnd())
+                wx = 2.0 * ((cx + frac - 0.5) / lv.scale) - 1.0
+                rows.append([wx, 1.9 * rnd() - 0.95, 1.9 * rnd() - 0.95])
+                notes.append((len(rows) - 1, l, f"t={t}"))
+        for rep in range(3):                                   # fraction exactly 0 along x
+            cx = 8 + int(rnd() * (lv.res - 16))
+            wx = _search_world(lv, cx, lambda f: f == 0.0)
+            if wx is not None:
+                rows.append([wx, 1.9 * rnd() - 0.95, 1.9 * rnd() - 0.95])
+                notes.append((len(rows) - 1, l, "fx=0"))
+        for cx in (-16, -9, -2, -1, 0, 1, 2, 3, 4, 5, 6, 7, 8, 11, 14, 15):
+            # cells around x = 0: positions below 16 in magnitude, the only ones whose fraction has more significant bits than the 19
+            # an x-pair record's fx keeps; fractions crowd towards 1, where the x corner's weight 1 - fx is small
+            frac = 1.0 - 0.98 * rnd() ** 3
+            rows.append([2.0 * ((cx + frac - 0.5) / lv.scale) - 1.0, 1.9 * rnd() - 0.95, 1.9 * rnd() - 0.95])
+            notes.append((len(rows) - 1, l, "low"))
+        for cx in (0, 1, 3, 7):                                # the largest reachable fraction of the cells next to the near face
+            cand, p = _neighbour_floats(2.0 * ((cx + 0.5) / lv.scale) - 1.0, 400)
+            cell, frac = locate(lv, p)
+            ok = cell[:, 0] == cx
+            if bool(ok.any()):
+                f = torch.where(ok, frac[:, 0], torch.full_like(frac[:, 0], -1.0))
+                best = float(cand[int(f.argmax())])
+                rows.append([best, 1.9 * rnd() - 0.95, 1.9 * rnd() - 0.95])
+                notes.append((len(rows) - 1, l, "fx->1"))
+    for axis in range(3):
+        for side in (-1.0, 1.0):
+            for rep in range(6):
+                p = [1.9 * rnd() - 0.95 for _ in range(3)]
+                p[axis] = side
+                rows.append(p); notes.append((len(rows) - 1, -1, "face"))
+            for rep in range(6 if outside else 0):
+                p = [1.9 * rnd() - 0.95 for _ in range(3)]
+                p[axis] = side * (1.0 + 0.35 * (rep + 1) / 6.0)
+                rows.append(p); notes.append((len(rows) - 1, -1, "outside"))
+    if outside:
+        rows.append([1.35, -1.35, 1.2]); notes.append((len(rows) - 1, -1, "outside"))
+        rows.append([-1.0, 1.0, -1.0]); notes.append((len(rows) - 1, -1, "face"))
+    return torch.tensor(rows, dtype=torch.float64).float(), notes
+
+
+SWEEP_EXPONENTS = tuple(range(-40, 15, 6))           # d_sigma 2^k, k = -40, -34, ..., 14
+
+
+def sweep_d_sigma(n, seed=5):
+    """normal deviates, one in six exactly 0"""
+    gen = torch.Generator().manual_seed(seed)
+    d = torch.randn(n, generator=gen)
+    d[2::6] = 0.0
+    return d
+
+
+def bunch_slots(S):
+    """[lo, hi) sample slots of the bunches of one ray: inside a 16-lane row, across row boundaries, across a wave boundary (S > 64; with
+    S = 100 ray 5 carries sample 512, the start of the second partition batch, in slot 12), up to the ray's last sample"""
+    slots = [(3, 7), (9, 21), (37, 40)]
+    if S > 64:
+        slots.append((58, 71))
+    slots.append((S - 7, S))
+    return slots
+
+
+def bunched_rays(S, seed=9):
+    """-> (rays [8,13], z [8,S], live = 7) float32 for the run-length combining of the levels below scale 3000: bunches of samples 1e-6
+    apart (the same cell on all of those levels) in the slots of `bunch_slots`, single samples in between; rays 3 and 4 are the same
+    ray and ray 4 begins 1e-6 behind ray 3's last sample, so with S = 128 a run crosses sample 512 - a partition batch - as well;
+    every other run that reaches its ray's last sample ends there.  The last ray is dead (n_rays_dev = 7)."""
+    gen = torch.Generator().manual_seed(seed + S)
+    n = 8
+    rays = torch.zeros(n, 13)
+    rays[:, 0:3] = torch.rand(n, 3, generator=gen) * 0.2 - 0.1
+    rays[:, 3:6] = torch.nn.functional.normalize(torch.randn(n, 3, generator=gen), dim=1)
+    rays[4] = rays[3]
+    rays[:, 6:9] = -rays[:, 3:6]
+    rays[:, 11], rays[:, 12] = 0.01, 0.8
+    z = torch.sort(torch.rand(n, S, generator=gen) * 0.6 + 0.05, dim=1).values.double()
+    for lo, hi in bunch_slots(S):
+        z[:, lo:hi] = z[:, lo:lo + 1] + 1e-6 * torch.arange(hi - lo, dtype=torch.float64)[None, :]
+    z[4, 0:4] = z[3, S - 1] + 1e-6 * torch.arange(1, 5, dtype=torch.float64)
+    return rays, z.float(), n - 1
+
+
+# ---------------------------------------------------------------- the record formats, in integers (lnr_density_api.h)
+def f2u(v):
+    return np.asarray(v, np.float32).view(np.uint32)
+
+
+def u2f(u):
+    return np.asarray(u, np.uint32).view(np.float32)
+
+
+def pack26(v):
+    """float32 -> 26 bits (sign, 8 exponent, 17 mantissa bits), round to nearest even"""
+    u = f2u(v).astype(np.uint64)
+    u = (u + 0x1F + ((u >> 6) & 1)) & M32
+    return (u >> 6).astype(np.uint32)
+
+
+def unpack26(p):
+    return u2f((np.asarray(p, np.uint64) << 6 & M32).astype(np.uint32))
+
+
+def pack_pair(pair_idx, v0, v1):
+    """-> (lo, hi):  hi = [v0: 31..6][v1 high 6: 5..0]   lo = [v1 low 20: 31..12][pair index: 11..0]"""
+    a, b = pack26(v0).astype(np.uint64), pack26(v1).astype(np.uint64)
+    lo = ((b << 12) & M32) | (np.asarray(pair_idx, np.uint64) & 0xFFF)
+    hi = ((a << 6) & M32) | (b >> 20)
+    return lo.astype(np.uint32), hi.astype(np.uint32)
+
+
+def unpack_pair(lo, hi):
+    lo, hi = np.asarray(lo, np.uint64), np.asarray(hi, np.uint64)
+    v0 = u2f((hi & 0xFFFFFFC0).astype(np.uint32))
+    v1 = u2f(((((hi & 0x3F) << 26) | ((lo >> 6) & 0x03FFFFC0)) & M32).astype(np.uint32))
+    return (lo & 0xFFF).astype(np.uint32), v0, v1
+
+
+def pack_fx(fx):
+    """fraction in [0,1) -> 28 bits (round half up on the float's bit pattern); may carry to the pattern of 1.0"""
+    return ((f2u(fx).astype(np.uint64) + 8) >> 4).astype(np.uint32)
+
+
+def unpack_fx(fb):
+    return u2f(((np.asarray(fb, np.uint64) & 0x0FFFFFFF) << 4).astype(np.uint32))
+
+
+def pack_xpair(pair_idx, t, a0, a1, fx):
+    """-> (a, b, c):  a = [a0 bits 25..10][t :4][pair index :12]   b = [a0 bits 9..0][a1 bits 25..4]   c = [a1 bits 3..0][fx :28]"""
+    p0, p1, fb = pack26(a0).astype(np.uint64), pack26(a1).astype(np.uint64), pack_fx(fx).astype(np.uint64)
+    a = (np.asarray(pair_idx, np.uint64) & 0xFFF) | ((np.asarray(t, np.uint64) & 0xF) << 12) | ((p0 >> 10) << 16)
+    b = ((p0 & 0x3FF) << 22) | (p1 >> 4)
+    c = ((p1 & 0xF) << 28) | (fb & 0x0FFFFFFF)
+    return (a & M32).astype(np.uint32), (b & M32).astype(np.uint32), (c & M32).astype(np.uint32)
+
+
+def unpack_xpair(a, b, c):
+    a, b, c = np.asarray(a, np.uint64), np.asarray(b, np.uint64), np.asarray(c, np.uint64)
+    a0 = u2f((((((a >> 16) << 10) | (b >> 22)) << 6) & M32).astype(np.uint32))
+    a1 = u2f((((((b & 0x3FFFFF) << 4) | (c >> 28)) << 6) & M32).astype(np.uint32))
+    return (a & 0xFFF).astype(np.uint32), ((a >> 12) & 0xF).astype(np.uint32), a0, a1, unpack_fx(c)
+
+
+def to_fix_generic(v):
+    """__float2ll_rn(v * 2^42): the float32 product (exact below 2^86) rounded to the nearest even integer, saturating at +-2^63"""
+    with np.errstate(over="ignore"):
+        x = np.rint((np.asarray(v, np.float32) * np.float32(2.0 ** FIX_BITS)).astype(np.float64))
+    return np.clip(x, -2.0 ** 63, 2.0 ** 63 - 1024).astype(np.int64)
+
+
+def to_fix_small(v):
+    """lnr_to_fix_small: fma((double) v, 2^42, 1.5 * 2^52) leaves rn(v * 2^42) in the low mantissa bits - while the sum stays in
+    [2^52, 2^53)"""
+    d = np.asarray(v, np.float32).astype(np.float64) * 2.0 ** FIX_BITS + 6755399441055744.0      # the product is exact: one rounding
+    return d.view(np.int64) - np.int64(0x4338000000000000)
+
+
+def to_fix(v):
+    v = np.asarray(v, np.float32)
+    return np.where(np.abs(v) < np.float32(256.0), to_fix_small(v), to_fix_generic(v))
+
+
+def xpair_fix(a0, a1, fx):
+    """the four fixed-point contributions of an unpacked x-pair record: (1-fx) a0, (1-fx) a1 to the x corner, fx a0, fx a1 to x+1;
+    float32 products; the small conversion when both |a0| and |a1| are below 256"""
+    a0, a1, fx = np.asarray(a0, np.float32), np.asarray(a1, np.float32), np.asarray(fx, np.float32)
+    gx = np.float32(1.0) - fx
+    small = np.maximum(np.abs(a0), np.abs(a1)) < np.float32(256.0)
+    prods = [gx * a0, gx * a1, fx * a0, fx * a1]
+    return [np.where(small, to_fix_small(p), to_fix_generic(p)) for p in prods]
+
+
+# ---------------------------------------------------------------- bounds and bookkeeping
+RECORD_REL = 2.0 ** -17           # 26-bit values (2^-18), the 28-bit fx (2^-20), the fp32 products and run sums of a record
+RECORD_REL_F32 = 2.0 ** -21       # n_features == 1: records carry the fp32 value
+FIX_STEP = 2.0 ** -FIX_BITS       # per contribution: 2^-43 rounding, doubled for the two products of an x-pair
+INPUT_ROUNDINGS = 32              # level_input_grad in fp32, any association: F <= 8 multiply-adds of a dot product, a difference, two
+                                  # interpolations (multiply, add each), the scale, 1 - fraction, and the sum over <= 16 levels
+
+
+def level_input_magnitude(lv, table_l, entries, frac, g):
+    """[n]: the sum of the absolute values of the terms level_input_grad adds up, the larger of the three axes - the size an fp32
+    evaluation's rounding errors scale with"""
+    dot = (table_l[entries] * g[:, None, :]).abs().sum(dim=2)
+    one = 1 - frac
+    out = []
+    for axis in range(3):
+        u, v = [a for a in range(3) if a != axis]
+        total = torch.zeros_like(dot[:, 0])
+        for k in range(8):
+            wu = frac[:, u] if (k >> u) & 1 else one[:, u]
+            wv = frac[:, v] if (k >> v) & 1 else one[:, v]
+            total = total + dot[:, k] * (wu * wv)
+        out.append(total * lv.scale * 0.5)
+    return torch.stack(out, dim=1).max(dim=1).values
+
+
+def input_magnitude(grid, table_flat, p, d_feat, live=None):
+    """[n] float64: level_input_magnitude summed over the levels"""
+    F = grid.n_features
+    total = torch.zeros(p.shape[0], dtype=torch.float64)
+    for l, lv in enumerate(grid.levels):
+        cell, frac = locate(lv, p)
+        g = d_feat[:, l * F:(l + 1) * F].double()
+        total = total + level_input_magnitude(lv, table_of(grid, table_flat.double(), l), corner_entries(lv, cell), frac.double(), g)
+    return total if live is None else total * live.double()
+
+
+class EncodeLedger(Ledger):
+    """Ledger with two more kinds of rows: blocks held to bound() + a budget, and element-wise bounds"""
+
+    def __init__(self):
+        super().__init__()
+        self.enc_rows = {}
+
+    def _keep(self, name, ratio, text):
+        row = self.enc_rows.get(name)
+        if row is None or ratio >= row[0]:
+            self.enc_rows[name] = (ratio, text)
+
+    def budget_block(self, name, x, x32, x64, budget, where=""):
+        """|x - x64| <= 4 x (error of x32) + 4 ulp of the block's largest entry + budget"""
+        err, noise, ref_max = block_err(x, x64), block_err(x32, x64), block_max(x64)
+        limit = bound(noise, x64) + budget
+        ratio = err / limit if limit > 0 else (0.0 if err == 0 else float("inf"))
+        norm = ref_max if ref_max > 0 else 1.0
+        self._keep(name, ratio, f"cpu float32 noise {noise / norm:.2e}  budget {budget / norm:.2e}  kernel {err / norm:.2e}  "
+                                f"(of the block's largest entry; worst block {where}: {ratio:.2f} of its bound)")
+        if err > limit:
+            self.failures.append(f"{name} {where}: error {err:.3e} > 4 x {noise:.3e} + 4 ulp of {ref_max:.3e} + {budget:.3e}")
+
+    def elements(self, name, x, x64, limit, where=""):
+        """|x_i - x64_i| <= limit_i for every element; limit_i == 0 asks for equality"""
+        x, x64, limit = x.detach().cpu().double().reshape(-1), x64.detach().cpu().double().reshape(-1), limit.double().reshape(-1)
+        if x.numel() == 0:
+            return
+        err = (x - x64).abs()
+        bad = err > limit
+        ratio = torch.where(limit > 0, err / limit.clamp_min(1e-300), torch.where(err > 0, torch.full_like(err, float("inf")), torch.zeros_like(err)))
+        i = int(ratio.argmax())
+        rel_self = float((err / x64.abs().clamp_min(1e-300))[x64 != 0].max()) if bool((x64 != 0).any()) else 0.0
+        self._keep(name, float(ratio[i]), f"{x.numel()} elements, {int((x64 != 0).sum())} non-zero; worst {float(ratio[i]):.2f} of its bound "
+                                          f"({where} element {i}: error {float(err[i]):.2e}, reference {float(x64[i]):.2e}); largest error relative "
+                                          f"to the element itself {rel_self:.2e}")
+        if bool(bad.any()):
+            j = int(torch.nonzero(bad)[0, 0])
+            self.failures.append(f"{name} {where}: {int(bad.sum())} of {x.numel()} elements beyond their bound, worst {float(ratio[i]):.2f} x; "
+                                 f"first: element {j} kernel {float(x[j]):.9e} reference {float(x64[j]):.9e} bound {float(limit[j]):.3e}")
+
+    def report(self):
+        for name, (ratio, text) in self.enc_rows.items():
+            print(f"FIGURES {name:<44s} {text}")
+        return super().report()
+
+
+def table_entry_limit(A, cnt, ref, record_rel):
+    """A_e x record_rel + n_e x 2^-42 + 4 ulp of |ref_e|"""
+    return A.double() * record_rel + cnt.double() * FIX_STEP + 4.0 * F32_EPS * ref.double().abs()
