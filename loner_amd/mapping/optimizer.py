@@ -23,6 +23,7 @@ Random numbers: by default the kernels' counter-based generator is used (seeded 
 torch's CPU generator).  For parity tests a `draws` object with the reference's draw order
 (per-keyframe randint, then rand, rand, randn) can be injected via `set_draws`.
 """
+import ctypes
 import os
 import time
 from dataclasses import dataclass
@@ -110,6 +111,23 @@ class _LidarLossFn(torch.autograd.Function):
     def backward(ctx, g):
         d_rays, grad_params = ctx.saved_tensors
         return ((g * d_rays).to(ctx.rays_device) if ctx.has[0] else None), (g * grad_params if ctx.has[1] else None), None, None, None
+
+
+class _Phase:
+    """What ONE optimisation phase decides before its first iteration (Optimizer._begin_phase): handed to every piece of the loop and
+    dropped when the phase ends.  Slotted: the loop reads it in every iteration."""
+    __slots__ = (
+        "active", "front_cap",                  # this rank's keyframes of the active window (may be none); sharded: depth slots of a front record
+        "pose_cpu", "free_list",                # the keyframes' own pose tensors, and which of them this phase optimises (and writes back)
+        "pose_dev", "free_rows", "any_free",    # [K,6] poses on the device (what the pose group steps); free_list as a uint8 device mask
+        "tab",                                  # window tables (_window_tables), None without keyframes
+        "param_groups", "base_lrs", "gamma",    # the Adam's groups: lr = base lr * gamma ** iteration
+        "density_params", "density_group",      # the density head's flat parameter; index of its group if this phase steps it, else None
+        "other_groups", "defer_density",        # every other group index; the density step waits in _pending_density for the next forward
+        "poison", "loss_log", "valid_log", "n_it",      # written by the kernels: failure word (int32[2]), [n_it,8] loss terms, [n_it] live rays
+        "occ_every",                            # an occupancy step whenever _global_step is a multiple of it; None without a grid
+        "idle_grad_cleared",                    # (_join_without_rays: an idle rank's zero contribution, cleared once per phase)
+        "side", "grad_event")                   # pipelined loop: the second stream and the input-gradient event, else None
 
 
 class Optimizer:
@@ -277,255 +295,16 @@ class Optimizer:
                 self._optimization_settings = optimizer_settings
             os_ = self._optimization_settings
             os_.freeze_poses = os_.freeze_poses or self._settings.freeze_poses or self._use_gt_poses
-            self._pc = None
-            pc = self._consts()
 
-            if self._settings.samples_selection.strategy == 'OGM':
-                self._ray_sampler.update_occ_grid(self._occupancy_grid.detach())
-            self._model.freeze_sigma_head(os_.freeze_sigma_mlp)
-            self._model.freeze_rgb_head(True)
-            optimize_poses = not os_.freeze_poses
-
-            # The phase is decided on the WHOLE window (latest keyframe, anchoring); in the sharded mode every rank is handed the
-            # same window and keeps the keyframes i mod G == rank of the active list (mapping/sharding.py).  A rank may end up
-            # with none (window smaller than the world size: the first keyframes of every run): it still joins every collective.
-            if os_.latest_kf_only:
-                active_all = [max(keyframe_window, key=lambda kf: float(kf.get_time()))]
-            else:
-                active_all = list(keyframe_window)
-            active = self._dist.owned(active_all) if self._dist is not None else active_all
-            # positions of this rank's keyframes in the window (the sharded far[0] agreement needs them)
-            self._active_order = self._dist.owned_indices(len(active_all)) if self._dist is not None else list(range(len(active_all)))
-            # depth slots of the sharded loop's front record (mapping/sharding.py): the candidate rays of the fullest rank
-            n_sky_cfg = self._settings.num_samples.sky if self._enable_sky_segmentation else 0
-            self._front_cap = self._dist.front_capacity(len(active_all), self._num_lidar_samples + n_sky_cfg) if self._dist is not None else 0
-            for kf in active:
-                if not kf.is_anchored:
-                    kf.get_lidar_pose().set_fixed(not optimize_poses)
-            tracking = (not os_.freeze_poses) and os_.freeze_rgb_mlp and os_.freeze_sigma_mlp
-
-            sigma_params = self._model.get_sigma_parameters()
-            groups = []
-            density_group = None
-            if not tracking and sigma_params:
-                density_group = len(groups)
-                groups.append({'params': sigma_params, 'lr': self._model_config.train.lrate_sigma_mlp})
-            # poses are optimised on the device as one [K,6] tensor (rows of fixed/anchored keyframes get zero gradient).
-            # Which pose a keyframe's rays are built from is the reference's choice: the ground-truth pose when the optimiser was
-            # constructed with use_gt_poses (keyframe.py:83-86 via optimizer.py:305), else the lidar pose.  A pose that is NOT optimised
-            # in this phase enters as the 4x4 matrix its get_transformation_matrix() hands out - which is what the reference's ray
-            # builder reads (pose.py:140-144: for a fixed pose that is the matrix cached at construction, whatever happened to the
-            # 6-vector since) - not as a matrix re-derived from get_pose_tensor().
-            pose_objs = [(kf._frame._gt_lidar_pose if self._use_gt_poses else kf.get_lidar_pose()) for kf in active]
-            free_list = [bool(optimize_poses and not kf.is_anchored) for kf in active]
-            pose_cpu = [p.get_pose_tensor() for p in pose_objs]
-            if active and all(p.device.type == "cpu" for p in pose_cpu):
-                pose_dev = torch.stack([p.detach().float() for p in pose_cpu]).to(self._device).contiguous()      # one upload
-            elif active:
-                pose_dev = torch.stack([p.detach().to(self._device, torch.float32) for p in pose_cpu]).contiguous()
-            else:
-                pose_dev = torch.zeros(0, 6, device=self._device)
-            free_rows = torch.tensor(free_list, device=self._device).to(torch.uint8)
-            tab = self._window_tables(active) if active else None
-            if tab is not None and not all(free_list):
-                with torch.no_grad():
-                    fixed = [(torch.zeros(12) if fr else p.get_transformation_matrix().detach().float().cpu()[:3, :4].reshape(12))
-                             for p, fr in zip(pose_objs, free_list)]
-                tab.fixed_T12 = torch.stack(fixed).to(self._device).contiguous()
-                tab.free_col = free_rows.bool()[:, None]
-                tab.any_free = any(free_list)
-            elif tab is not None:
-                tab.fixed_T12 = None
-            any_free = bool(optimize_poses and any(not kf.is_anchored for kf in active))
-            pose_dev.requires_grad_(any_free)
-            if any_free:
-                groups.append({'params': [pose_dev], 'lr': self._model_config.train.lrate_pose})
-            # always an Adam, like the reference (Mapper.build_ckpt reads its state_dict unconditionally, mapper.py:161-175)
-            # failure guard: {code, iteration} written by the loss / pose-gradient kernels of the iteration that fails; every
-            # step kernel after it does nothing (the reference raises before optimizer.step(), optimizer.py:368-376,590)
-            poison = torch.zeros(2, device=self._device, dtype=torch.int32)
-            self._poison = poison
-            self._idle_grad_cleared = False              # (_join_without_rays: an idle rank's zero contribution, cleared once per phase)
-            self._optimizer = HipAdam(groups if groups else [{'params': []}], poison=poison)
-            gamma = float(self._model_config.train.lrate_gamma)
-            base_lrs = [g['lr'] for g in groups]
-            # the density step may be deferred (see below) when the density parameters are trained in this phase
-            if os_.freeze_sigma_mlp or not self._defer_density_step:
-                density_group = None
-            n_it = os_.num_iterations
-            loss_log = torch.zeros(max(n_it, 1), 8, device=self._device)
-            valid_log = torch.zeros(max(n_it, 1), device=self._device, dtype=torch.int32)
-
-            # Pipelined loop (one GPU, keyframes to work on): the input gradient of an iteration is complete when the encode backward
-            # ends, while the table-gradient reduce, the weight-gradient fold and the (deferred) density Adam step still follow.
-            # Everything that depends on the input gradient only - pose gradient, pose step, occupancy step - and the whole front
-            # end of the NEXT iteration (pose -> [R|t], ray draw / build / compaction, loss normalisers, sampler: ~0.2 ms of small,
-            # latency-bound kernels) runs on a second stream beside that tail; the streams meet again in front of the next density
-            # forward.  Same kernels, same arguments, same order of the random draws: the results do not change.
-            # (measured on the bench window: 2.35 -> 2.33 ms per iteration - the reduce occupies every wave slot, so the side stream
-            # mostly fills its tail; with a single keyframe the two extra stream hand-overs cost more than they hide: 0.50 -> 0.51 ms)
-            pipelined = len(active) >= 2 and self._dist is None and self._pipeline and profiler is None and self.should_enable_lidar()
-            if pipelined:
-                main = torch.cuda.current_stream(self._device)
-                if self._side_stream is None:
-                    self._side_stream = torch.cuda.Stream(self._device)     # (a high-priority stream measured the same: 2.32 ms)
-                    self._grad_event = torch.cuda.Event()
-                    self._grad_event.record(main)                   # (torch creates the handle at the first record)
-                side, ev = self._side_stream, self._grad_event
-                sp = sigma_params[0] if sigma_params else self._model.nerf_model._model_sigma.params
-
-                def front_end(it_next):
-                    b = self._build_window_rays(active, pose_dev, tab, n_out=valid_log[it_next:it_next + 1])
-                    b["front"] = self._sample_front(b["rays"], b["depths"], b["n_dev"], pre=b)
-                    return b
-                batch = front_end(0) if n_it > 0 else None
-                for it_idx in range(n_it):
-                    out = self._loss_and_grads(batch["rays"], batch["depths"], sp, it_idx, want_ray_grads=any_free,
-                                               want_param_grads=not os_.freeze_sigma_mlp, n_rays_dev=batch["n_dev"],
-                                               loss_out=loss_log[it_idx], accumulate_into_param_grad=True, want_stats=False,
-                                               defer_grad_wait=True, poison=poison, front=batch["front"], input_grad_event=ev,
-                                               defer_weight_fold=density_group is not None)
-                    side.wait_event(ev)
-                    with torch.cuda.stream(side):
-                        # (only when the density step is deferred: it then waits for this stream; a step taken right away on the main
-                        # stream must find the folded gradient there)
-                        if out["grad_params"] is not None and density_group is not None:
-                            # the weight-gradient slabs of the MLP backward, folded here instead of behind the table-gradient reduce
-                            ops.density_fold_weight_grads(self._model.nerf_model._model_sigma.spec, out["grad_params"],
-                                                          batch["rays"].shape[0] * batch["front"]["z"].shape[1],
-                                                          overwrite_grad=self._overwrite_grads)
-                        if any_free:
-                            self._pose_backward(batch, out["d_rays"], pose_dev, free_rows, poison=poison, poison_tag=it_idx)
-                        if groups:
-                            for g, lr0 in zip(self._optimizer.param_groups, base_lrs):
-                                g['lr'] = lr0 * (gamma ** it_idx)
-                            dg = density_group if density_group is not None else \
-                                (0 if (sigma_params and not tracking and not os_.freeze_sigma_mlp) else None)
-                            self._optimizer.step_now(zero_grad=True, groups=tuple(i for i in range(len(groups)) if i != dg))
-                        else:
-                            dg = None
-                        if pc["ogm"] and self._global_step % pc["occ_every"] == 0:
-                            self._step_occupancy_grid()
-                        if it_idx + 1 < n_it:
-                            batch = front_end(it_idx + 1)
-                    if groups and dg is not None:
-                        if density_group is None:
-                            main.wait_stream(side)                        # (the pose check of this iteration may still mark the failure word)
-                            self._step_density(out["grad_work"], dg)      # not deferred: behind the reduce, on the main stream
-                        else:
-                            self._pending_density = (out["grad_work"], density_group, self._optimizer.param_groups[density_group]['lr'])
-                    main.wait_stream(side)
-                    self._global_step += 1
-                    if self._progress_bar is not None:
-                        self._progress_bar.update()
-                n_loop = 0
-            else:
-                n_loop = n_it
-            for it_idx in range(n_loop):
-                if not self.should_enable_lidar():
-                    break
-                if active:
-                    batch = self._build_window_rays(active, pose_dev, tab, n_out=valid_log[it_idx:it_idx + 1])
-                    out = self._loss_and_grads(batch["rays"], batch["depths"], sigma_params[0] if sigma_params else
-                                               self._model.nerf_model._model_sigma.params, it_idx, want_ray_grads=any_free,
-                                               want_param_grads=not os_.freeze_sigma_mlp, n_rays_dev=batch["n_dev"],
-                                               loss_out=loss_log[it_idx], accumulate_into_param_grad=True, want_stats=False,
-                                               defer_grad_wait=True, poison=poison, shard_segments=(batch["seg_start"], tab.seg_order_c), pre=batch)
-                else:
-                    out = self._join_without_rays(sigma_params[0] if sigma_params else None, want_param_grads=not os_.freeze_sigma_mlp)
-                if any_free:
-                    self._pose_backward(batch, out["d_rays"], pose_dev, free_rows, poison=poison, poison_tag=it_idx)
-                if groups:
-                    for g, lr0 in zip(self._optimizer.param_groups, base_lrs):
-                        g['lr'] = lr0 * (gamma ** it_idx)
-                    if density_group is None:
-                        dg = 0 if (sigma_params and not tracking and not os_.freeze_sigma_mlp) else None     # stepped right away
-                        self._optimizer.step_now(zero_grad=True, groups=tuple(i for i in range(len(groups)) if i != dg))
-                        if dg is not None:
-                            self._step_density(out["grad_work"], dg)
-                    else:
-                        # The density step is deferred to just before the next density forward (_flush_density_step): nothing in
-                        # between reads the density parameters - pose gradient and pose step, occupancy step, the next batch's ray
-                        # build, compaction, counts and sampling - so in the sharded mode all of that runs beside the gradient
-                        # all-reduce instead of behind it.  Same arithmetic, same order per parameter group.
-                        self._optimizer.step_now(zero_grad=True, groups=tuple(i for i in range(len(groups)) if i != density_group))
-                        self._pending_density = (out["grad_work"], density_group, self._optimizer.param_groups[density_group]['lr'])
-                if self.should_enable_lidar() and pc["ogm"] and self._global_step % pc["occ_every"] == 0:
-                    self._step_occupancy_grid()
-                self._global_step += 1
-                if profiler is not None:
-                    profiler.step()
-                if self._progress_bar is not None:
-                    self._progress_bar.update()
-
+            ph = self._begin_phase(keyframe_window, os_, profiler)
+            if ph.side is not None:
+                self._run_pipelined(ph)
+            elif self.should_enable_lidar():            # (nothing to optimise otherwise: the phase ends as it began)
+                self._run_single_stream(ph, profiler)
             self._flush_density_step()
-            # ---- one host sync per phase.  The checks the reference makes in every iteration (:368-374,:590) were made on the
-            # device, by the kernels of that iteration; the state below is the one the failing iteration started from ----
-            if self._dist is not None:
-                # A failure on any rank is everybody's.  The guarantee "parameters as the failing iteration began" is a SINGLE-GPU one:
-                # the word is per rank until here, so the healthy ranks kept stepping (with the failing rank's non-finite gradient in
-                # their all-reduce) - the run is lost either way.  What all ranks agree on is WHICH failure to report: the earliest
-                # iteration, with the code that belongs to it (one packed value, so code and iteration cannot come from different ranks).
-                poison.copy_(self._dist.earliest_failure(poison))
-            # Everything the host needs from the phase travels in ONE device -> host copy (round 3 made eight small ones, each a
-            # sync: ~1 ms per phase together with the per-keyframe pose copies, 2 % of a 20-iteration phase): the failure word, the
-            # per-iteration live-ray counts and loss terms, the poses, a finite-poses flag and the origin check of the last batch.
-            n_log = max(n_it, 1)
-            res = self._results_lidar
-            if active and n_it and res is not None:
-                last = res["rays"]
-                n_live_t = res["n_rays_dev"].reshape(1).float() if res["n_rays_dev"] is not None else \
-                    torch.full((1,), float(last.shape[0]), device=self._device)
-                row = torch.arange(last.shape[0], device=self._device, dtype=torch.float32)[:, None]
-                outside = ((last[:, :3].abs() > 1) & (row < n_live_t)).any().reshape(1).float()
-            else:
-                outside = torch.zeros(1, device=self._device)
-            pose_ok = torch.isfinite(pose_dev.detach()).all().reshape(1).float()
-            # (the integer words - failure code and iteration, live-ray counts - travel as their BIT PATTERNS inside the float32 buffer,
-            # so they are exact whatever their size; the pieces are split by the sizes of the tensors that were concatenated)
-            pieces = [poison.view(torch.float32), valid_log.view(torch.float32), loss_log.detach().reshape(-1),
-                      pose_dev.detach().reshape(-1).float(), pose_ok, outside]
-            host = torch.cat(pieces).cpu().split([p_.numel() for p_ in pieces])
-            code, failed_it = (int(v) for v in host[0].view(torch.int32))
-            valid_host = host[1].view(torch.int32).float()
-            loss_terms_host = host[2].reshape(loss_log.shape).clone()
-            pose_host = host[3].reshape(pose_dev.shape)
-            pose_finite, origins_outside = bool(host[4][0] != 0), bool(host[5][0] != 0)
-            self._poison = None
-            self._model.nerf_model.warn_if_clipped(self._device)      # nerf_tcnn.py:70-78, once per phase instead of per forward
-            loss_host = loss_terms_host[:, 0]
-
-            def hand_poses_back():
-                with torch.no_grad():
-                    for k, p_ in enumerate(pose_cpu):
-                        if free_list[k]:        # (the others were not stepped: their tensors are left exactly as they are)
-                            p_.data.copy_(pose_host[k].to(p_.device))
-            if code != 0:
-                hand_poses_back()               # the poses of the last good iteration, like every other phase end
-                self.last_failure = {"code": code, "iteration": failed_it}
-                if code == hip.POISON_NAN_LOSS:
-                    raise AssertionError("NaN Loss Encountered")
-                if code == hip.POISON_POSE_GRAD:
-                    raise RuntimeError("Fatal: Encountered invalid gradient in pose.")
-                raise RuntimeError("Fatal: Encountered invalid pose tensor.")
-            if n_it and torch.isnan(loss_host).any():
-                raise AssertionError("NaN Loss Encountered")
-            if any_free and not pose_finite:
-                raise RuntimeError("Fatal: Encountered invalid pose tensor.")
-            # the reference asserts on every ray build that the ray origins lie inside the world cube (ray_utils.py:301-303);
-            # here once per phase, on the last batch (all rays of a keyframe share its origin)
-            if origins_outside:
-                raise AssertionError("ray origins are outside the world cube")
-            hand_poses_back()
-            sigma = self._model.nerf_model._model_sigma.params
-            if sigma.grad is not None and os_.freeze_sigma_mlp:
-                sigma.grad = None
-            elif sigma.grad is not None and self._overwrite_grads and n_it:
-                sigma.grad.zero_()              # as after the last zero_grad of the phase (one fill per phase instead of one per iteration)
-            losses_log.append(loss_host.tolist())
-            depth_eps_log.append((loss_terms_host[:, 4] / valid_host.clamp(min=1)).tolist())
-            self._depth_eps = depth_eps_log[-1][-1] if n_it else None
-            self.last_stats = {"n_valid_rays": int(valid_host.sum().item()), "iterations": n_it, "loss_terms": loss_terms_host}
+            losses, depth_eps = self._end_phase(ph)
+            losses_log.append(losses)
+            depth_eps_log.append(depth_eps)
 
         if self._settings.debug.log_losses:
             for name, logs in (("losses", losses_log), ("depth_eps", depth_eps_log)):
@@ -536,10 +315,255 @@ class Optimizer:
                         f.write("\n".join(str(v) for v in log))
         return None
 
+    def _begin_phase(self, keyframe_window, os_, profiler) -> _Phase:
+        """Everything a phase decides before its first iteration, from the active keyframes to the Adam over this phase's parameter
+        groups, on the caller's stream.  Keyframes, poses and settings are read through the members the reference's classes have;
+        nothing of the phase is written onto them."""
+        ph = _Phase()
+        self._pc = None
+        pc = self._consts()
+        if pc["ogm"]:
+            self._ray_sampler.update_occ_grid(self._occupancy_grid.detach())
+        self._model.freeze_sigma_head(os_.freeze_sigma_mlp)
+        self._model.freeze_rgb_head(True)
+        optimize_poses = not os_.freeze_poses
+
+        # The phase is decided on the WHOLE window (latest keyframe, anchoring); in the sharded mode every rank is handed the
+        # same window and keeps the keyframes i mod G == rank of the active list (mapping/sharding.py).  A rank may end up
+        # with none (window smaller than the world size: the first keyframes of every run): it still joins every collective.
+        if os_.latest_kf_only:
+            active_all = [max(keyframe_window, key=lambda kf: float(kf.get_time()))]
+        else:
+            active_all = list(keyframe_window)
+        if self._dist is not None:
+            active = self._dist.owned(active_all)
+            order = self._dist.owned_indices(len(active_all))       # positions of this rank's keyframes in the window
+            # depth slots of the sharded loop's front record (mapping/sharding.py): the candidate rays of the fullest rank
+            n_sky_cfg = self._settings.num_samples.sky if self._enable_sky_segmentation else 0
+            ph.front_cap = self._dist.front_capacity(len(active_all), self._num_lidar_samples + n_sky_cfg)
+        else:
+            active, order, ph.front_cap = active_all, list(range(len(active_all))), 0
+        ph.active = active
+        for kf in active:
+            if not kf.is_anchored:
+                kf.get_lidar_pose().set_fixed(not optimize_poses)
+
+        # WHICH density group is stepped, and WHEN, is decided here and nowhere else.  The density head has one flat parameter; it
+        # is trained unless the phase freezes it (a tracking phase - poses free, both heads frozen - always does) and is then
+        # group 0, stepped by _step_density_now_or_later: deferred unless _defer_density_step is off.
+        sigma_params = self._model.get_sigma_parameters()
+        groups = [{'params': sigma_params, 'lr': self._model_config.train.lrate_sigma_mlp}] if sigma_params else []
+        ph.density_params = self._model.nerf_model._model_sigma.params
+        ph.density_group = 0 if sigma_params else None
+        ph.defer_density = bool(sigma_params) and self._defer_density_step
+        # poses are optimised on the device as one [K,6] tensor (rows of fixed/anchored keyframes get zero gradient).
+        # Which pose a keyframe's rays are built from is the reference's choice: the ground-truth pose when the optimiser was
+        # constructed with use_gt_poses (keyframe.py:83-86 via optimizer.py:305), else the lidar pose.  A pose that is NOT optimised
+        # in this phase enters as the 4x4 matrix its get_transformation_matrix() hands out - which is what the reference's ray
+        # builder reads (pose.py:140-144: for a fixed pose that is the matrix cached at construction, whatever happened to the
+        # 6-vector since) - not as a matrix re-derived from get_pose_tensor().
+        pose_objs = [(kf._frame._gt_lidar_pose if self._use_gt_poses else kf.get_lidar_pose()) for kf in active]
+        ph.free_list = free_list = [bool(optimize_poses and not kf.is_anchored) for kf in active]
+        ph.pose_cpu = pose_cpu = [p.get_pose_tensor() for p in pose_objs]
+        if active and all(p.device.type == "cpu" for p in pose_cpu):
+            pose_dev = torch.stack([p.detach().float() for p in pose_cpu]).to(self._device).contiguous()      # one upload
+        elif active:
+            pose_dev = torch.stack([p.detach().to(self._device, torch.float32) for p in pose_cpu]).contiguous()
+        else:
+            pose_dev = torch.zeros(0, 6, device=self._device)
+        ph.pose_dev = pose_dev
+        ph.free_rows = free_rows = torch.tensor(free_list, device=self._device).to(torch.uint8)
+        ph.tab = tab = self._window_tables(active, order) if active else None
+        if tab is not None and not all(free_list):
+            with torch.no_grad():
+                fixed = [(torch.zeros(12) if fr else p.get_transformation_matrix().detach().float().cpu()[:3, :4].reshape(12))
+                         for p, fr in zip(pose_objs, free_list)]
+            tab.fixed_T12 = torch.stack(fixed).to(self._device).contiguous()
+            tab.free_col = free_rows.bool()[:, None]
+            tab.any_free = any(free_list)
+        ph.any_free = any(free_list)
+        pose_dev.requires_grad_(ph.any_free)
+        if ph.any_free:
+            groups.append({'params': [pose_dev], 'lr': self._model_config.train.lrate_pose})
+        # failure guard: {code, iteration} written by the loss / pose-gradient kernels of the iteration that fails; every
+        # step kernel after it does nothing (the reference raises before optimizer.step(), optimizer.py:368-376,590)
+        ph.poison = self._poison = torch.zeros(2, device=self._device, dtype=torch.int32)
+        # always an Adam, like the reference (Mapper.build_ckpt reads its state_dict unconditionally, mapper.py:161-175)
+        self._optimizer = HipAdam(groups if groups else [{'params': []}], poison=ph.poison)
+        ph.param_groups, ph.base_lrs = self._optimizer.param_groups, [g['lr'] for g in groups]
+        ph.gamma = float(self._model_config.train.lrate_gamma)
+        ph.other_groups = tuple(i for i in range(len(groups)) if i != ph.density_group)
+        ph.n_it = n_it = os_.num_iterations
+        ph.loss_log = torch.zeros(max(n_it, 1), 8, device=self._device)
+        ph.valid_log = torch.zeros(max(n_it, 1), device=self._device, dtype=torch.int32)
+        ph.occ_every = pc["occ_every"] if pc["ogm"] else None
+        ph.idle_grad_cleared, ph.side, ph.grad_event = False, None, None
+        if len(active) >= 2 and self._dist is None and self._pipeline and profiler is None and self.should_enable_lidar():
+            if self._side_stream is None:       # the pipelined loop (_run_pipelined)
+                self._side_stream = torch.cuda.Stream(self._device)     # (a high-priority stream measured the same: 2.32 ms)
+                self._grad_event = torch.cuda.Event()
+                self._grad_event.record(torch.cuda.current_stream(self._device))     # (torch creates the handle at the first record)
+            ph.side, ph.grad_event = self._side_stream, self._grad_event
+        return ph
+
+    def _input_grad_tail(self, ph, batch, d_rays, it_idx):
+        """What follows from the INPUT gradient of iteration it_idx alone: pose gradient, learning-rate decay, the step of every group
+        but the density group.  On the current stream (pipelined: the side stream, behind the input-gradient event); may not read
+        the density gradient or parameters, whose reduce / exchange / step is still running."""
+        if ph.any_free:
+            self._pose_backward(ph, batch, d_rays, it_idx)
+        if ph.base_lrs:
+            decay = ph.gamma ** it_idx
+            for g, lr0 in zip(ph.param_groups, ph.base_lrs):
+                g['lr'] = lr0 * decay
+            self._optimizer.step_now(zero_grad=True, groups=ph.other_groups)
+
+    def _step_density_now_or_later(self, ph, grad_work, join=None):
+        """The Adam step of the density group, if the phase trains it, on the current (main) stream once _input_grad_tail has set the
+        iteration's learning rate.  Deferred: to just before the next density forward (_flush_density_step): nothing in between
+        reads the density parameters - pose gradient and pose step, occupancy step, the next batch's ray build, compaction, counts
+        and sampling - so in the sharded mode all of that runs beside the gradient all-reduce instead of behind it.  Same arithmetic,
+        same order per parameter group.  Not deferred: now, behind the reduce, and behind `join`, the pipelined loop's side stream
+        (the pose check of this iteration may still mark the failure word)."""
+        if ph.defer_density:
+            self._pending_density = (grad_work, ph.density_group, ph.param_groups[ph.density_group]['lr'])
+        elif ph.density_group is not None:
+            if join is not None:
+                torch.cuda.current_stream(self._device).wait_stream(join)
+            self._step_density(grad_work, ph.density_group)
+
+    def _occupancy_step(self, ph):
+        """On the current stream; reads the rays and samples of the last loss evaluation, never the density parameters."""
+        if ph.occ_every is not None and self._global_step % ph.occ_every == 0:
+            self._step_occupancy_grid()
+
+    def _run_single_stream(self, ph, profiler):
+        """The loop on the caller's stream alone: one keyframe, sharded runs, under the profiler.  The occupancy step FOLLOWS the
+        density step."""
+        batch = None
+        for it_idx in range(ph.n_it):
+            if ph.active:
+                batch = self._front_end(ph, it_idx)
+                out = self._loss_and_grads(batch["rays"], batch["depths"], ph.density_params, it_idx, want_ray_grads=ph.any_free,
+                                           want_param_grads=ph.density_group is not None, loop=(ph, batch))
+            else:
+                out = self._join_without_rays(ph)
+            self._input_grad_tail(ph, batch, out["d_rays"], it_idx)
+            self._step_density_now_or_later(ph, out["grad_work"])
+            self._occupancy_step(ph)
+            self._global_step += 1
+            if profiler is not None:
+                profiler.step()
+            if self._progress_bar is not None:
+                self._progress_bar.update()
+
+    def _run_pipelined(self, ph):
+        """The loop on two streams (one GPU, keyframes to work on): the input gradient of an iteration is complete when the encode
+        backward ends, while the table-gradient reduce, the weight-gradient fold and the (deferred) density Adam step still follow.
+        Everything that depends on the input gradient only - pose gradient, pose step, occupancy step (here BEFORE the density step)
+        - and the whole front end of the NEXT iteration (pose -> [R|t], ray draw / build / compaction, loss normalisers, sampler:
+        ~0.2 ms of small, latency-bound kernels) runs on a second stream beside that tail; the streams meet again in front of the
+        next density forward.  Same kernels, same arguments, same order of the random draws: the results do not change.
+        (measured on the bench window: 2.35 -> 2.33 ms per iteration - the reduce occupies every wave slot, so the side stream
+        mostly fills its tail; with a single keyframe the two extra stream hand-overs cost more than they hide: 0.50 -> 0.51 ms)"""
+        main, side = torch.cuda.current_stream(self._device), ph.side
+        batch = self._front_end(ph, 0) if ph.n_it > 0 else None
+        for it_idx in range(ph.n_it):
+            out = self._loss_and_grads(batch["rays"], batch["depths"], ph.density_params, it_idx, want_ray_grads=ph.any_free,
+                                       want_param_grads=ph.density_group is not None, loop=(ph, batch))
+            side.wait_event(ph.grad_event)
+            with torch.cuda.stream(side):
+                # (only when the density step is deferred: it then waits for this stream; a step taken right away on the main
+                # stream must find the folded gradient there)
+                if out["grad_params"] is not None and ph.defer_density:
+                    # the weight-gradient slabs of the MLP backward, folded here instead of behind the table-gradient reduce
+                    ops.density_fold_weight_grads(self._model.nerf_model._model_sigma.spec, out["grad_params"],
+                                                  batch["rays"].shape[0] * batch["front"]["z"].shape[1],
+                                                  overwrite_grad=self._overwrite_grads)
+                self._input_grad_tail(ph, batch, out["d_rays"], it_idx)
+                self._occupancy_step(ph)
+                if it_idx + 1 < ph.n_it:
+                    batch = self._front_end(ph, it_idx + 1)
+            self._step_density_now_or_later(ph, out["grad_work"], join=side)
+            main.wait_stream(side)
+            self._global_step += 1
+            if self._progress_bar is not None:
+                self._progress_bar.update()
+
+    def _end_phase(self, ph):
+        """One host sync per phase, on the caller's stream, after the last (flushed) density step.  The checks the reference makes
+        in every iteration (:368-374,:590) were made on the device, by the kernels of that iteration; the state handed back is the
+        one the failing iteration started from.  -> (loss per iteration, depth eps per iteration) for the loss logs."""
+        poison, pose_dev, n_it = ph.poison, ph.pose_dev, ph.n_it
+        if self._dist is not None:
+            # A failure on any rank is everybody's.  The guarantee "parameters as the failing iteration began" is a SINGLE-GPU one:
+            # the word is per rank until here, so the healthy ranks kept stepping (with the failing rank's non-finite gradient in
+            # their all-reduce) - the run is lost either way.  What all ranks agree on is WHICH failure to report: the earliest
+            # iteration, with the code that belongs to it (one packed value, so code and iteration cannot come from different ranks).
+            poison.copy_(self._dist.earliest_failure(poison))
+        # Everything the host needs from the phase travels in ONE device -> host copy (round 3 made eight small ones, each a
+        # sync: ~1 ms per phase together with the per-keyframe pose copies, 2 % of a 20-iteration phase): the failure word, the
+        # per-iteration live-ray counts and loss terms, the poses, a finite-poses flag and the origin check of the last batch.
+        res = self._results_lidar
+        if ph.active and n_it and res is not None:
+            last = res["rays"]
+            n_live_t = res["n_rays_dev"].reshape(1).float() if res["n_rays_dev"] is not None else \
+                torch.full((1,), float(last.shape[0]), device=self._device)
+            row = torch.arange(last.shape[0], device=self._device, dtype=torch.float32)[:, None]
+            outside = ((last[:, :3].abs() > 1) & (row < n_live_t)).any().reshape(1).float()
+        else:
+            outside = torch.zeros(1, device=self._device)
+        pose_ok = torch.isfinite(pose_dev.detach()).all().reshape(1).float()
+        # (the integer words - failure code and iteration, live-ray counts - travel as their BIT PATTERNS inside the float32 buffer,
+        # so they are exact whatever their size; the pieces are split by the sizes of the tensors that were concatenated)
+        pieces = [poison.view(torch.float32), ph.valid_log.view(torch.float32), ph.loss_log.detach().reshape(-1),
+                  pose_dev.detach().reshape(-1).float(), pose_ok, outside]
+        host = torch.cat(pieces).cpu().split([p_.numel() for p_ in pieces])
+        code, failed_it = (int(v) for v in host[0].view(torch.int32))
+        valid_host = host[1].view(torch.int32).float()
+        loss_terms_host = host[2].reshape(ph.loss_log.shape).clone()
+        pose_host = host[3].reshape(pose_dev.shape)
+        pose_finite, origins_outside = bool(host[4][0] != 0), bool(host[5][0] != 0)
+        self._poison = None
+        self._model.nerf_model.warn_if_clipped(self._device)      # nerf_tcnn.py:70-78, once per phase instead of per forward
+        loss_host = loss_terms_host[:, 0]
+
+        def hand_poses_back():
+            with torch.no_grad():
+                for k, p_ in enumerate(ph.pose_cpu):
+                    if ph.free_list[k]:        # (the others were not stepped: their tensors are left exactly as they are)
+                        p_.data.copy_(pose_host[k].to(p_.device))
+        if code != 0:
+            hand_poses_back()               # the poses of the last good iteration, like every other phase end
+            self.last_failure = {"code": code, "iteration": failed_it}
+            if code == hip.POISON_NAN_LOSS:
+                raise AssertionError("NaN Loss Encountered")
+            if code == hip.POISON_POSE_GRAD:
+                raise RuntimeError("Fatal: Encountered invalid gradient in pose.")
+            raise RuntimeError("Fatal: Encountered invalid pose tensor.")
+        if n_it and torch.isnan(loss_host).any():
+            raise AssertionError("NaN Loss Encountered")
+        if ph.any_free and not pose_finite:
+            raise RuntimeError("Fatal: Encountered invalid pose tensor.")
+        # the reference asserts on every ray build that the ray origins lie inside the world cube (ray_utils.py:301-303);
+        # here once per phase, on the last batch (all rays of a keyframe share its origin)
+        if origins_outside:
+            raise AssertionError("ray origins are outside the world cube")
+        hand_poses_back()
+        sigma = ph.density_params
+        if sigma.grad is not None and ph.density_group is None:      # (frozen in this phase)
+            sigma.grad = None
+        elif sigma.grad is not None and self._overwrite_grads and n_it:
+            sigma.grad.zero_()              # as after the last zero_grad of the phase (one fill per phase instead of one per iteration)
+        depth_eps = (loss_terms_host[:, 4] / valid_host.clamp(min=1)).tolist()
+        self._depth_eps = depth_eps[-1] if n_it else None
+        self.last_stats = {"n_valid_rays": int(valid_host.sum().item()), "iterations": n_it, "loss_terms": loss_terms_host}
+        return loss_host.tolist(), depth_eps
+
     # -------------------------------------------------------------------------------------------
-    def _window_tables(self, active):
+    def _window_tables(self, active, order_of):
         """Static per-window segment tables (built once per optimisation phase): per keyframe one lidar segment and,
-        when sky segmentation is on, one sky segment (keyframe.py:91-100)."""
+        when sky segmentation is on, one sky segment (keyframe.py:91-100).  order_of: window position of every active keyframe."""
         dev = self._device
         n_lidar = self._num_lidar_samples
         n_sky = self._settings.num_samples.sky if self._enable_sky_segmentation else 0
@@ -557,12 +581,11 @@ class Optimizer:
                 is_sky.append(True); lens.append(sdirs.shape[1])
         tab = ops.WindowTables(dirs_l, dist_l, const_l, counts, poses)
         tab.is_sky, tab.seg_kf, tab.lens, tab.dirs_list = is_sky, poses, lens, dirs_l
-        # window position of every segment (lidar before sky inside a keyframe): the order of the single-GPU batch
-        order_of = getattr(self, "_active_order", None) or list(range(len(active)))
+        # window position of every segment (lidar before sky inside a keyframe): the order of the single-GPU batch (the sharded
+        # far[0] agreement needs it)
         tab.seg_order = [2 * order_of[k] + (1 if sky_ else 0) for k, sky_ in zip(poses, is_sky)]
-        import ctypes as _C
-        tab.seg_order_c = (_C.c_int32 * len(tab.seg_order))(*tab.seg_order)      # (for lnr_shard_front_pack, every iteration)
-        tab.fixed_T12 = None           # set per phase: the matrices of the poses that are not optimised (_do_iterate_optimizer)
+        tab.seg_order_c = (ctypes.c_int32 * len(tab.seg_order))(*tab.seg_order)      # (for lnr_shard_front_pack, every iteration)
+        tab.fixed_T12 = None           # set per phase: the matrices of the poses that are not optimised (_begin_phase)
         tab.seg_kf_dev = torch.tensor(poses, device=dev)
         tab.lidar_seg_mask = torch.tensor([0.0 if s else 1.0 for s in is_sky], device=dev)[:, None]
         tab.has_sky = any(is_sky)
@@ -592,31 +615,33 @@ class Optimizer:
             out.append(idx.to(self._device))
         return torch.cat(out)
 
-    def _build_window_rays(self, active, pose_dev, tab, n_out=None):
-        """optimizer.py:285-340 on the device: pose -> [R|t], index draw + ray build for the whole window in one
-        launch, one order-preserving compaction.  n_out: where the live ray count goes (a row of the phase's log)."""
+    def _front_end(self, ph, it_idx):
+        """The part of iteration it_idx that does not touch the density parameters, on the current stream (the side stream where the
+        pipelined loop runs it ahead).  optimizer.py:285-340 on the device: pose -> [R|t], index draw + ray build for the whole window
+        in one launch, one order-preserving compaction (live ray count -> row it_idx of the phase's log), then _sample_front.  Draws
+        from torch's CPU generator once for the ray build, then once in the sampler."""
+        tab, pose_dev, n_out = ph.tab, ph.pose_dev, ph.valid_log[it_idx:it_idx + 1]
         if tab.fixed_T12 is not None and not tab.any_free:
             T12 = tab.fixed_T12                            # nothing is optimised (e.g. the anchored keyframe of a one-keyframe shard)
         else:
             T12 = ops.pose_forward(pose_dev)
             if tab.fixed_T12 is not None:                  # poses that are not optimised in this phase: the matrix their Pose hands out
                 T12 = torch.where(tab.free_col, T12, tab.fixed_T12)
-        rr = self._ray_range_f
-        index = self._draw_window_indices(active, tab)
+        index = self._draw_window_indices(ph.active, tab)
         seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if index is None else 0
-        rays_c, depths_c, keep, src_c = ops.build_window_rays(tab, T12, rr, self._scale_f, self._shift_f, index=index, seed=seed)
+        rays_c, depths_c, keep, src_c = ops.build_window_rays(tab, T12, self._ray_range_f, self._scale_f, self._shift_f, index=index, seed=seed)
         # (the table's ctypes arrays: built once per phase.)  The compaction launch also delivers what the loss needs next from the compacted
         # batch - the normalisers {#rays, #opaque rays}, or this rank's front record in the sharded loop: one launch instead of two
-        if self._dist is not None:
-            rays, depths, src, out_seg, n_dev, rec = ops.compact_rays(rays_c, depths_c, keep, src_c, tab.seg_start, n_out=n_out,
-                                                                      front=(tab.seg_order_c, self._front_cap))
-            return dict(rays=rays, depths=depths, src=src, seg_start=out_seg, n_dev=n_dev, T12=T12, tab=tab, front_record=rec)
-        rays, depths, src, out_seg, n_dev, counts = ops.compact_rays(rays_c, depths_c, keep, src_c, tab.seg_start, n_out=n_out, want_counts=True)
-        return dict(rays=rays, depths=depths, src=src, seg_start=out_seg, n_dev=n_dev, T12=T12, tab=tab, counts=counts)
+        front = (tab.seg_order_c, ph.front_cap) if self._dist is not None else None
+        rays, depths, src, out_seg, n_dev, head = ops.compact_rays(rays_c, depths_c, keep, src_c, tab.seg_start, n_out=n_out,
+                                                                   want_counts=front is None, front=front)
+        batch = dict(rays=rays, depths=depths, src=src, seg_start=out_seg, n_dev=n_dev, T12=T12)
+        batch["front"] = self._sample_front(rays, depths, n_dev, head=head)
+        return batch
 
-    def _pose_backward(self, batch, d_rays, pose_dev, free_mask_u8, poison=None, poison_tag=0):
+    def _pose_backward(self, ph, batch, d_rays, it_idx):
         """dL/drays -> dL/d[R|t] per segment (HIP) -> dL/dpose6 (HIP, analytic axis-angle Jacobian)."""
-        tab = batch["tab"]
+        tab, pose_dev = ph.tab, ph.pose_dev
         seg_T = batch["T12"] if not tab.has_sky else batch["T12"][tab.seg_kf_dev]
         dT_seg = ops.lidar_rays_backward(d_rays, batch["rays"], batch["src"], batch["seg_start"], tab.dirs_list, seg_T, self._scale_f)
         if tab.has_sky:          # sky rays are built from a detached pose (keyframe.py:93): drop their contribution
@@ -624,9 +649,9 @@ class Optimizer:
         else:
             dT = dT_seg
         if pose_dev.grad is None:
-            pose_dev.grad = ops.pose_backward(pose_dev, dT, mask=free_mask_u8, poison=poison, poison_tag=poison_tag)
+            pose_dev.grad = ops.pose_backward(pose_dev, dT, mask=ph.free_rows, poison=ph.poison, poison_tag=it_idx)
         else:
-            ops.pose_backward(pose_dev, dT, mask=free_mask_u8, out=pose_dev.grad, accumulate=True, poison=poison, poison_tag=poison_tag)
+            ops.pose_backward(pose_dev, dT, mask=ph.free_rows, out=pose_dev.grad, accumulate=True, poison=ph.poison, poison_tag=it_idx)
 
     # -------------------------------------------------------------------------------------------
     def _loss_config(self, iteration_idx) -> hip.LossConfig:
@@ -646,12 +671,11 @@ class Optimizer:
             cfg.fixed_eps = lc["depth_eps"]
         return cfg
 
-    def _sample_front(self, rays, depths, n_rays_dev, draws=None, shard_segments=None, pre=None):
+    def _sample_front(self, rays, depths, n_rays_dev, head=None):
         """The part of an iteration that does not touch the density parameters: loss normalisers and sample depths for `rays`
-        (optimizer.py:437-470 up to the network call).  -> dict(counts, front_work, z, seed, far0).  shard_segments (sharded loop):
-        (compacted segment starts on the device, window position of every segment) of this rank's batch.  pre: the batch dictionary of
-        _build_window_rays, whose compaction launch has already computed the counts / written the front record."""
-        draws = draws if draws is not None else self._draws
+        (optimizer.py:437-470 up to the network call).  -> dict(counts, front_work, z, seed, far0).  head: what the
+        compaction launch of _front_end has already computed from these rays - the counts, sharded this rank's front record."""
+        draws = self._draws
         pc = self._consts()
         S, perturb, ogm = pc["S"], pc["perturb"], pc["ogm"]
         dev = self._device
@@ -669,19 +693,13 @@ class Optimizer:
         # right before the loss kernel, its first consumer.
         counts = far0 = front_work = None
         if self._dist is not None:
-            if shard_segments is not None:
-                seg_start, seg_order, cap = shard_segments[0], shard_segments[1], self._front_cap
-            else:       # a caller outside the training loop (compute_loss): the batch is one segment at this rank's position
-                seg_start, seg_order = torch.tensor([0, n], device=dev, dtype=torch.int32), [self._dist.rank]
-                cap = self._dist.max_over_ranks(n)
-            rec = pre.get("front_record") if (pre is not None and shard_segments is not None) else None
-            if rec is None:
-                rec = ops.shard_front_pack(rays, seg_start, seg_order, depths, n_rays_dev, cap)
+            rec = head
+            if rec is None:     # a caller outside the training loop (compute_loss): the batch is one segment at this rank's position
+                rec = ops.shard_front_pack(rays, torch.tensor([0, n], device=dev, dtype=torch.int32), [self._dist.rank], depths,
+                                           n_rays_dev, self._dist.max_over_ranks(n))
             front_work = self._dist.gather_front(rec)
         else:
-            counts = pre.get("counts") if pre is not None else None
-            if counts is None:
-                counts = ops.count_opaque(rays, depths, n_rays_dev=n_rays_dev)
+            counts = head if head is not None else ops.count_opaque(rays, depths, n_rays_dev=n_rays_dev)
         if ogm:
             z = ops.sample_rays_occ(rays, self._occupancy_grid.detach(), S, perturb, u_jitter=u1, u_pdf=u2, seed=seed,
                                     n_rays_dev=n_rays_dev)
@@ -689,24 +707,27 @@ class Optimizer:
             z = ops.sample_rays_uniform(rays, S, perturb, u_jitter=u1, seed=seed, n_rays_dev=n_rays_dev)
         return dict(counts=counts, front_work=front_work, z=z, seed=seed, far0=far0)
 
-    def _loss_and_grads(self, rays, depths, params, iteration_idx, want_ray_grads, want_param_grads, n_rays_dev=None,
-                        loss_out=None, accumulate_into_param_grad=False, draws=None, want_stats=True, defer_grad_wait=False,
-                        poison=None, front=None, input_grad_event=None, defer_weight_fold=False, shard_segments=None, pre=None):
+    def _loss_and_grads(self, rays, depths, params, iteration_idx, want_ray_grads, want_param_grads, loop=None):
         """sample -> density -> fused render+loss(+backward) -> density backward.  rays [N,13], depths [N] on device.
-        front: the result of _sample_front for these rays when the caller already ran it (the pipelined training loop);
-        input_grad_event: recorded by the density backward as soon as d_rays is complete (ops.density_backward)."""
-        draws = draws if draws is not None else self._draws
+        loop: (phase, batch of _front_end) when the training loop calls.  The loss terms then go into row iteration_idx of the phase's
+        log (no per-ray statistics), failures mark the phase's word, the gradient lands in params.grad, its exchange is left running
+        for the density step to wait for, and in the pipelined loop the density backward records the phase's event as soon as d_rays
+        is complete (ops.density_backward).  Every other caller (autograd) gets the statistics and fresh, fully reduced gradients."""
+        draws = self._draws
         pc = self._consts()
         S, noise_std = pc["S"], pc["noise_std"]
         spec = self._model.nerf_model._model_sigma.spec
-        dev = self._device
-        n = rays.shape[0]
-        if front is None:
-            front = self._sample_front(rays, depths, n_rays_dev, draws, shard_segments=shard_segments, pre=pre)
+        in_loop = loop is not None
+        if in_loop:
+            ph, batch = loop
+            n_rays_dev, front, loss_out, poison, grad_event = batch["n_dev"], batch["front"], ph.loss_log[iteration_idx], ph.poison, ph.grad_event
+        else:
+            n_rays_dev = loss_out = poison = grad_event = None
+            front = self._sample_front(rays, depths, None)
         counts, front_work, z, seed, far0 = front["counts"], front["front_work"], front["z"], front["seed"], front["far0"]
         noise = None
         if draws is not None and noise_std > 0:
-            noise = (draws.noise(n, S) * noise_std).to(dev)
+            noise = (draws.noise(rays.shape[0], S) * noise_std).to(self._device)
         p = params.detach()
         self._flush_density_step()            # the previous iteration's (deferred) density Adam step lands here
         sigma = ops.density_forward(spec, p, rays=rays, z=z, n_rays_dev=n_rays_dev)
@@ -714,71 +735,69 @@ class Optimizer:
             counts, far0 = front_work.wait()
         loss, d_sigma, d_rays, stats, _ = ops.los_loss_fused(sigma, z, rays, depths, self._scale_f, self._loss_config(iteration_idx),
                                                             counts, noise=noise, noise_std=noise_std, seed=seed + 1,
-                                                            n_rays_dev=n_rays_dev, want_stats=want_stats, loss_out=loss_out, far0=far0,
-                                                            poison=poison, poison_tag=iteration_idx, zero_dead_rows=not defer_grad_wait)
-        grad_params = None
-        grad_work = None
+                                                            n_rays_dev=n_rays_dev, want_stats=not in_loop, loss_out=loss_out, far0=far0,
+                                                            poison=poison, poison_tag=iteration_idx, zero_dead_rows=not in_loop)
+        grad_params = grad_work = None
         if want_param_grads or want_ray_grads:
-            if not want_param_grads:
-                grad_params = None            # frozen parameters (tracking / freeze_sigma phases): input gradient only - no table-
-                                              # gradient records, no reduce, no 30 MB zero buffer (lnr_density_backward, grad_params NULL)
-            elif accumulate_into_param_grad:
+            # (grad_params None - frozen parameters, tracking / freeze_sigma phases: input gradient only - no table-gradient records,
+            # no reduce, no 30 MB zero buffer: lnr_density_backward, grad_params NULL)
+            if want_param_grads and in_loop:
                 if params.grad is None:
                     params.grad = torch.zeros_like(params)
                 grad_params = params.grad
-            else:
+            elif want_param_grads:
                 grad_params = torch.zeros_like(p)
             # the point gradient is reduced per ray inside the backward and added to d_rays (no [N,S,3] tensor)
             # the training loop steps after every backward: the gradient buffer then RECEIVES the gradient (no read in the reduce, no
             # zeroing in the optimiser: 60 MB of HBM traffic per iteration); every other caller accumulates, as autograd expects
-            overwrite = self._overwrite_grads and defer_grad_wait and accumulate_into_param_grad and grad_params is not None
+            overwrite = self._overwrite_grads and in_loop and grad_params is not None
+            # (only the pipelined loop with a deferred density step folds the weight-gradient slabs itself, on its side stream)
+            fold_later = in_loop and ph.side is not None and ph.defer_density and grad_params is not None
             ops.density_backward(spec, p, d_sigma, grad_params, rays=rays, z=z, n_rays_dev=n_rays_dev,
-                                 reuse_features=True, d_rays=d_rays if want_ray_grads else None, input_grad_event=input_grad_event,
-                                 defer_weight_fold=defer_weight_fold and grad_params is not None, overwrite_grad=overwrite)
+                                 reuse_features=True, d_rays=d_rays if want_ray_grads else None, input_grad_event=grad_event,
+                                 defer_weight_fold=fold_later, overwrite_grad=overwrite)
             if self._dist is not None and want_param_grads:
-                # only the training loop (defer_grad_wait) steps a slice and gathers the parameters; every other caller
+                # only the training loop steps a slice and gathers the parameters; every other caller
                 # (compute_loss -> autograd -> an optimiser of its own) gets the whole sum whatever the exchange form
                 # (overwrite mode: the next backward stores every float of the gradient - the chunks of other ranks need no zeroing)
-                grad_work = self._dist.exchange_grads(grad_params, async_op=True, force_all_reduce=not defer_grad_wait,
-                                                      zero_rest=not overwrite)
-                if not defer_grad_wait:
+                grad_work = self._dist.exchange_grads(grad_params, async_op=True, force_all_reduce=not in_loop, zero_rest=not overwrite)
+                if not in_loop:
                     grad_work.wait()
                     grad_work = None
-        elif input_grad_event is not None:
-            input_grad_event.record()
+        elif grad_event is not None:
+            grad_event.record()
         self._results_lidar = {"rays": rays, "depths": depths, "samples_fine": z, "n_rays_dev": n_rays_dev, "stats": stats}
         return dict(loss=loss, d_rays=d_rays if want_ray_grads else None,
                     grad_params=grad_params if want_param_grads else None, stats=stats, z=z, grad_work=grad_work)
 
-    def _join_without_rays(self, params, want_param_grads):
+    def _join_without_rays(self, ph):
         """Sharded mode, this rank owns no keyframe of the active window: take part in every collective of an iteration
         (far[0] broadcast, loss normalisers, density gradient) with zero contributions, in the order _loss_and_grads issues
         them, so that the other ranks neither block nor see different sums."""
-        dev = self._device
-        front_work = self._dist.gather_front(ops.shard_front_pack(None, None, (), None, None, self._front_cap, device=dev))
+        params = ph.density_params if ph.density_group is not None else None
+        front_work = self._dist.gather_front(ops.shard_front_pack(None, None, (), None, None, ph.front_cap, device=self._device))
         self._flush_density_step()
         front_work.wait()
         grad_work = None
-        if want_param_grads and params is not None:
+        if params is not None:
             if params.grad is None:
                 params.grad = torch.zeros_like(params)
             elif self._overwrite_grads:
                 # no backward of this rank overwrites what the previous exchange left in the buffer: contribute zeros again.  The
                 # all-reduce form leaves the sum in the whole vector; the reduce-scatter form only reads the buffer and writes this
-                # rank's chunk (and the phase starts from an all-zero gradient: _do_iterate_optimizer's phase end).
+                # rank's chunk (and the phase starts from an all-zero gradient: _end_phase).
                 # The rest of the buffer must be zero as well - it is after a phase that ended normally, but not after an autograd
                 # backward through compute_loss() without a zero_grad, nor after anything else that wrote params.grad in between
                 # (ADVICE r5) - so the first idle iteration of a phase clears the whole vector: one fill per phase, not per iteration.
                 sl = self._dist.owned_range(params.grad.numel())
-                if sl is None or not self._idle_grad_cleared:
+                if sl is None or not ph.idle_grad_cleared:
                     params.grad.zero_()
-                    self._idle_grad_cleared = True
+                    ph.idle_grad_cleared = True
                 else:
                     params.grad.view(-1)[sl[0]:sl[1]].zero_()
             grad_work = self._dist.exchange_grads(params.grad.view(-1), async_op=True, zero_rest=not self._overwrite_grads)
         self._results_lidar = None
-        return dict(loss=None, d_rays=None, grad_params=params.grad if (want_param_grads and params is not None) else None,
-                    stats=None, z=None, grad_work=grad_work)
+        return dict(d_rays=None, grad_params=params.grad if params is not None else None, grad_work=grad_work)
 
     def _flush_density_step(self):
         """Apply the density Adam step the training loop deferred (after its gradient all-reduce, if any, has finished)."""

@@ -658,17 +658,18 @@ def test_optimizer_survives_spawn_pickling_and_mask_ray_selection():
     assert drawn.numel() == 5 * 64 and int(drawn.min()) >= 1000 and int(drawn.max()) < 1400 and len(torch.unique(drawn)) > 100
 
 
-def test_deferred_density_step_is_taken_and_changes_nothing():
+@pytest.mark.parametrize("pipeline", [True, False])
+def test_deferred_density_step_is_taken_and_changes_nothing(pipeline):
     """The density Adam step is deferred to just before the next density forward (so that, sharded, the gradient all-reduce
     overlaps the pose tail and the next batch's ray build).  It must actually be deferred in a joint phase, and the result
-    must be bit-identical to stepping right away."""
+    must be bit-identical to stepping right away - in the pipelined and in the single-stream loop."""
     from loner_amd.mapping import optimizer as OM
     from loner_amd.utils import synthetic as SY
 
     def run(defer):
         torch.manual_seed(0)
         opt = OM.Optimizer(small_settings(96, 64), None, world_cube(), 0, False, True, False)
-        opt._defer_density_step = defer
+        opt._defer_density_step, opt._pipeline = defer, pipeline
         base = SY.trajectory_pose6(2)
         kfs = make_keyframes([base[0], base[1] + torch.tensor([0.02, 0.0, -0.01, 0.0, 0.0, 0.0])])
         kfs[0].is_anchored = True
