@@ -1,12 +1,16 @@
 """Run LiDAR SLAM on a folder of scans.
 
-    python examples/run_sequence.py <folder> [--gt poses_tum.txt] [--out ~/LonerSLAM/outputs] [--name run] [--ray-range 1 50]
+    python examples/run_sequence.py <folder> [--gt poses_tum.txt] [--gt-mesh mesh.ply [--mesh-resolution 0.1]]
+                                    [--out ~/LonerSLAM/outputs] [--name run] [--ray-range 1 50]
 
 <folder> holds one `.npy` file per scan, [N,4] columns x, y, z, t (t: per-point time, local to the scan or global, seconds or
 nanoseconds), read in sorted name order, and `stamps.txt` with one scan time in seconds per line.  With --gt (a TUM file: ts x y z qx
 qy qz qw) every scan gets the ground-truth pose nearest in time, the world cube is computed from the ground truth and the estimated
-trajectory is scored against it; without it the cube comes from system.world_cube.trajectory_bounding_box.  The log directory holds
-the checkpoints, the four trajectory files and the configuration, as the analysis tools of this package expect them."""
+trajectory is scored against it; without it the cube comes from system.world_cube.trajectory_bounding_box.  With --gt-mesh (the
+.ply the scans were simulated from, or surveyed) the trained map is meshed at --mesh-resolution over the ground-truth mesh's box grown
+by 1 m, written to <log>/meshes/, and scored against that mesh with the exact point-to-surface distance
+(mesh_eval.evaluate_mesh_to_mesh).  The log directory holds the checkpoints, the four trajectory files and the configuration, as the
+analysis tools of this package expect them."""
 import argparse
 import glob
 import os
@@ -29,6 +33,8 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("folder")
     ap.add_argument("--gt")
+    ap.add_argument("--gt-mesh")
+    ap.add_argument("--mesh-resolution", type=float, default=0.1)
     ap.add_argument("--out", default="~/LonerSLAM/outputs")
     ap.add_argument("--name", default=None)
     ap.add_argument("--ray-range", type=float, nargs=2, default=(1.0, 50.0))
@@ -68,6 +74,32 @@ def main():
     if args.gt:
         score = ape(os.path.join(log, "trajectory", "estimated_trajectory.txt"), args.gt)
         print("APE (aligned, m): " + ", ".join(f"{k} {score[k]:.4f}" for k in ("rmse", "mean", "median", "std", "min", "max")))
+    if args.gt_mesh:
+        score_against_mesh(loner, args.gt_mesh, args.mesh_resolution, args.ray_range, log)
+
+
+def score_against_mesh(loner, gt_mesh_path, resolution, ray_range, log):
+    """Mesh the map the run trained and print evaluate_mesh_to_mesh against the ground-truth mesh"""
+    from loner_amd.analysis.mesh_eval import evaluate_mesh_to_mesh
+    from loner_amd.analysis.mesher import Mesher, TriangleMesh
+    gt_mesh = TriangleMesh.read_ply(gt_mesh_path)
+    bound = np.stack([gt_mesh.vertices.min(axis=0) - 1.0, gt_mesh.vertices.max(axis=0) + 1.0], axis=1)
+    opt = loner._mapper._optimizer
+    ckpt = {"poses": loner._mapper._keyframe_manager.get_poses_state()}
+    mesher = Mesher(opt._model, ckpt, loner.get_world_cube(), torch.tensor(list(ray_range)), resolution=resolution,
+                    marching_cubes_bound=bound.tolist(), level_set=0)
+    device = opt._device
+    mesh = mesher.get_mesh(device, opt._ray_sampler, skip_step=1)
+    if mesh is None:
+        print("map against the ground-truth mesh: the trained map has no surface to score")
+        return
+    os.makedirs(os.path.join(log, "meshes"), exist_ok=True)
+    out = os.path.join(log, "meshes", f"mesh_{resolution}.ply")
+    mesh.write_ply(out)
+    score = evaluate_mesh_to_mesh(mesh, gt_mesh, device=device)
+    print(f"mesh: {mesh.triangles.shape[0]} triangles written to {out}")
+    print("map against the ground-truth mesh (exact distances, m; shares at 0.1 m): " +
+          ", ".join(f"{k} {score[k]:.4f}" for k in ("accuracy", "completion", "chamfer", "precision", "recall", "f_score")))
 
 
 if __name__ == "__main__":

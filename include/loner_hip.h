@@ -761,7 +761,37 @@ int lnr_mesh_smooth(double* vertices, double* scratch, int64_t n_vertices, const
  * is left out and counted.  This is the whole definition: the tree only decides which triangles a ray is tested against, and its box
  * test is padded (by 2^-36 of the largest slab distance of the box, and the same share of the box's offset on an axis the ray does not
  * move along) so that it keeps every box whose triangle the rule above accepts; a node is dropped only when its padded entry distance
- * is strictly greater than the best t so far. */
+ * is strictly greater than the best t so far.
+ *
+ * The closest point q of a triangle (A, B, C) to a point p is the region walk of Ericson, Real-Time Collision Detection, 5.1.5, in
+ * fp64, every operation rounded on its own, with dot(x, y) = (x0 * y0 + x1 * y1) + x2 * y2 and vectors handled per axis:
+ *   ab = B - A, ac = C - A, ap = p - A, d1 = dot(ab, ap), d2 = dot(ac, ap);       d1 <= 0 && d2 <= 0: q = A;
+ *   bp = p - B, d3 = dot(ab, bp), d4 = dot(ac, bp);                               d3 >= 0 && d4 <= d3: q = B;
+ *   vc = d1 * d4 - d3 * d2;             vc <= 0 && d1 >= 0 && d3 <= 0: v = d1 / (d1 - d3), q = A + v * ab;
+ *   cp = p - C, d5 = dot(ab, cp), d6 = dot(ac, cp);                               d6 >= 0 && d5 <= d6: q = C;
+ *   vb = d5 * d2 - d1 * d6;             vb <= 0 && d2 >= 0 && d6 <= 0: w = d2 / (d2 - d6), q = A + w * ac;
+ *   va = d3 * d6 - d5 * d4;             va <= 0 && (d4 - d3) >= 0 && (d5 - d6) >= 0: w = (d4 - d3) / ((d4 - d3) + (d5 - d6)),
+ *                                                                                  q = B + w * (C - B);
+ *   otherwise den = 1 / ((va + vb) + vc), v = vb * den, w = vc * den, q = (A + ab * v) + ac * w.
+ * The first branch that applies wins.  The squared distance is dot(p - q, p - q).  The barycentrics follow the ray's convention, (u, v)
+ * weigh A and B: with v_B and w_C the weights of B and C in the branch taken - (0, 0) at A, (1, 0) at B, (0, 1) at C, (v, 0) on AB,
+ * (0, w) on AC, (1 - w, w) on BC, (v, w) inside - v_out = v_B and u_out = (1.0 - v_B) - w_C.
+ * The answer of a query p: a triangle is a candidate when its squared distance is <= max_distance_sq (a NaN, which a triangle
+ * collapsed to a point or a line can produce through 0 / 0, never is); the answer is the candidate with the smallest squared
+ * distance, the smallest triangle index among equal ones; with no candidate the squared distance is +inf, the id -1, the point and
+ * the uv zeros.  A query with a non-finite coordinate gets that answer too and is counted; the triangles the build left out are no
+ * candidates.  The tree's bound of a box [lo, hi]: per axis g = max(lo - p, p - hi, 0) reduced by 2^-36 max(|lo|, |hi|, |p|) and
+ * clamped at 0, bound = (g0 * g0 + g1 * g1) + g2 * g2; a node is dropped only when its bound is strictly greater than the best
+ * squared distance so far or than max_distance_sq, so equal distances still reach the lower index.
+ *
+ * The crossing count of a ray is the number of triangles the watertight rule above accepts with t_min <= t <= t_max, with the same
+ * exclusions (a ray that is not finite or has a zero direction counts 0 and is counted).  A point is inside a closed mesh when the
+ * count along LNR_OCCUPANCY_DIRECTIONS[0] from it, over [0, +inf], is odd; with three samples, when at least two of the three
+ * directions give an odd count.  The directions are fixed, not drawn: the answer is a function of the mesh and the point.  The
+ * limit: a ray through an edge or a corner shared by several triangles is accepted by each of them, so one direction can miscount;
+ * the majority vote exists for this case. */
+#define LNR_OCCUPANCY_DIRECTIONS {{1.0, 0.4142135623730951, 0.7320508075688772}, {-0.6180339887498949, 1.0, 0.3027756377319946}, \
+                                  {0.2360679774997897, -0.7071067811865476, 1.0}}
 #define LNR_RAYCAST_INFO 8
 #define LNR_BVH_STACK 96            /* words of traversal stack per ray; a tree is at most 63 + 31 levels deep (code bits + tie bits) */
 
@@ -789,6 +819,22 @@ int lnr_bvh_build(const double* vertices, int64_t n_vertices, const int32_t* tri
  * out of bounds). */
 int lnr_cast_rays(const void* bvh, int64_t n_triangles, const double* rays, int64_t n_rays, double t_min, double t_max, double* t_hit,
                   int32_t* primitive_ids, double* primitive_uvs, int64_t* info_dev, void* stream);
+
+/* open3d's RaycastingScene::ComputeClosestPoints with a reach: the closest point of the mesh to every query, by the rule above.
+ * points fp64 [n_points,3]; max_distance_sq not NaN (+inf: no limit).  dist_sq fp64 [n_points], primitive_ids int32 [n_points],
+ * closest fp64 [n_points,3] (nullable), primitive_uvs fp64 [n_points,2] (nullable).  One query per lane, the child with the smaller
+ * bound first, at most 2 x nodes visits per query.  info_dev: {status, queries answered (id >= 0), queries with a non-finite
+ * coordinate, node visits over all queries, queries stopped by the visit cap, triangles the build left out, depth, 0}; the status
+ * bits are lnr_cast_rays'. */
+int lnr_closest_points(const void* bvh, int64_t n_triangles, const double* points, int64_t n_points, double max_distance_sq,
+                       double* dist_sq, int32_t* primitive_ids, double* closest, double* primitive_uvs, int64_t* info_dev, void* stream);
+
+/* open3d's RaycastingScene::CountIntersections with a window: counts int32 [n_rays], the crossing count stated above; rays, t_min and
+ * t_max as lnr_cast_rays takes them.  Every box whose padded slab meets the window is visited.  info_dev: {status, rays with a count
+ * above 0, rays that are not finite or have a zero direction, node visits, rays stopped by the visit cap, triangles the build left
+ * out, depth, 0}; the status bits are lnr_cast_rays'. */
+int lnr_count_intersections(const void* bvh, int64_t n_triangles, const double* rays, int64_t n_rays, double t_min, double t_max,
+                            int32_t* counts, int64_t* info_dev, void* stream);
 
 /* The rays of a sensor that moves while it sweeps: the inverse of lnr_cloud_trajectory_transform.  directions fp32 [3,n_rays] in the
  * sensor frame (a scan's layout), timestamps fp64 [n_rays] (absolute), the trajectory arrays as lnr_cloud_trajectory_transform takes

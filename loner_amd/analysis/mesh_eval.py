@@ -9,6 +9,10 @@ the reference, by intent:
   * the cumulative area is summed as a 64-ary tree, open3d's one addition after the other; the two differ in the last bits, which can
     move a triangle's share by one point;
   * the script's unused camera-to-LiDAR constants (T_lc) are not restated.
+
+evaluate_mesh_to_mesh has no counterpart in the reference: where the ground truth is a mesh (a simulated sequence's, a survey's) it
+scores against the surface itself - the exact point-to-triangle distance of analysis/raycast.py - so the ground truth is not sampled
+into a cloud and no figure carries that cloud's density or a voxel size.  cloud_to_mesh_distance is its building block.
 """
 import os
 
@@ -45,6 +49,65 @@ def evaluate_mesh(mesh, gt_cloud, output_dir, f_score_threshold=0.1, voxel_size=
     cloud = mesh_to_point_cloud(mesh, voxel_size if resolution is None else resolution, number_of_points, seed,
                                 device=gt_cloud.points.device)
     return compare_point_clouds(cloud, gt_cloud, output_dir, f_score_threshold, voxel_size, **compare_kwargs)
+
+
+def cloud_to_mesh_distance(cloud_or_points, scene, max_distance=float("inf")):
+    """The exact distance fp64 [n], on the device, from every point of a PointCloud (or of points [n,3]) to the surface of scene (a
+    RaycastingScene): RaycastingScene.compute_distance.  +inf where no triangle lies within max_distance."""
+    from .raycast import RaycastingScene
+    if not isinstance(scene, RaycastingScene):
+        raise ValueError(f"cloud_to_mesh_distance: scene must be a RaycastingScene, got {type(scene).__name__}")
+    points = cloud_or_points.points if hasattr(cloud_or_points, "points") else cloud_or_points
+    if len(getattr(points, "shape", ())) != 2 or points.shape[1] != 3:
+        raise ValueError(f"cloud_to_mesh_distance: a PointCloud or points [n,3], got {tuple(getattr(points, 'shape', ()))}")
+    return scene.compute_distance(points, max_distance)
+
+
+def evaluate_mesh_to_mesh(est_mesh, gt_mesh, f_score_threshold=0.1, number_of_points=1_000_000, seed=0, device=None):
+    """Accuracy, completion and F-score of a mesh against the mesh it should be, with the exact point-to-surface distance on both
+    sides: number_of_points uniform samples of each mesh (TriangleMesh.sample_points_uniformly's rule and seed), each sample's
+    distance to the OTHER mesh's surface.  The ground truth is neither sampled into a cloud to search in nor down-sampled, so no
+    figure carries a sampling density or a voxel size.  est_mesh, gt_mesh: TriangleMesh, .ply path or RaycastingScene.
+    -> {"accuracy": the mean distance of the estimate's samples to the ground truth, "completion": the ground truth's samples to the
+    estimate, "chamfer": their sum, "precision" / "recall": the share of each side's samples within f_score_threshold, "f_score":
+    2 p r / (p + r), 0 when both are 0, "n_est", "n_gt": the samples drawn}.  A side without area has no samples: its mean is NaN and
+    its share 0.  The sums run in fp64 on the device (torch) and are read in one host read, after the sampler's own one per mesh."""
+    import torch
+    from .. import ops
+    from .raycast import RaycastingScene
+    threshold, n = float(f_score_threshold), int(number_of_points)
+    if not threshold >= 0:
+        raise ValueError(f"evaluate_mesh_to_mesh: f_score_threshold must be >= 0, got {f_score_threshold!r}")
+    if n <= 0:
+        raise ValueError(f"evaluate_mesh_to_mesh: number_of_points must be > 0, got {number_of_points!r}")
+    scenes = []
+    for mesh in (est_mesh, gt_mesh):
+        if isinstance(mesh, RaycastingScene):
+            scenes.append(mesh)
+            continue
+        if isinstance(mesh, (str, os.PathLike)):
+            mesh = TriangleMesh.read_ply(mesh)
+        if not (hasattr(mesh, "vertices") and hasattr(mesh, "triangles")):
+            raise ValueError(f"evaluate_mesh_to_mesh: a TriangleMesh, a .ply path or a RaycastingScene, got {type(mesh).__name__}")
+        scenes.append(RaycastingScene(mesh, device=device))
+    est, gt = scenes
+    if est.device != gt.device:
+        raise ValueError(f"evaluate_mesh_to_mesh: the meshes live on {est.device} and {gt.device}")
+    sums, counts = [], []
+    for own, other in ((est, gt), (gt, est)):
+        samples = ops.mesh_sample_points(own.vertices, own.triangles, n, seed)
+        d = other.compute_distance(samples)
+        sums += [d.sum(), (d <= threshold).sum().double()]
+        counts.append(d.shape[0])
+    out = torch.stack(sums).cpu().tolist()
+    n_est, n_gt = counts
+    accuracy = out[0] / n_est if n_est else float("nan")
+    completion = out[2] / n_gt if n_gt else float("nan")
+    precision = out[1] / n_est if n_est else 0.0
+    recall = out[3] / n_gt if n_gt else 0.0
+    f_score = 2.0 * precision * recall / (precision + recall) if precision + recall > 0 else 0.0
+    return {"accuracy": accuracy, "completion": completion, "chamfer": accuracy + completion, "precision": precision, "recall": recall,
+            "f_score": f_score, "n_est": n_est, "n_gt": n_gt}
 
 
 def mesh_depth_l1(est_scene, gt_scene, poses, directions, ray_range):

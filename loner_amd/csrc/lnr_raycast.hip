@@ -1,6 +1,8 @@
 // Ray casting against triangle meshes (gfx950): what a user of open3d's RaycastingScene calls, and the rays of a sweeping LiDAR.
 //   RaycastingScene(mesh)                                            lnr_bvh_build
 //   RaycastingScene.cast_rays                                        lnr_cast_rays
+//   RaycastingScene.compute_closest_points / compute_distance        lnr_closest_points
+//   RaycastingScene.count_intersections / compute_occupancy          lnr_count_intersections
 //   the rays of a sensor that moves while it sweeps                  lnr_trajectory_rays
 // with the definitions stated in include/loner_hip.h ("ray casting").  This file is compiled with -ffp-contract=off (build.py EXACT):
 // every fp64 expression of the triangle rule and of the pose rule rounds operation by operation, as the numpy restatement
@@ -21,6 +23,9 @@
 //   cast       one ray per lane, one wave per workgroup; the stack is a column of LDS per lane (LNR_BVH_STACK words, no private array
 //              is indexed at run time); near child first; a node is dropped only when its padded entry distance is strictly greater
 //              than the best t, so equal t still reaches the lower index
+//   closest    the same walk for a point: the child with the smaller bound first; a node is dropped only when a lower bound of the
+//              squared distance to its box is strictly greater than the best so far (box_bound)
+//   count      the cast's walk without a best t: every box whose padded slab meets the window is visited
 #include "lnr_radix_sort.h"
 
 namespace {
@@ -341,9 +346,9 @@ __device__ inline bool slab(const RayCtx& r, const double* lo, const double* hi,
     return inside && !(entry > exit) && !(entry > best) && !(exit < r.t_min) && !(entry > r.t_max);
 }
 
-// the watertight rule of include/loner_hip.h on the triangle at sorted position j
-__device__ inline void hit_leaf(const RayCtx& r, const double* __restrict__ leaf_v, const int32_t* __restrict__ leaf_id, uint32_t j,
-                                double* best_t, int32_t* best_id, double* best_u, double* best_v) {
+// the watertight rule of include/loner_hip.h on the triangle at sorted position j -> accepted; t, and U, V, det for the barycentrics
+__device__ inline bool hit_rule(const RayCtx& r, const double* __restrict__ leaf_v, uint32_t j, double* t_out, double* U_out, double* V_out,
+                                double* det_out) {
     const double* p = leaf_v + 9 * (size_t)j;
     const double a0 = p[0] - r.o[0], a1 = p[1] - r.o[1], a2 = p[2] - r.o[2];
     const double b0 = p[3] - r.o[0], b1 = p[4] - r.o[1], b2 = p[5] - r.o[2];
@@ -353,11 +358,22 @@ __device__ inline void hit_leaf(const RayCtx& r, const double* __restrict__ leaf
     const double bx = sel3(r.kx, b0, b1, b2) - r.sx * bkz, by = sel3(r.ky, b0, b1, b2) - r.sy * bkz;
     const double cx = sel3(r.kx, c0, c1, c2) - r.sx * ckz, cy = sel3(r.ky, c0, c1, c2) - r.sy * ckz;
     const double U = cx * by - cy * bx, V = ax * cy - ay * cx, W = bx * ay - by * ax;
-    if ((U < 0.0 || V < 0.0 || W < 0.0) && (U > 0.0 || V > 0.0 || W > 0.0)) return;
+    if ((U < 0.0 || V < 0.0 || W < 0.0) && (U > 0.0 || V > 0.0 || W > 0.0)) return false;
     const double det = (U + V) + W;
-    if (det == 0.0) return;
+    if (det == 0.0) return false;
     const double t = ((U * (r.sz * akz) + V * (r.sz * bkz)) + W * (r.sz * ckz)) / det;
-    if (!(t >= r.t_min && t <= r.t_max)) return;
+    if (!(t >= r.t_min && t <= r.t_max)) return false;
+    *t_out = t;
+    *U_out = U;
+    *V_out = V;
+    *det_out = det;
+    return true;
+}
+
+__device__ inline void hit_leaf(const RayCtx& r, const double* __restrict__ leaf_v, const int32_t* __restrict__ leaf_id, uint32_t j,
+                                double* best_t, int32_t* best_id, double* best_u, double* best_v) {
+    double t, U, V, det;
+    if (!hit_rule(r, leaf_v, j, &t, &U, &V, &det)) return;
     const int32_t id = leaf_id[j];
     if (t < *best_t || (t == *best_t && id < *best_id)) {
         *best_t = t;
@@ -367,95 +383,49 @@ __device__ inline void hit_leaf(const RayCtx& r, const double* __restrict__ leaf
     }
 }
 
-__global__ __launch_bounds__(RC_WAVE) void cast_rays_kernel(const BvhHead* __restrict__ h, const BvhNode* __restrict__ nodes,
-                                                            const double* __restrict__ leaf_v, const int32_t* __restrict__ leaf_id,
-                                                            const double* __restrict__ rays, uint32_t n_rays, double t_min, double t_max,
-                                                            double* __restrict__ t_hit, int32_t* __restrict__ ids, double* __restrict__ uvs,
-                                                            unsigned long long* __restrict__ tally) {
-    __shared__ int32_t stack[LNR_BVH_STACK][RC_WAVE];
-    const uint32_t lane = threadIdx.x;
-    const uint32_t i = blockIdx.x * RC_WAVE + lane;
-    const uint32_t n = (h->status & (RC_ST_BAD_INDEX | RC_ST_TOO_DEEP)) ? 0u : h->n;
-    const unsigned long long cap = 2ull * (n > 1 ? 2ull * n - 1ull : (unsigned long long)n);
-    double best_t = INFINITY, best_u = 0.0, best_v = 0.0;
-    int32_t best_id = -1;
-    unsigned long long visits = 0;
-    bool invalid = false, capped = false, overflow = false;
-    if (i < n_rays) {
-        RayCtx r;
-        double d[3];
-        bool fin = true;
+// ray i of rays [n,6] -> false: not finite or a zero direction; else r holds what the slab test and the triangle rule need
+__device__ inline bool ray_setup(const double* __restrict__ rays, uint32_t i, double t_min, double t_max, RayCtx& r) {
+    double d[3];
+    bool fin = true;
 #pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            r.o[a] = rays[6 * (size_t)i + a];
-            d[a] = rays[6 * (size_t)i + 3 + a];
-            fin = fin && isfinite(r.o[a]) && isfinite(d[a]);
-        }
-        invalid = !fin || (d[0] == 0.0 && d[1] == 0.0 && d[2] == 0.0);
-        if (!invalid && n > 0) {
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const double inv = 1.0 / d[a];
-                r.par[a] = d[a] == 0.0 || !isfinite(inv);
-                r.inv[a] = r.par[a] ? 0.0 : inv;
-            }
-            int kz = 0;
-            if (fabs(d[1]) > fabs(d[0])) kz = 1;
-            if (fabs(d[2]) > fabs(sel3(kz, d[0], d[1], d[2]))) kz = 2;
-            int kx = (kz + 1) % 3, ky = (kx + 1) % 3;
-            const double dkz = sel3(kz, d[0], d[1], d[2]);
-            if (dkz < 0.0) { const int s = kx; kx = ky; ky = s; }
-            r.kx = kx; r.ky = ky; r.kz = kz;
-            r.sx = sel3(kx, d[0], d[1], d[2]) / dkz;
-            r.sy = sel3(ky, d[0], d[1], d[2]) / dkz;
-            r.sz = 1.0 / dkz;
-            r.t_min = t_min;
-            r.t_max = t_max;
-            int sp = 0;
-            int32_t node = n == 1 ? ~0 : 0;
-            for (;;) {
-                if (visits >= cap) { capped = true; break; }
-                ++visits;
-                bool pop = true;
-                if (node < 0) {
-                    hit_leaf(r, leaf_v, leaf_id, (uint32_t)(~node), &best_t, &best_id, &best_u, &best_v);
-                } else {
-                    const BvhNode* nd = nodes + node;
-                    double e0, e1;
-                    const bool h0 = slab(r, nd->lo[0], nd->hi[0], best_t, &e0);
-                    const bool h1 = slab(r, nd->lo[1], nd->hi[1], best_t, &e1);
-                    const int32_t c0 = nd->child[0], c1 = nd->child[1];
-                    if (h0 && h1) {
-                        const bool first0 = !(e1 < e0);
-                        if (sp < LNR_BVH_STACK) {
-                            stack[sp][lane] = first0 ? c1 : c0;
-                            ++sp;
-                        } else {
-                            overflow = true;
-                        }
-                        node = first0 ? c0 : c1;
-                        pop = false;
-                    } else if (h0 || h1) {
-                        node = h0 ? c0 : c1;
-                        pop = false;
-                    }
-                }
-                if (pop) {
-                    if (sp == 0) break;
-                    --sp;
-                    node = stack[sp][lane];
-                }
-            }
-        }
-        t_hit[i] = best_t;
-        ids[i] = best_id;
-        if (uvs) {
-            uvs[2 * (size_t)i] = best_u;
-            uvs[2 * (size_t)i + 1] = best_v;
-        }
+    for (int a = 0; a < 3; ++a) {
+        r.o[a] = rays[6 * (size_t)i + a];
+        d[a] = rays[6 * (size_t)i + 3 + a];
+        fin = fin && isfinite(r.o[a]) && isfinite(d[a]);
     }
-    // the call's counts: one atomic per wave and quantity
-    const unsigned long long hits = __ballot(best_id >= 0), bad = __ballot(invalid), cp = __ballot(capped), ov = __ballot(overflow);
+    if (!fin || (d[0] == 0.0 && d[1] == 0.0 && d[2] == 0.0)) return false;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double inv = 1.0 / d[a];
+        r.par[a] = d[a] == 0.0 || !isfinite(inv);
+        r.inv[a] = r.par[a] ? 0.0 : inv;
+    }
+    int kz = 0;
+    if (fabs(d[1]) > fabs(d[0])) kz = 1;
+    if (fabs(d[2]) > fabs(sel3(kz, d[0], d[1], d[2]))) kz = 2;
+    int kx = (kz + 1) % 3, ky = (kx + 1) % 3;
+    const double dkz = sel3(kz, d[0], d[1], d[2]);
+    if (dkz < 0.0) { const int s = kx; kx = ky; ky = s; }
+    r.kx = kx; r.ky = ky; r.kz = kz;
+    r.sx = sel3(kx, d[0], d[1], d[2]) / dkz;
+    r.sy = sel3(ky, d[0], d[1], d[2]) / dkz;
+    r.sz = 1.0 / dkz;
+    r.t_min = t_min;
+    r.t_max = t_max;
+    return true;
+}
+
+// the usable triangles and the visit cap of a walk: none when the build set a status bit
+__device__ inline uint32_t walk_size(const BvhHead* __restrict__ h, unsigned long long* cap) {
+    const uint32_t n = (h->status & (RC_ST_BAD_INDEX | RC_ST_TOO_DEEP)) ? 0u : h->n;
+    *cap = 2ull * (n > 1 ? 2ull * n - 1ull : (unsigned long long)n);
+    return n;
+}
+
+// a call's counts: one atomic per wave and quantity
+__device__ inline void wave_tally(uint32_t lane, bool found, bool invalid, bool capped, bool overflow, unsigned long long visits,
+                                  unsigned long long* __restrict__ tally) {
+    const unsigned long long hits = __ballot(found), bad = __ballot(invalid), cp = __ballot(capped), ov = __ballot(overflow);
     unsigned long long vs = visits;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) vs += __shfl_xor(vs, o, 64);
@@ -468,13 +438,259 @@ __global__ __launch_bounds__(RC_WAVE) void cast_rays_kernel(const BvhHead* __res
     }
 }
 
-// info_dev doubles as the tally while the cast runs (words 1..5); this puts the words in their stated places
+// The walk the three queries share, one node per turn: leaf(sorted position) tests a triangle; boxes(node, &h0, &h1) says which
+// children to enter and returns whether child 0 goes first.  The other child waits in the lane's stack column; a full column drops it
+// and reports it, and cap visits end any walk
+template <class Boxes, class Leaf>
+__device__ inline void walk(const BvhNode* __restrict__ nodes, uint32_t n, unsigned long long cap, int32_t (*stack)[RC_WAVE], uint32_t lane,
+                            Boxes boxes, Leaf leaf, unsigned long long* visits_out, bool* capped, bool* overflow) {
+    unsigned long long visits = 0;
+    int sp = 0;
+    int32_t node = n == 1 ? ~0 : 0;
+    for (;;) {
+        if (visits >= cap) { *capped = true; break; }
+        ++visits;
+        bool pop = true;
+        if (node < 0) {
+            leaf((uint32_t)(~node));
+        } else {
+            const BvhNode* nd = nodes + node;
+            bool h0, h1;
+            const bool first0 = boxes(nd, &h0, &h1);
+            const int32_t c0 = nd->child[0], c1 = nd->child[1];
+            if (h0 && h1) {
+                if (sp < LNR_BVH_STACK) {
+                    stack[sp][lane] = first0 ? c1 : c0;
+                    ++sp;
+                } else {
+                    *overflow = true;
+                }
+                node = first0 ? c0 : c1;
+                pop = false;
+            } else if (h0 || h1) {
+                node = h0 ? c0 : c1;
+                pop = false;
+            }
+        }
+        if (pop) {
+            if (sp == 0) break;
+            --sp;
+            node = stack[sp][lane];
+        }
+    }
+    *visits_out = visits;
+}
+
+__global__ __launch_bounds__(RC_WAVE) void cast_rays_kernel(const BvhHead* __restrict__ h, const BvhNode* __restrict__ nodes,
+                                                            const double* __restrict__ leaf_v, const int32_t* __restrict__ leaf_id,
+                                                            const double* __restrict__ rays, uint32_t n_rays, double t_min, double t_max,
+                                                            double* __restrict__ t_hit, int32_t* __restrict__ ids, double* __restrict__ uvs,
+                                                            unsigned long long* __restrict__ tally) {
+    __shared__ int32_t stack[LNR_BVH_STACK][RC_WAVE];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t i = blockIdx.x * RC_WAVE + lane;
+    unsigned long long cap;
+    const uint32_t n = walk_size(h, &cap);
+    double best_t = INFINITY, best_u = 0.0, best_v = 0.0;
+    int32_t best_id = -1;
+    unsigned long long visits = 0;
+    bool invalid = false, capped = false, overflow = false;
+    if (i < n_rays) {
+        RayCtx r;
+        invalid = !ray_setup(rays, i, t_min, t_max, r);
+        if (!invalid && n > 0) {
+            walk(nodes, n, cap, stack, lane,
+                 [&](const BvhNode* nd, bool* h0, bool* h1) {
+                     double e0, e1;
+                     *h0 = slab(r, nd->lo[0], nd->hi[0], best_t, &e0);
+                     *h1 = slab(r, nd->lo[1], nd->hi[1], best_t, &e1);
+                     return !(e1 < e0);
+                 },
+                 [&](uint32_t j) { hit_leaf(r, leaf_v, leaf_id, j, &best_t, &best_id, &best_u, &best_v); }, &visits, &capped, &overflow);
+        }
+        t_hit[i] = best_t;
+        ids[i] = best_id;
+        if (uvs) {
+            uvs[2 * (size_t)i] = best_u;
+            uvs[2 * (size_t)i + 1] = best_v;
+        }
+    }
+    wave_tally(lane, best_id >= 0, invalid, capped, overflow, visits, tally);
+}
+
+// info_dev doubles as the tally while a walk (cast, closest points, crossing counts) runs (words 1..5); this puts the words in their
+// stated places
 __global__ void cast_info(const BvhHead* __restrict__ h, int64_t* __restrict__ info) {
     const int64_t capped = info[4], overflow = info[5];
     info[0] = (int64_t)(h->status & (RC_ST_BAD_INDEX | RC_ST_TOO_DEEP)) | (capped ? RC_ST_VISIT_CAP : 0) | (overflow ? RC_ST_STACK : 0);
     info[5] = h->nonfinite + h->bad_index;
     info[6] = h->depth;
     info[7] = 0;
+}
+
+// ------------------------------------------------------------------------------------------------ closest points
+__device__ inline double dot3(const double* x, const double* y) { return (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2]; }
+
+// Ericson's region walk as include/loner_hip.h states it, on the triangle at sorted position j: the candidate replaces the best when
+// the answer rule says so
+__device__ inline void closest_leaf(const double* p, double max_d2, const double* __restrict__ leaf_v, const int32_t* __restrict__ leaf_id,
+                                    uint32_t j, double* best_d2, int32_t* best_id, double* best_q, double* best_u, double* best_v) {
+    const double* c = leaf_v + 9 * (size_t)j;
+    double A[3], B[3], ab[3], ac[3], ap[3], bp[3], cp[3], q[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        A[a] = c[a];
+        B[a] = c[3 + a];
+        ab[a] = c[3 + a] - c[a];
+        ac[a] = c[6 + a] - c[a];
+        ap[a] = p[a] - c[a];
+        bp[a] = p[a] - c[3 + a];
+        cp[a] = p[a] - c[6 + a];
+    }
+    const double d1 = dot3(ab, ap), d2 = dot3(ac, ap), d3 = dot3(ab, bp), d4 = dot3(ac, bp), d5 = dot3(ab, cp), d6 = dot3(ac, cp);
+    const double vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+    double vB, wC;                                      // the weights of B and C
+    if (d1 <= 0.0 && d2 <= 0.0) {
+        vB = 0.0; wC = 0.0;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) q[a] = A[a];
+    } else if (d3 >= 0.0 && d4 <= d3) {
+        vB = 1.0; wC = 0.0;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) q[a] = B[a];
+    } else if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) {
+        vB = d1 / (d1 - d3); wC = 0.0;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) q[a] = A[a] + vB * ab[a];
+    } else if (d6 >= 0.0 && d5 <= d6) {
+        vB = 0.0; wC = 1.0;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) q[a] = c[6 + a];
+    } else if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0) {
+        vB = 0.0; wC = d2 / (d2 - d6);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) q[a] = A[a] + wC * ac[a];
+    } else if (va <= 0.0 && (d4 - d3) >= 0.0 && (d5 - d6) >= 0.0) {
+        wC = (d4 - d3) / ((d4 - d3) + (d5 - d6));
+        vB = 1.0 - wC;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) q[a] = B[a] + wC * (c[6 + a] - B[a]);
+    } else {
+        const double den = 1.0 / ((va + vb) + vc);
+        vB = vb * den; wC = vc * den;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) q[a] = (A[a] + ab[a] * vB) + ac[a] * wC;
+    }
+    double pq[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) pq[a] = p[a] - q[a];
+    const double dd = dot3(pq, pq);
+    if (!(dd <= max_d2)) return;                        // a NaN is no candidate
+    const int32_t id = leaf_id[j];
+    if (*best_id < 0 || dd < *best_d2 || (dd == *best_d2 && id < *best_id)) {
+        *best_d2 = dd;
+        *best_id = id;
+        best_q[0] = q[0]; best_q[1] = q[1]; best_q[2] = q[2];
+        *best_u = (1.0 - vB) - wC;
+        *best_v = vB;
+    }
+}
+
+// A lower bound of every squared distance closest_leaf computes for a triangle inside the box [lo, hi].  With M = max(|lo_a|, |hi_a|,
+// |p_a|): the computed q_a is a convex combination of corners in [lo_a, hi_a] up to the rounding of the rule's own operations; with
+// weights in [0, 1] that is a few ulps of M, and inside the triangle, where the weights come from differences of products of the d's,
+// about 2^-53 M r^2 for a triangle of aspect ratio r = edge^2 / (2 area).  So |p_a - q_a| >= g_a - e M with g_a = max(lo_a - p_a,
+// p_a - hi_a, 0), and the relative part alone would not do: at a box face g_a is 0 or tiny while e M is not, hence the absolute
+// reduction by RC_PAD M (2^-36 M: 10^5 ulps of M, r up to 300) and the clamp at 0.  Rounding is monotone, so with reduced gaps no
+// larger than |p_a - q_a| their squares, summed in dot3's order, are no larger than the computed dot3(p - q, p - q).  A NaN cannot
+// arise: p is finite here and so are the boxes of usable triangles
+__device__ inline double box_bound(const double* p, const double* lo, const double* hi) {
+    double g[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double gap = fmax(fmax(lo[a] - p[a], p[a] - hi[a]), 0.0);
+        g[a] = fmax(gap - RC_PAD * fmax(fmax(fabs(lo[a]), fabs(hi[a])), fabs(p[a])), 0.0);
+    }
+    return dot3(g, g);
+}
+
+__global__ __launch_bounds__(RC_WAVE) void closest_points_kernel(const BvhHead* __restrict__ h, const BvhNode* __restrict__ nodes,
+                                                                 const double* __restrict__ leaf_v, const int32_t* __restrict__ leaf_id,
+                                                                 const double* __restrict__ points, uint32_t n_points, double max_d2,
+                                                                 double* __restrict__ dist_sq, int32_t* __restrict__ ids,
+                                                                 double* __restrict__ closest, double* __restrict__ uvs,
+                                                                 unsigned long long* __restrict__ tally) {
+    __shared__ int32_t stack[LNR_BVH_STACK][RC_WAVE];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t i = blockIdx.x * RC_WAVE + lane;
+    unsigned long long cap;
+    const uint32_t n = walk_size(h, &cap);
+    double best_d2 = INFINITY, best_u = 0.0, best_v = 0.0, best_q[3] = {0.0, 0.0, 0.0};
+    int32_t best_id = -1;
+    unsigned long long visits = 0;
+    bool invalid = false, capped = false, overflow = false;
+    if (i < n_points) {
+        const double p[3] = {points[3 * (size_t)i], points[3 * (size_t)i + 1], points[3 * (size_t)i + 2]};
+        invalid = !finite3(p[0], p[1], p[2]);
+        if (!invalid && n > 0) {
+            walk(nodes, n, cap, stack, lane,
+                 [&](const BvhNode* nd, bool* h0, bool* h1) {
+                     const double b0 = box_bound(p, nd->lo[0], nd->hi[0]), b1 = box_bound(p, nd->lo[1], nd->hi[1]);
+                     *h0 = !(b0 > best_d2) && !(b0 > max_d2);
+                     *h1 = !(b1 > best_d2) && !(b1 > max_d2);
+                     return !(b1 < b0);
+                 },
+                 [&](uint32_t j) { closest_leaf(p, max_d2, leaf_v, leaf_id, j, &best_d2, &best_id, best_q, &best_u, &best_v); }, &visits,
+                 &capped, &overflow);
+        }
+        dist_sq[i] = best_d2;
+        ids[i] = best_id;
+        if (closest) {
+            closest[3 * (size_t)i] = best_q[0];
+            closest[3 * (size_t)i + 1] = best_q[1];
+            closest[3 * (size_t)i + 2] = best_q[2];
+        }
+        if (uvs) {
+            uvs[2 * (size_t)i] = best_u;
+            uvs[2 * (size_t)i + 1] = best_v;
+        }
+    }
+    wave_tally(lane, best_id >= 0, invalid, capped, overflow, visits, tally);
+}
+
+// ------------------------------------------------------------------------------------------------ crossing counts
+__global__ __launch_bounds__(RC_WAVE) void count_intersections_kernel(const BvhHead* __restrict__ h, const BvhNode* __restrict__ nodes,
+                                                                      const double* __restrict__ leaf_v, const double* __restrict__ rays,
+                                                                      uint32_t n_rays, double t_min, double t_max,
+                                                                      int32_t* __restrict__ counts, unsigned long long* __restrict__ tally) {
+    __shared__ int32_t stack[LNR_BVH_STACK][RC_WAVE];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t i = blockIdx.x * RC_WAVE + lane;
+    unsigned long long cap;
+    const uint32_t n = walk_size(h, &cap);
+    int32_t count = 0;
+    unsigned long long visits = 0;
+    bool invalid = false, capped = false, overflow = false;
+    if (i < n_rays) {
+        RayCtx r;
+        invalid = !ray_setup(rays, i, t_min, t_max, r);
+        if (!invalid && n > 0) {
+            walk(nodes, n, cap, stack, lane,
+                 [&](const BvhNode* nd, bool* h0, bool* h1) {
+                     double e0, e1;
+                     *h0 = slab(r, nd->lo[0], nd->hi[0], INFINITY, &e0);
+                     *h1 = slab(r, nd->lo[1], nd->hi[1], INFINITY, &e1);
+                     return true;
+                 },
+                 [&](uint32_t j) {
+                     double t, U, V, det;
+                     if (hit_rule(r, leaf_v, j, &t, &U, &V, &det)) ++count;
+                 },
+                 &visits, &capped, &overflow);
+        }
+        counts[i] = count;
+    }
+    wave_tally(lane, count > 0, invalid, capped, overflow, visits, tally);
 }
 
 // ------------------------------------------------------------------------------------------------ trajectory rays
@@ -640,6 +856,46 @@ extern "C" int lnr_cast_rays(const void* bvh, int64_t n_triangles, const double*
                            (unsigned long long*)(info_dev + 1));
     hipLaunchKernelGGL(cast_info, dim3(1), dim3(1), 0, st, (const BvhHead*)(bb + b.head), info_dev);
     LNR_CHECK_LAUNCH("lnr_cast_rays");
+    return LNR_OK;
+}
+
+extern "C" int lnr_closest_points(const void* bvh, int64_t n_triangles, const double* points, int64_t n_points, double max_distance_sq,
+                                  double* dist_sq, int32_t* primitive_ids, double* closest, double* primitive_uvs, int64_t* info_dev,
+                                  void* stream) {
+    CL_REQUIRE_COUNTS("lnr_closest_points", n_triangles, "triangles", n_points, "points");
+    LNR_REQUIRE(!(max_distance_sq != max_distance_sq), "lnr_closest_points: max_distance_sq is NaN");
+    LNR_REQUIRE(bvh && info_dev && (n_points == 0 || (points && dist_sq && primitive_ids)), "lnr_closest_points: null argument");
+    const BvhLayout b = bvh_layout(n_triangles);
+    const char* bb = (const char*)bvh;
+    hipStream_t st = (hipStream_t)stream;
+    LnrProfScope prof("closest_points", st);
+    if (int rc = clear_words(info_dev, 8 * sizeof(int64_t), st, "lnr_closest_points", "info words")) return rc;
+    if (n_points > 0)
+        hipLaunchKernelGGL(closest_points_kernel, dim3((uint32_t)((n_points + RC_WAVE - 1) / RC_WAVE)), dim3(RC_WAVE), 0, st,
+                           (const BvhHead*)(bb + b.head), (const BvhNode*)(bb + b.nodes), (const double*)(bb + b.leaf_v),
+                           (const int32_t*)(bb + b.leaf_id), points, (uint32_t)n_points, max_distance_sq, dist_sq, primitive_ids, closest,
+                           primitive_uvs, (unsigned long long*)(info_dev + 1));
+    hipLaunchKernelGGL(cast_info, dim3(1), dim3(1), 0, st, (const BvhHead*)(bb + b.head), info_dev);
+    LNR_CHECK_LAUNCH("lnr_closest_points");
+    return LNR_OK;
+}
+
+extern "C" int lnr_count_intersections(const void* bvh, int64_t n_triangles, const double* rays, int64_t n_rays, double t_min, double t_max,
+                                       int32_t* counts, int64_t* info_dev, void* stream) {
+    CL_REQUIRE_COUNTS("lnr_count_intersections", n_triangles, "triangles", n_rays, "rays");
+    LNR_REQUIRE(!(t_min != t_min) && !(t_max != t_max), "lnr_count_intersections: t_min or t_max is NaN");
+    LNR_REQUIRE(bvh && info_dev && (n_rays == 0 || (rays && counts)), "lnr_count_intersections: null argument");
+    const BvhLayout b = bvh_layout(n_triangles);
+    const char* bb = (const char*)bvh;
+    hipStream_t st = (hipStream_t)stream;
+    LnrProfScope prof("count_intersections", st);
+    if (int rc = clear_words(info_dev, 8 * sizeof(int64_t), st, "lnr_count_intersections", "info words")) return rc;
+    if (n_rays > 0)
+        hipLaunchKernelGGL(count_intersections_kernel, dim3((uint32_t)((n_rays + RC_WAVE - 1) / RC_WAVE)), dim3(RC_WAVE), 0, st,
+                           (const BvhHead*)(bb + b.head), (const BvhNode*)(bb + b.nodes), (const double*)(bb + b.leaf_v), rays,
+                           (uint32_t)n_rays, t_min, t_max, counts, (unsigned long long*)(info_dev + 1));
+    hipLaunchKernelGGL(cast_info, dim3(1), dim3(1), 0, st, (const BvhHead*)(bb + b.head), info_dev);
+    LNR_CHECK_LAUNCH("lnr_count_intersections");
     return LNR_OK;
 }
 

@@ -26,6 +26,8 @@ SKY_MAX_RAYS = 65160         # LNR_SKY_MAX_RAYS
 SCAN_MAX_FOV_SEGMENTS = 8    # LNR_SCAN_MAX_FOV_SEGMENTS
 RAYCAST_INFO = 8             # LNR_RAYCAST_INFO
 BVH_STACK = 96               # LNR_BVH_STACK
+OCCUPANCY_DIRECTIONS = ((1.0, 0.4142135623730951, 0.7320508075688772), (-0.6180339887498949, 1.0, 0.3027756377319946),
+                        (0.2360679774997897, -0.7071067811865476, 1.0))      # LNR_OCCUPANCY_DIRECTIONS
 SCAN_TIME_NONE, SCAN_TIME_GIVEN, SCAN_TIME_RECOMPUTE = 0, 1, 2       # LNR_SCAN_TIME_*
 SCAN_NANOSECONDS, SCAN_NEGATIVE_START, SCAN_LOCAL, SCAN_GLOBAL, SCAN_CONSTANT, SCAN_NO_TIMES = 1, 2, 4, 8, 16, 32     # LNR_SCAN_* flag bits
 
@@ -155,6 +157,8 @@ _SIGNATURES = {
     "lnr_bvh_bytes": (C.c_size_t, [C.c_int64]),
     "lnr_bvh_build": (C.c_int, [P, C.c_int64, P, C.c_int64, P, C.c_size_t, P, C.c_size_t, P, P]),
     "lnr_cast_rays": (C.c_int, [P, C.c_int64, P, C.c_int64, C.c_double, C.c_double, P, P, P, P, P]),
+    "lnr_closest_points": (C.c_int, [P, C.c_int64, P, C.c_int64, C.c_double, P, P, P, P, P, P]),
+    "lnr_count_intersections": (C.c_int, [P, C.c_int64, P, C.c_int64, C.c_double, C.c_double, P, P, P]),
     "lnr_trajectory_rays": (C.c_int, [P, P, C.c_int64, P, P, P, P, C.c_int64, P, P, P]),
     "lnr_frame_cloud": (C.c_int, [P, P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, P, P]),
     "lnr_motion_compensate": (C.c_int, [P, P, P, C.c_int32, C.c_int64, C.c_double, C.c_double, C.POINTER(C.c_double), P]),

@@ -1201,6 +1201,74 @@ def cast_rays(bvh, rays, t_min=0.0, t_max=math.inf, want_uvs=True, stats=None):
     return t_hit, ids, uvs
 
 
+def _walk_stats(what, info, stats, first, second):
+    """the one host read of a BVH walk: raise on a status bit, else fill stats under the call's own names for words 1 and 2"""
+    host = info.cpu()
+    status = int(host[0])
+    if status:
+        raise RuntimeError(f"{what}: " + ", ".join(m for b, m in _CAST_STATUS.items() if status & b))
+    stats.update({first: int(host[1]), second: int(host[2])}, node_visits=int(host[3]), capped=int(host[4]),
+                 excluded_triangles=int(host[5]), depth=int(host[6]))
+
+
+def closest_points(bvh, points, max_distance=math.inf, want_points=True, want_uvs=True, stats=None):
+    """open3d's RaycastingScene.compute_closest_points with a reach (include/loner_hip.h: lnr_closest_points): points [n,3] (a float
+    dtype) on the BVH's device -> (dist_sq fp64 [n], +inf with no triangle within max_distance; primitive_ids int32 [n], -1 then;
+    closest fp64 [n,3] or None; primitive_uvs fp64 [n,2] or None).  stats (a dict, optional) receives {"answered", "invalid_points",
+    "node_visits", "capped", "excluded_triangles", "depth"} at the price of one device -> host read, which then also raises
+    RuntimeError on a status bit; without it nothing is read back."""
+    if not isinstance(bvh, BVH):
+        raise ValueError(f"closest_points: bvh must be an ops.BVH, got {type(bvh).__name__}")
+    if not torch.is_tensor(points) or points.dim() != 2 or points.shape[1] != 3 or not points.dtype.is_floating_point:
+        raise ValueError(f"closest_points: points [n,3] of a float dtype, got {tuple(getattr(points, 'shape', ()))} "
+                         f"{getattr(points, 'dtype', type(points).__name__)}")
+    reach = float(max_distance)
+    if math.isnan(reach) or reach < 0:
+        raise ValueError(f"closest_points: max_distance must be a number >= 0, got {max_distance!r}")
+    if points.device != bvh.device:
+        raise ValueError(f"closest_points: points on {points.device}, the BVH on {bvh.device}")
+    require_device(points)
+    p = points.to(torch.float64).contiguous()
+    n, dev = p.shape[0], p.device
+    dist_sq = torch.empty(n, device=dev, dtype=torch.float64)
+    ids = torch.empty(n, device=dev, dtype=torch.int32)
+    closest = torch.empty(n, 3, device=dev, dtype=torch.float64) if want_points else None
+    uvs = torch.empty(n, 2, device=dev, dtype=torch.float64) if want_uvs else None
+    info = torch.empty(hip.RAYCAST_INFO, device=dev, dtype=torch.int64)
+    check(load().lnr_closest_points(_ptr(bvh.buf), bvh.n_triangles, _ptr(p), n, reach * reach, _ptr(dist_sq), _ptr(ids), _ptr(closest),
+                                    _ptr(uvs), _ptr(info), _stream()), "lnr_closest_points")
+    if stats is not None:
+        _walk_stats("closest_points", info, stats, "answered", "invalid_points")
+    return dist_sq, ids, closest, uvs
+
+
+def count_intersections(bvh, rays, t_min=0.0, t_max=math.inf, stats=None):
+    """open3d's RaycastingScene.count_intersections with a window (include/loner_hip.h: lnr_count_intersections): rays [n,6] (a float
+    dtype) on the BVH's device -> counts int32 [n], the triangles each ray crosses with t_min <= t <= t_max.  stats (a dict,
+    optional) receives {"rays_crossing", "invalid_rays", "node_visits", "capped", "excluded_triangles", "depth"} at the price of one
+    device -> host read, which then also raises RuntimeError on a status bit."""
+    if not isinstance(bvh, BVH):
+        raise ValueError(f"count_intersections: bvh must be an ops.BVH, got {type(bvh).__name__}")
+    if not torch.is_tensor(rays) or rays.dim() != 2 or rays.shape[1] != 6 or not rays.dtype.is_floating_point:
+        raise ValueError(f"count_intersections: rays [n,6] of a float dtype, got {tuple(getattr(rays, 'shape', ()))} "
+                         f"{getattr(rays, 'dtype', type(rays).__name__)}")
+    lo, hi = float(t_min), float(t_max)
+    if math.isnan(lo) or math.isnan(hi):
+        raise ValueError(f"count_intersections: t_min and t_max must be numbers, got {t_min!r} and {t_max!r}")
+    if rays.device != bvh.device:
+        raise ValueError(f"count_intersections: rays on {rays.device}, the BVH on {bvh.device}")
+    require_device(rays)
+    r = rays.to(torch.float64).contiguous()
+    n, dev = r.shape[0], r.device
+    counts = torch.empty(n, device=dev, dtype=torch.int32)
+    info = torch.empty(hip.RAYCAST_INFO, device=dev, dtype=torch.int64)
+    check(load().lnr_count_intersections(_ptr(bvh.buf), bvh.n_triangles, _ptr(r), n, lo, hi, _ptr(counts), _ptr(info), _stream()),
+          "lnr_count_intersections")
+    if stats is not None:
+        _walk_stats("count_intersections", info, stats, "rays_crossing", "invalid_rays")
+    return counts
+
+
 def trajectory_rays(directions, timestamps, trajectory):
     """The rays of a sensor that moves while it sweeps (include/loner_hip.h: lnr_trajectory_rays): directions [3,n] fp32 in the sensor
     frame, timestamps [n] (absolute, widened to fp64), trajectory a Trajectory on the same device -> (rays fp64 [n,6], NaN where the
