@@ -1,6 +1,6 @@
 """Run LiDAR SLAM on a folder of scans.
 
-    python examples/run_sequence.py <folder> [--gt poses_tum.txt] [--gt-mesh mesh.ply [--mesh-resolution 0.1]]
+    python examples/run_sequence.py <folder> [--gt poses_tum.txt] [--gt-mesh mesh.ply [--mesh-resolution 0.1] [--tsdf-baseline]]
                                     [--out ~/LonerSLAM/outputs] [--name run] [--ray-range 1 50]
 
 <folder> holds one `.npy` file per scan, [N,4] columns x, y, z, t (t: per-point time, local to the scan or global, seconds or
@@ -9,7 +9,10 @@ qy qz qw) every scan gets the ground-truth pose nearest in time, the world cube 
 trajectory is scored against it; without it the cube comes from system.world_cube.trajectory_bounding_box.  With --gt-mesh (the
 .ply the scans were simulated from, or surveyed) the trained map is meshed at --mesh-resolution over the ground-truth mesh's box grown
 by 1 m, written to <log>/meshes/, and scored against that mesh with the exact point-to-surface distance
-(mesh_eval.evaluate_mesh_to_mesh).  The log directory holds the checkpoints, the four trajectory files and the configuration, as the
+(mesh_eval.evaluate_mesh_to_mesh).  With --tsdf-baseline (needs --gt-mesh) the scan files are then read again and fused into a TSDF
+volume (analysis/tsdf.py) along estimated_trajectory.txt and, with --gt, along the ground truth, every ray from the pose at its own
+time; both volumes are meshed at --mesh-resolution over the same box, written beside the neural mesh and scored the same way: the
+ground-truth one shows what the scans support at that resolution, the estimated one what the tracking costs.  The log directory holds the checkpoints, the four trajectory files and the configuration, as the
 analysis tools of this package expect them."""
 import argparse
 import glob
@@ -35,11 +38,14 @@ def main():
     ap.add_argument("--gt")
     ap.add_argument("--gt-mesh")
     ap.add_argument("--mesh-resolution", type=float, default=0.1)
+    ap.add_argument("--tsdf-baseline", action="store_true")
     ap.add_argument("--out", default="~/LonerSLAM/outputs")
     ap.add_argument("--name", default=None)
     ap.add_argument("--ray-range", type=float, nargs=2, default=(1.0, 50.0))
     ap.add_argument("--log-level", default="STANDARD", choices=("DISABLED", "STANDARD", "VERBOSE"))
     args = ap.parse_args()
+    if args.tsdf_baseline and not args.gt_mesh:
+        raise SystemExit("--tsdf-baseline needs --gt-mesh")
 
     files = sorted(glob.glob(os.path.join(args.folder, "*.npy")))
     stamps = np.loadtxt(os.path.join(args.folder, "stamps.txt"), dtype=np.float64, ndmin=1)
@@ -76,6 +82,13 @@ def main():
         print("APE (aligned, m): " + ", ".join(f"{k} {score[k]:.4f}" for k in ("rmse", "mean", "median", "std", "min", "max")))
     if args.gt_mesh:
         score_against_mesh(loner, args.gt_mesh, args.mesh_resolution, args.ray_range, log)
+    if args.tsdf_baseline:
+        device = loner._mapper._optimizer._device
+        scans = reread_scans(files, stamps, fov, device)
+        tsdf_baseline("estimated trajectory", "estimated", scans, os.path.join(log, "trajectory", "estimated_trajectory.txt"), args.gt_mesh,
+                      args.mesh_resolution, log, device)
+        if args.gt:
+            tsdf_baseline("ground-truth trajectory", "gt", scans, args.gt, args.gt_mesh, args.mesh_resolution, log, device)
 
 
 def score_against_mesh(loner, gt_mesh_path, resolution, ray_range, log):
@@ -99,6 +112,41 @@ def score_against_mesh(loner, gt_mesh_path, resolution, ray_range, log):
     score = evaluate_mesh_to_mesh(mesh, gt_mesh, device=device)
     print(f"mesh: {mesh.triangles.shape[0]} triangles written to {out}")
     print("map against the ground-truth mesh (exact distances, m; shares at 0.1 m): " +
+          ", ".join(f"{k} {score[k]:.4f}" for k in ("accuracy", "completion", "chamfer", "precision", "recall", "f_score")))
+
+
+def reread_scans(files, stamps, fov, device):
+    """The scan files once more, as the run ingested them (build_scan_from_points: directions, ranges, absolute fp32 times)"""
+    scans = []
+    for path, stamp in zip(files, stamps):
+        points = np.load(path)
+        scan, _ = build_scan_from_points(points[:, :3].astype(np.float32), points[:, 3], float(stamp), fov=fov)
+        scans.append(scan.to(device))
+    return scans
+
+
+def tsdf_baseline(what, tag, scans, trajectory, gt_mesh_path, resolution, log, device):
+    """Fuse the scans along a trajectory (a TUM file) into a TSDF volume over the neural mesh's box, mesh it at the same resolution,
+    write it beside the neural mesh and print the same evaluate_mesh_to_mesh line"""
+    from loner_amd.analysis.mesh_eval import evaluate_mesh_to_mesh
+    from loner_amd.analysis.mesher import TriangleMesh
+    from loner_amd.analysis.tsdf import fuse_scans
+    gt_mesh = TriangleMesh.read_ply(gt_mesh_path)
+    bound = (gt_mesh.vertices.min(axis=0) - 1.0, gt_mesh.vertices.max(axis=0) + 1.0)
+    stats = {}
+    volume = fuse_scans(scans, trajectory, bound, resolution, device=device, stats=stats)
+    print(f"TSDF on the {what}: {stats['scans'] - stats['skipped_scans']} of {stats['scans']} scans fused (a scan whose sweep leaves "
+          f"the trajectory's time span is left out), {stats.get('node_updates', 0)} node updates")
+    mesh = volume.extract_mesh()
+    if mesh is None:
+        print(f"TSDF on the {what} against the ground-truth mesh: the volume has no surface to score")
+        return
+    os.makedirs(os.path.join(log, "meshes"), exist_ok=True)
+    out = os.path.join(log, "meshes", f"tsdf_{tag}_{resolution}.ply")
+    mesh.write_ply(out)
+    score = evaluate_mesh_to_mesh(mesh, gt_mesh, device=device)
+    print(f"mesh: {mesh.triangles.shape[0]} triangles written to {out}")
+    print(f"TSDF on the {what} against the ground-truth mesh (exact distances, m; shares at 0.1 m): " +
           ", ".join(f"{k} {score[k]:.4f}" for k in ("accuracy", "completion", "chamfer", "precision", "recall", "f_score")))
 
 

@@ -476,6 +476,17 @@ int lnr_mc_emit(const float* volume, int32_t nx, int32_t ny, int32_t nz, float l
                 float* verts, int32_t* tris, void* stream);
 /* host only: the case table, out [256 * LNR_MC_TABLE_WIDTH] */
 int lnr_mc_case_table(int8_t* out);
+/* The same pair over the observed part of a volume: valid uint8 [nx][ny][nz], a node counts as valid when its byte is not 0.  A
+ * lattice edge carries a vertex only when both its ends are valid and differ; a cell emits its case's triangles only when all eight
+ * corners are valid (the rule of scikit-image's `mask`).  Vertex and triangle order, the arithmetic, the workspace and the two-call
+ * protocol are those above; with every node valid the outputs are the unmasked pair's byte for byte.  A vertex on an edge whose
+ * four cells all lost a corner is emitted and used by no triangle (lnr_mesh_select drops such vertices), so V > 0 with F = 0 is
+ * possible: tris may then be NULL. */
+int lnr_mc_count_masked(const float* volume, const uint8_t* valid, int32_t nx, int32_t ny, int32_t nz, float level, void* workspace,
+                        size_t workspace_bytes, uint64_t* totals_dev, void* stream);
+int lnr_mc_emit_masked(const float* volume, const uint8_t* valid, int32_t nx, int32_t ny, int32_t nz, float level,
+                       const float* spacing /*host [3]*/, const float* origin /*host [3]*/, void* workspace, size_t workspace_bytes,
+                       int64_t n_verts, int64_t n_tris, float* verts, int32_t* tris, void* stream);
 
 /* ---- point clouds (analysis/renderer_lidar.py:71-91, :296-349; analysis/evaluate_lidar_map.py:16-98) ----------------------- */
 /* Points are fp64 [n,3] (x y z per point), n <= 2^31 - 4096 per call (LNR_ERR_INVALID_ARG beyond).  Every fp64 expression rounds
@@ -853,7 +864,42 @@ int lnr_trajectory_rays(const float* directions, const double* timestamps, int64
                         const double* traj_positions, const double* traj_rotations, const double* traj_rotvecs, int64_t n_poses,
                         double* rays, int64_t* info_dev, void* stream);
 
-/* ---- tracking (src/common/frame.py:104-145; src/common/sensors.py:176-232; src/tracking/tracker.py:257-297) ----------------- */
+/* ---- TSDF fusion (no counterpart in the reference; open3d's UniformTSDFVolume for range rays) --------------------------------- */
+/* A dense volume of nx ny nz lattice nodes (each >= 2, the product < 2^31), z fastest: the layout the marching cubes above read.  Node
+ * (i, j, k) lies at origin_a + (double) index_a * v per axis (origin: host fp64 [3], v = voxel_size; one multiply, one add); its voxel
+ * is the cube of edge v centred on it.  Per node the caller owns, and zeroes, sum (int64) and count (uint32).  Every fp64 expression
+ * here rounds operation by operation (no fma), and divides are IEEE.
+ *
+ * lnr_tsdf_integrate adds rays to the volume: rays fp64 [n_rays,6] = (o, d) as lnr_trajectory_rays writes them (d of unit length:
+ * t below is metres along it), ranges fp64 [n_rays] (r), trunc > 0 and front >= trunc (+inf: free space is carved from the origin
+ * on), n_rays < 2^32 - 256.  A ray is left out and counted as invalid when a component of o or d is not finite, d is zero, r is not
+ * finite or r <= 0, or a grid-frame value below is not finite.  The grid frame puts voxel i of an axis on [i, i + 1):
+ *   go_a = (o_a - origin_a) / v + 0.5,   gd_a = d_a / v.
+ * The segment is t0 = max(0, r - front), t1 = r + trunc, clipped to the box [0, n_a] by slabs: per axis, with gd_a == 0 the ray misses
+ * unless 0 <= go_a < n_a; otherwise ta = (0 - go_a) / gd_a, tb = (n_a - go_a) / gd_a, t0 = max(t0, min(ta, tb)), t1 = min(t1,
+ * max(ta, tb)).  The ray misses the box, and is counted so, unless t0 < t1.
+ * The walk is that of Amanatides and Woo (1987).  It enters at the grid coordinate e_a = go_a + t0 * gd_a, in voxel c_a = floor(e_a)
+ * clamped to [0, n_a - 1].  Per axis step_a = sign(gd_a), tDelta_a = 1 / |gd_a| and tMax_a = ((c_a + (1 if gd_a > 0 else 0)) - go_a)
+ * / gd_a, the t of the voxel's face ahead; an axis with gd_a == 0 has tMax_a = +inf and never steps.  Then, repeatedly: the voxel c
+ * is visited; a is the axis of the smallest tMax, a tie going to x before y before z (a = x when tMax_x <= tMax_y and tMax_x <=
+ * tMax_z, else y when tMax_y <= tMax_z, else z); the walk stops unless tMax_a < t1, and stops when c_a + step_a leaves [0, n_a - 1];
+ * otherwise c_a += step_a and tMax_a += tDelta_a.
+ * A visited voxel with node p gets s = r - (((p_x - o_x) * d_x + (p_y - o_y) * d_y) + (p_z - o_z) * d_z).  Nothing is written unless
+ * s >= -trunc; otherwise q = llrint(min(s / trunc, 1) * 1048576) (ties to even), sum[node] += q and count[node] += 1, both integer
+ * atomics whose result is not used: a volume does not depend on the order of waves, rays or calls, and is the same on every run.  A
+ * ray updates a node at most once.  info_dev int64 [8], written by the call: {status (0), rays that updated at least one node,
+ * invalid rays, rays that miss the box, node updates, 0, 0, 0}.
+ *
+ * lnr_tsdf_field reads the volume (min_count >= 1): field fp32 [nx][ny][nz] = (float) (-(double) sum / ((double) count * 1048576.0))
+ * where count > 0 and 0 elsewhere; valid uint8 = 1 where count >= min_count, else 0.  The sign is flipped: field > 0 behind the
+ * surface, which the marching cubes above call inside, so that their triangles face the sensor's side. */
+int lnr_tsdf_integrate(const double* rays, const double* ranges, int64_t n_rays, int32_t nx, int32_t ny, int32_t nz,
+                       const double* origin /*host [3]*/, double voxel_size, double trunc, double front, int64_t* sum, uint32_t* count,
+                       int64_t* info_dev, void* stream);
+int lnr_tsdf_field(const int64_t* sum, const uint32_t* count, int32_t nx, int32_t ny, int32_t nz, uint32_t min_count, float* field,
+                   uint8_t* valid, void* stream);
+
+/* ---- tracking(src/common/frame.py:104-145; src/common/sensors.py:176-232; src/tracking/tracker.py:257-297) ----------------- */
 #define LNR_MOCOMP_CONSTS 30      /* fp64 entries of lnr_motion_compensate's consts */
 #define LNR_SKY_MAX_RAYS 65160    /* 181 x 360: the row stride lnr_sky_rays' output needs */
 

@@ -179,28 +179,34 @@ __device__ __forceinline__ void mc_ijk(uint32_t node, const McDims& d, uint32_t&
     k = r - j * d.nz;
 }
 
-// bits 0..2: the node's +x / +y / +z edge crosses the level
-__device__ __forceinline__ uint32_t mc_edge_bits(const float* __restrict__ v, uint32_t node, uint32_t i, uint32_t j, uint32_t k,
-                                                 const McDims& d, float level) {
+// bits 0..2: the node's +x / +y / +z edge crosses the level.  MASKED (lnr_mc_*_masked): and both its ends are valid
+template <bool MASKED>
+__device__ __forceinline__ uint32_t mc_edge_bits(const float* __restrict__ v, const uint8_t* __restrict__ valid, uint32_t node, uint32_t i,
+                                                 uint32_t j, uint32_t k, const McDims& d, float level) {
+    if (MASKED && !valid[node]) return 0;
     const bool a = v[node] > level;
     uint32_t bits = 0;
-    if (i + 1 < d.nx && (v[node + d.nyz] > level) != a) bits |= 1u;
-    if (j + 1 < d.ny && (v[node + d.nz] > level) != a) bits |= 2u;
-    if (k + 1 < d.nz && (v[node + 1] > level) != a) bits |= 4u;
+    if (i + 1 < d.nx && (!MASKED || valid[node + d.nyz]) && (v[node + d.nyz] > level) != a) bits |= 1u;
+    if (j + 1 < d.ny && (!MASKED || valid[node + d.nz]) && (v[node + d.nz] > level) != a) bits |= 2u;
+    if (k + 1 < d.nz && (!MASKED || valid[node + 1]) && (v[node + 1] > level) != a) bits |= 4u;
     return bits;
 }
 
-// the case of the cell whose lower node this is (0 for nodes on the upper faces: they name no cell)
-__device__ __forceinline__ uint32_t mc_case(const float* __restrict__ v, uint32_t node, uint32_t i, uint32_t j, uint32_t k,
-                                            const McDims& d, float level) {
+// the case of the cell whose lower node this is (0 for nodes on the upper faces: they name no cell).  MASKED: 0 as well for a cell
+// with a corner that is not valid
+template <bool MASKED>
+__device__ __forceinline__ uint32_t mc_case(const float* __restrict__ v, const uint8_t* __restrict__ valid, uint32_t node, uint32_t i,
+                                            uint32_t j, uint32_t k, const McDims& d, float level) {
     if (i + 1 >= d.nx || j + 1 >= d.ny || k + 1 >= d.nz) return 0;
     uint32_t cas = 0;
+    bool all_valid = true;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
         const uint32_t off = ((c & 1) ? d.nyz : 0u) + ((c & 2) ? d.nz : 0u) + ((c & 4) ? 1u : 0u);
         cas |= (v[node + off] > level ? 1u : 0u) << c;
+        if (MASKED) all_valid = all_valid && valid[node + off];
     }
-    return cas;
+    return all_valid ? cas : 0;
 }
 
 __device__ __forceinline__ uint32_t popc64(uint64_t m) { return (uint32_t)__popcll(m); }
@@ -212,8 +218,10 @@ __device__ __forceinline__ uint32_t mc_wave_prefix(uint32_t cnt, uint64_t lt_mas
     return popc64(b0 & lt_mask) + 2u * popc64(b1 & lt_mask) + 4u * popc64(b2 & lt_mask);
 }
 
+template <bool MASKED>
 __global__ void __launch_bounds__(MC_BLOCK)
-mc_count_kernel(const float* __restrict__ v, const McDims d, float level, uint32_t* __restrict__ block_counts) {
+mc_count_kernel(const float* __restrict__ v, const uint8_t* __restrict__ valid, const McDims d, float level,
+                uint32_t* __restrict__ block_counts) {
     __shared__ uint32_t part[MC_BLOCK / 64][2];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t base = blockIdx.x * MC_BLOCK_NODES + wave * MC_WAVE_NODES;
@@ -224,8 +232,8 @@ mc_count_kernel(const float* __restrict__ v, const McDims d, float level, uint32
         if (node < d.n) {
             uint32_t i, j, k;
             mc_ijk(node, d, i, j, k);
-            nv += __popc(mc_edge_bits(v, node, i, j, k, d, level));
-            nt += c_mc_ntri[mc_case(v, node, i, j, k, d, level)];
+            nv += __popc(mc_edge_bits<MASKED>(v, valid, node, i, j, k, d, level));
+            nt += c_mc_ntri[mc_case<MASKED>(v, valid, node, i, j, k, d, level)];
         }
     }
 #pragma unroll
@@ -281,8 +289,10 @@ mc_scan_kernel(const uint32_t* __restrict__ block_counts, int n_blocks, uint64_t
 
 // the first vertex id of the node in bits 2.., its x- and y-edge bits in bits 0 and 1: the id of its vertex on axis a is
 // (w >> 2) + the number of its crossing edges on the axes before a
+template <bool MASKED>
 __global__ void __launch_bounds__(MC_BLOCK)
-mc_vertex_kernel(const float* __restrict__ v, const McDims d, float level, const uint64_t* __restrict__ block_offsets,
+mc_vertex_kernel(const float* __restrict__ v, const uint8_t* __restrict__ valid, const McDims d, float level,
+                 const uint64_t* __restrict__ block_offsets,
                  float sx, float sy, float sz, float ox, float oy, float oz, uint32_t* __restrict__ packed, float* __restrict__ verts,
                  uint64_t n_verts) {
     __shared__ uint32_t wtot[MC_BLOCK / 64];
@@ -298,7 +308,7 @@ mc_vertex_kernel(const float* __restrict__ v, const McDims d, float level, const
         if (node < d.n) {
             uint32_t i, j, k;
             mc_ijk(node, d, i, j, k);
-            bits = mc_edge_bits(v, node, i, j, k, d, level);
+            bits = mc_edge_bits<MASKED>(v, valid, node, i, j, k, d, level);
         }
         bits_all |= (uint64_t)bits << (3 * it);
         uint32_t t;
@@ -342,8 +352,10 @@ mc_vertex_kernel(const float* __restrict__ v, const McDims d, float level, const
     }
 }
 
+template <bool MASKED>
 __global__ void __launch_bounds__(MC_BLOCK)
-mc_triangle_kernel(const float* __restrict__ v, const McDims d, float level, const uint64_t* __restrict__ block_offsets,
+mc_triangle_kernel(const float* __restrict__ v, const uint8_t* __restrict__ valid, const McDims d, float level,
+                   const uint64_t* __restrict__ block_offsets,
                    const uint32_t* __restrict__ packed, int32_t* __restrict__ tris, uint64_t n_tris) {
     __shared__ uint32_t wtot[MC_BLOCK / 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -358,7 +370,7 @@ mc_triangle_kernel(const float* __restrict__ v, const McDims d, float level, con
         if (node < d.n) {
             uint32_t i, j, k;
             mc_ijk(node, d, i, j, k);
-            cas = mc_case(v, node, i, j, k, d, level);
+            cas = mc_case<MASKED>(v, valid, node, i, j, k, d, level);
         }
         cases[it] = cas;
         uint32_t t;
@@ -529,60 +541,91 @@ extern "C" size_t lnr_mc_workspace(int32_t nx, int32_t ny, int32_t nz) {
     return mc_layout((int64_t)nx * ny * nz).total;
 }
 
-extern "C" int lnr_mc_count(const float* volume, int32_t nx, int32_t ny, int32_t nz, float level, void* workspace, size_t workspace_bytes,
-                            uint64_t* totals_dev, void* stream) {
-    if (int rc = mc_check_dims(nx, ny, nz, "lnr_mc_count")) return rc;
-    LNR_REQUIRE(volume && workspace && totals_dev, "lnr_mc_count: null argument");
+namespace {
+template <bool MASKED>
+int mc_count_impl(const char* fn, const float* volume, const uint8_t* valid, int32_t nx, int32_t ny, int32_t nz, float level, void* workspace,
+                  size_t workspace_bytes, uint64_t* totals_dev, void* stream) {
+    if (int rc = mc_check_dims(nx, ny, nz, fn)) return rc;
+    LNR_REQUIRE(volume && workspace && totals_dev && (!MASKED || valid), "%s: null argument", fn);
     const McLayout l = mc_layout((int64_t)nx * ny * nz);
-    LNR_REQUIRE(workspace_bytes >= l.total, "lnr_mc_count: workspace of %zu bytes, %zu needed", workspace_bytes, l.total);
+    LNR_REQUIRE(workspace_bytes >= l.total, "%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes, l.total);
     const McTable& tab = mc_table();
-    LNR_REQUIRE(tab.ntri_ok, "lnr_mc_count: case table overflow");
+    LNR_REQUIRE(tab.ntri_ok, "%s: case table overflow", fn);
     hipStream_t st = (hipStream_t)stream;
     // the table goes to constant memory of the current device with every call (4.3 KB, stream ordered: any device, any stream)
     if (hipMemcpyToSymbolAsync(HIP_SYMBOL(c_mc_table), tab.t, sizeof(tab.t), 0, hipMemcpyHostToDevice, st) != hipSuccess ||
         hipMemcpyToSymbolAsync(HIP_SYMBOL(c_mc_ntri), tab.ntri, sizeof(tab.ntri), 0, hipMemcpyHostToDevice, st) != hipSuccess) {
-        lnr_set_error("lnr_mc_count: upload of the case table failed");
+        lnr_set_error("%s: upload of the case table failed", fn);
         return LNR_ERR_LAUNCH;
     }
     char* ws = (char*)workspace;
     const McDims d = mc_dims(nx, ny, nz);
     {
         LnrProfScope prof("mc_count", st);
-        hipLaunchKernelGGL(mc_count_kernel, dim3(l.n_blocks), dim3(MC_BLOCK), 0, st, volume, d, level, (uint32_t*)(ws + l.counts));
-        LNR_CHECK_LAUNCH("lnr_mc_count");
+        hipLaunchKernelGGL(mc_count_kernel<MASKED>, dim3(l.n_blocks), dim3(MC_BLOCK), 0, st, volume, valid, d, level,
+                           (uint32_t*)(ws + l.counts));
+        LNR_CHECK_LAUNCH(fn);
     }
     {
         LnrProfScope prof("mc_scan", st);
         hipLaunchKernelGGL(mc_scan_kernel, dim3(1), dim3(MC_SCAN_BLOCK), 0, st, (const uint32_t*)(ws + l.counts), l.n_blocks,
                            (uint64_t*)(ws + l.offsets), (unsigned long long*)totals_dev);
-        LNR_CHECK_LAUNCH("lnr_mc_count(scan)");
+        LNR_CHECK_LAUNCH(fn);
     }
     return LNR_OK;
 }
 
-extern "C" int lnr_mc_emit(const float* volume, int32_t nx, int32_t ny, int32_t nz, float level, const float* spacing, const float* origin,
-                           void* workspace, size_t workspace_bytes, int64_t n_verts, int64_t n_tris, float* verts, int32_t* tris, void* stream) {
-    if (int rc = mc_check_dims(nx, ny, nz, "lnr_mc_emit")) return rc;
-    LNR_REQUIRE(volume && workspace && spacing && origin, "lnr_mc_emit: null argument");
-    LNR_REQUIRE(n_verts >= 0 && n_verts < ((int64_t)1 << 30), "lnr_mc_emit: %lld vertices, the limit is 2^30 - 1", (long long)n_verts);
-    LNR_REQUIRE(n_tris >= 0 && (n_verts == 0 || (verts && tris)), "lnr_mc_emit: bad outputs");
+template <bool MASKED>
+int mc_emit_impl(const char* fn, const float* volume, const uint8_t* valid, int32_t nx, int32_t ny, int32_t nz, float level,
+                 const float* spacing, const float* origin, void* workspace, size_t workspace_bytes, int64_t n_verts, int64_t n_tris,
+                 float* verts, int32_t* tris, void* stream) {
+    if (int rc = mc_check_dims(nx, ny, nz, fn)) return rc;
+    LNR_REQUIRE(volume && workspace && spacing && origin && (!MASKED || valid), "%s: null argument", fn);
+    LNR_REQUIRE(n_verts >= 0 && n_verts < ((int64_t)1 << 30), "%s: %lld vertices, the limit is 2^30 - 1", fn, (long long)n_verts);
+    // (masked: vertices whose cells all lost a corner come without a triangle)
+    LNR_REQUIRE(n_tris >= 0 && (n_verts == 0 || (verts && (tris || (MASKED && n_tris == 0)))), "%s: bad outputs", fn);
     const McLayout l = mc_layout((int64_t)nx * ny * nz);
-    LNR_REQUIRE(workspace_bytes >= l.total, "lnr_mc_emit: workspace of %zu bytes, %zu needed", workspace_bytes, l.total);
+    LNR_REQUIRE(workspace_bytes >= l.total, "%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes, l.total);
     if (n_verts == 0) return LNR_OK;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     const McDims d = mc_dims(nx, ny, nz);
     {
         LnrProfScope prof("mc_vertices", st);
-        hipLaunchKernelGGL(mc_vertex_kernel, dim3(l.n_blocks), dim3(MC_BLOCK), 0, st, volume, d, level, (const uint64_t*)(ws + l.offsets),
-                           spacing[0], spacing[1], spacing[2], origin[0], origin[1], origin[2], (uint32_t*)(ws + l.packed), verts, (uint64_t)n_verts);
-        LNR_CHECK_LAUNCH("lnr_mc_emit(vertices)");
+        hipLaunchKernelGGL(mc_vertex_kernel<MASKED>, dim3(l.n_blocks), dim3(MC_BLOCK), 0, st, volume, valid, d, level,
+                           (const uint64_t*)(ws + l.offsets), spacing[0], spacing[1], spacing[2], origin[0], origin[1], origin[2],
+                           (uint32_t*)(ws + l.packed), verts, (uint64_t)n_verts);
+        LNR_CHECK_LAUNCH(fn);
     }
     if (n_tris > 0) {
         LnrProfScope prof("mc_triangles", st);
-        hipLaunchKernelGGL(mc_triangle_kernel, dim3(l.n_blocks), dim3(MC_BLOCK), 0, st, volume, d, level, (const uint64_t*)(ws + l.offsets),
-                           (const uint32_t*)(ws + l.packed), tris, (uint64_t)n_tris);
-        LNR_CHECK_LAUNCH("lnr_mc_emit(triangles)");
+        hipLaunchKernelGGL(mc_triangle_kernel<MASKED>, dim3(l.n_blocks), dim3(MC_BLOCK), 0, st, volume, valid, d, level,
+                           (const uint64_t*)(ws + l.offsets), (const uint32_t*)(ws + l.packed), tris, (uint64_t)n_tris);
+        LNR_CHECK_LAUNCH(fn);
     }
     return LNR_OK;
+}
+}  // namespace
+
+extern "C" int lnr_mc_count(const float* volume, int32_t nx, int32_t ny, int32_t nz, float level, void* workspace, size_t workspace_bytes,
+                            uint64_t* totals_dev, void* stream) {
+    return mc_count_impl<false>("lnr_mc_count", volume, nullptr, nx, ny, nz, level, workspace, workspace_bytes, totals_dev, stream);
+}
+
+extern "C" int lnr_mc_emit(const float* volume, int32_t nx, int32_t ny, int32_t nz, float level, const float* spacing, const float* origin,
+                           void* workspace, size_t workspace_bytes, int64_t n_verts, int64_t n_tris, float* verts, int32_t* tris, void* stream) {
+    return mc_emit_impl<false>("lnr_mc_emit", volume, nullptr, nx, ny, nz, level, spacing, origin, workspace, workspace_bytes, n_verts, n_tris,
+                               verts, tris, stream);
+}
+
+extern "C" int lnr_mc_count_masked(const float* volume, const uint8_t* valid, int32_t nx, int32_t ny, int32_t nz, float level,
+                                   void* workspace, size_t workspace_bytes, uint64_t* totals_dev, void* stream) {
+    return mc_count_impl<true>("lnr_mc_count_masked", volume, valid, nx, ny, nz, level, workspace, workspace_bytes, totals_dev, stream);
+}
+
+extern "C" int lnr_mc_emit_masked(const float* volume, const uint8_t* valid, int32_t nx, int32_t ny, int32_t nz, float level,
+                                  const float* spacing, const float* origin, void* workspace, size_t workspace_bytes, int64_t n_verts,
+                                  int64_t n_tris, float* verts, int32_t* tris, void* stream) {
+    return mc_emit_impl<true>("lnr_mc_emit_masked", volume, valid, nx, ny, nz, level, spacing, origin, workspace, workspace_bytes, n_verts,
+                              n_tris, verts, tris, stream);
 }

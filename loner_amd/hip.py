@@ -125,6 +125,9 @@ _SIGNATURES = {
     "lnr_mc_emit": (C.c_int, [P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), P, C.c_size_t,
                               C.c_int64, C.c_int64, P, P, P]),
     "lnr_mc_case_table": (C.c_int, [P]),
+    "lnr_mc_count_masked": (C.c_int, [P, P, C.c_int32, C.c_int32, C.c_int32, C.c_float, P, C.c_size_t, P, P]),
+    "lnr_mc_emit_masked": (C.c_int, [P, P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), P,
+                                     C.c_size_t, C.c_int64, C.c_int64, P, P, P]),
     "lnr_cloud_workspace": (C.c_size_t, [C.c_int64]),
     "lnr_lidar_scan_points": (C.c_int, [P, P, P, C.c_int64, P, C.c_int64, C.c_float, C.c_float, C.c_float, P, C.c_size_t, P, P, P]),
     "lnr_voxel_down_sample": (C.c_int, [P, C.c_int64, P, C.c_double, P, C.c_size_t, P, P, P]),
@@ -160,6 +163,9 @@ _SIGNATURES = {
     "lnr_closest_points": (C.c_int, [P, C.c_int64, P, C.c_int64, C.c_double, P, P, P, P, P, P]),
     "lnr_count_intersections": (C.c_int, [P, C.c_int64, P, C.c_int64, C.c_double, C.c_double, P, P, P]),
     "lnr_trajectory_rays": (C.c_int, [P, P, C.c_int64, P, P, P, P, C.c_int64, P, P, P]),
+    "lnr_tsdf_integrate": (C.c_int, [P, P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_double, C.c_double,
+                                     C.c_double, P, P, P, P]),
+    "lnr_tsdf_field": (C.c_int, [P, P, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, P, P, P]),
     "lnr_frame_cloud": (C.c_int, [P, P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, P, P]),
     "lnr_motion_compensate": (C.c_int, [P, P, P, C.c_int32, C.c_int64, C.c_double, C.c_double, C.POINTER(C.c_double), P]),
     "lnr_sky_rays_workspace": (C.c_size_t, []),

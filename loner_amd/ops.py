@@ -525,20 +525,32 @@ def mc_case_table():
     return out
 
 
-def marching_cubes(volume, level=0.0, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0)):
+def marching_cubes(volume, level=0.0, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0), valid=None):
     """Marching cubes of a device volume [nx, ny, nz] at `level` (inside: v > level) -> (verts [V,3] fp32, faces [F,3] int32) on the
     device; both empty when nothing crosses the level.  Vertex i lies at index * spacing + origin (include/loner_hip.h: lnr_mc_*).
-    One device -> host read of the two totals sizes the outputs."""
+    One device -> host read of the two totals sizes the outputs.
+    valid (uint8 or bool [nx, ny, nz] on the volume's device, optional): the nodes that were observed (lnr_mc_*_masked); a cell with a
+    corner that is not valid emits nothing, and vertices no surviving cell uses may remain (mesh_select(drop_unreferenced=True))."""
     require_device(volume)
     vol = _f32c(volume)
     assert vol.dim() == 3, "marching_cubes: a 3-D volume [nx, ny, nz]"
     nx, ny, nz = (int(x) for x in vol.shape)
     dev = vol.device
+    if valid is not None:
+        require_device(valid)
+        if tuple(valid.shape) != (nx, ny, nz) or valid.dtype not in (torch.uint8, torch.bool) or valid.device != dev:
+            raise ValueError(f"marching_cubes: valid must be uint8 or bool [{nx},{ny},{nz}] on {dev}, got {valid.dtype} "
+                             f"{tuple(valid.shape)} on {valid.device}")
+        mask = valid.to(torch.uint8).contiguous()
     lib = load()
     ws_bytes = lib.lnr_mc_workspace(nx, ny, nz)
     ws = torch.empty(max(int(ws_bytes), 1), device=dev, dtype=torch.uint8)
     totals = torch.empty(2, device=dev, dtype=torch.int64)
-    check(lib.lnr_mc_count(_ptr(vol), nx, ny, nz, float(level), _ptr(ws), int(ws_bytes), _ptr(totals), _stream()), "lnr_mc_count")
+    if valid is None:
+        check(lib.lnr_mc_count(_ptr(vol), nx, ny, nz, float(level), _ptr(ws), int(ws_bytes), _ptr(totals), _stream()), "lnr_mc_count")
+    else:
+        check(lib.lnr_mc_count_masked(_ptr(vol), _ptr(mask), nx, ny, nz, float(level), _ptr(ws), int(ws_bytes), _ptr(totals), _stream()),
+              "lnr_mc_count_masked")
     n_verts, n_tris = (int(x) for x in totals.cpu())
     if n_verts >= 1 << 30:                          # lnr_mc_emit's limit: refused before the outputs are allocated
         raise RuntimeError(f"marching_cubes: {n_verts} vertices, the limit is 2^30 - 1")
@@ -546,8 +558,12 @@ def marching_cubes(volume, level=0.0, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0,
     faces = torch.empty(n_tris, 3, device=dev, dtype=torch.int32)
     sp = (C.c_float * 3)(*[float(x) for x in spacing])
     org = (C.c_float * 3)(*[float(x) for x in origin])
-    check(lib.lnr_mc_emit(_ptr(vol), nx, ny, nz, float(level), sp, org, _ptr(ws), int(ws_bytes), n_verts, n_tris, _ptr(verts), _ptr(faces),
-                          _stream()), "lnr_mc_emit")
+    if valid is None:
+        check(lib.lnr_mc_emit(_ptr(vol), nx, ny, nz, float(level), sp, org, _ptr(ws), int(ws_bytes), n_verts, n_tris, _ptr(verts),
+                              _ptr(faces), _stream()), "lnr_mc_emit")
+    else:
+        check(lib.lnr_mc_emit_masked(_ptr(vol), _ptr(mask), nx, ny, nz, float(level), sp, org, _ptr(ws), int(ws_bytes), n_verts, n_tris,
+                                     _ptr(verts), _ptr(faces), _stream()), "lnr_mc_emit_masked")
     return verts, faces
 
 
@@ -1290,6 +1306,65 @@ def trajectory_rays(directions, timestamps, trajectory):
     check(load().lnr_trajectory_rays(_ptr(d), _ptr(stamps), n, _ptr(tr.times), _ptr(tr.positions), _ptr(tr.rotations), _ptr(tr.rotvecs),
                                      tr.n_poses, _ptr(rays), _ptr(info), _stream()), "lnr_trajectory_rays")
     return rays, info
+
+
+# ---------------------------------------------------------------- TSDF fusion
+def _tsdf_volume(sum_, count, what):
+    """the checks the two TSDF calls share -> (nx, ny, nz)"""
+    require_device(sum_, count)
+    if sum_.dim() != 3 or sum_.dtype != torch.int64 or count.dtype != torch.uint32 or count.shape != sum_.shape or count.device != sum_.device:
+        raise ValueError(f"{what}: sum int64 [nx,ny,nz] and count uint32 of the same shape on one device, got {sum_.dtype} "
+                         f"{tuple(sum_.shape)} and {count.dtype} {tuple(count.shape)}")
+    nx, ny, nz = (int(x) for x in sum_.shape)
+    if min(nx, ny, nz) < 2 or nx * ny * nz >= 1 << 31:
+        raise ValueError(f"{what}: every axis needs at least two nodes and the volume fewer than 2^31, got {nx} x {ny} x {nz}")
+    return nx, ny, nz
+
+
+def tsdf_integrate(rays, ranges, sum_, count, origin, voxel_size, trunc, front=None):
+    """Adds rays to a TSDF volume in place (include/loner_hip.h: lnr_tsdf_integrate): rays [n,6] (ox oy oz dx dy dz, unit directions)
+    and ranges [n] of a float dtype, sum_ int64 [nx,ny,nz] and count uint32 [nx,ny,nz] (zeroed by the caller before the first call),
+    all on one device; node (i,j,k) lies at origin + (i,j,k) * voxel_size.  front (default: trunc) is how far in front of the return a
+    ray writes; math.inf carves free space from the sensor on.  -> info int64 [8] on the device: {status, rays that updated a node,
+    invalid rays, rays that miss the volume, node updates}."""
+    nx, ny, nz = _tsdf_volume(sum_, count, "tsdf_integrate")
+    require_device(rays, ranges)
+    if rays.dim() != 2 or rays.shape[1] != 6 or not rays.dtype.is_floating_point:
+        raise ValueError(f"tsdf_integrate: rays [n,6] of a float dtype, got {tuple(rays.shape)} {rays.dtype}")
+    n = rays.shape[0]
+    if tuple(ranges.shape) != (n,) or not ranges.dtype.is_floating_point:
+        raise ValueError(f"tsdf_integrate: ranges [{n}] of a float dtype, got {tuple(ranges.shape)} {ranges.dtype}")
+    if rays.device != sum_.device or ranges.device != sum_.device:
+        raise ValueError(f"tsdf_integrate: rays on {rays.device}, ranges on {ranges.device}, the volume on {sum_.device}")
+    v, tr = float(voxel_size), float(trunc)
+    fr = tr if front is None else float(front)
+    org = [float(x) for x in origin]
+    if len(org) != 3 or not all(math.isfinite(x) for x in org):
+        raise ValueError(f"tsdf_integrate: origin must be three finite numbers, got {origin!r}")
+    if not (math.isfinite(v) and v > 0):
+        raise ValueError(f"tsdf_integrate: voxel_size must be finite and > 0, got {voxel_size!r}")
+    if not (math.isfinite(tr) and tr > 0):
+        raise ValueError(f"tsdf_integrate: trunc must be finite and > 0, got {trunc!r}")
+    if not fr >= tr:
+        raise ValueError(f"tsdf_integrate: front must be at least trunc ({tr}), got {front!r}")
+    r = rays.to(torch.float64).contiguous()
+    rng = ranges.to(torch.float64).contiguous()
+    info = torch.empty(8, device=sum_.device, dtype=torch.int64)
+    check(load().lnr_tsdf_integrate(_ptr(r), _ptr(rng), n, nx, ny, nz, (C.c_double * 3)(*org), v, tr, fr, _ptr(sum_), _ptr(count),
+                                    _ptr(info), _stream()), "lnr_tsdf_integrate")
+    return info
+
+
+def tsdf_field(sum_, count, min_count=1):
+    """A TSDF volume's mean (include/loner_hip.h: lnr_tsdf_field) -> (field fp32 [nx,ny,nz]: minus the mean truncated distance in units
+    of trunc, > 0 behind the surface, 0 where nothing was observed; valid uint8 [nx,ny,nz]: count >= min_count), on the device."""
+    nx, ny, nz = _tsdf_volume(sum_, count, "tsdf_field")
+    if isinstance(min_count, bool) or int(min_count) != min_count or not 1 <= min_count < 1 << 32:
+        raise ValueError(f"tsdf_field: min_count must be an integer in [1, 2^32), got {min_count!r}")
+    field = torch.empty(nx, ny, nz, device=sum_.device, dtype=torch.float32)
+    valid = torch.empty(nx, ny, nz, device=sum_.device, dtype=torch.uint8)
+    check(load().lnr_tsdf_field(_ptr(sum_), _ptr(count), nx, ny, nz, int(min_count), _ptr(field), _ptr(valid), _stream()), "lnr_tsdf_field")
+    return field, valid
 
 
 # ---------------------------------------------------------------- scan ingestion
