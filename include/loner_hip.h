@@ -171,12 +171,15 @@ size_t lnr_density_workspace_forward(const LnrNetSpec* spec /*host*/, int64_t n_
  *   LNR_ROUTE_LDS          general fp32 kernels; w_lds (weights in LDS), waves per workgroup and - backward - dw64 (64-bit
  *                          fixed-point weight-gradient accumulators) name the tier that fits the LDS
  * f16_part: the object of the general fp16 kernels that holds the kernel (0: compile-time ReLU / Sine; run-time activations:
- * forward 1, backward 1 up to 64 neurons and 2 from 128); 0 for every other route. */
+ * forward 1, backward 1 up to 64 neurons and 2 from 128); 0 for every other route.
+ * grid, tile: the launch shape of the MLP kernels - workgroups (of four waves on every route but LNR_ROUTE_LDS, which has `waves`) and
+ * samples a wave takes per step of its loop (32 or 16); wave w of workgroup b runs tiles b * waves + w, + grid * waves, ...  Both are 0
+ * for LNR_ROUTE_UNSUPPORTED, tile is 0 for LNR_ROUTE_WIDE (it sizes its own launches). */
 typedef enum LnrRouteKind {
     LNR_ROUTE_UNSUPPORTED = 0, LNR_ROUTE_WIDE = 1, LNR_ROUTE_F16_FAST = 2, LNR_ROUTE_F16_FREQ = 3, LNR_ROUTE_F16_GEN = 4,
     LNR_ROUTE_BF3 = 5, LNR_ROUTE_FAST32 = 6, LNR_ROUTE_REGS = 7, LNR_ROUTE_LDS = 8
 } LnrRouteKind;
-typedef struct LnrDensityRoute { int32_t kind, w_lds, waves, dw64, f16_part; } LnrDensityRoute;
+typedef struct LnrDensityRoute { int32_t kind, w_lds, waves, dw64, f16_part, grid, tile; } LnrDensityRoute;
 int lnr_density_route(const LnrNetSpec* spec /*host*/, int64_t n_points, int32_t backward, LnrDensityRoute* out /*host*/);
 
 /* The first LNR_WORKSPACE_STATUS_BYTES of a workspace are int32 status words the kernels write and the caller may read (with

@@ -575,6 +575,7 @@ static DensityRoute lnr_route(const LnrNetSpec* spec, int64_t n_points, bool bac
     r.waves = 4;
     const bool f16 = spec->precision == LNR_PREC_F16;
     const int64_t max_blocks = backward ? LNR_BWD_MAX_BLOCKS : LNR_DENSITY_MAX_BLOCKS;
+    auto blocks = [&](int tile, int waves, int64_t cap) { r.tile = tile; return mlp_blocks(n_points, tile, waves, cap); };
     auto done = [&](int kind, int grid) {
         if (f16 && kind >= LNR_ROUTE_BF3) return DensityRoute{};          // an fp16 network the fp16 kernels do not cover: unsupported, no fall-back to fp32
         r.kind = kind; r.grid = grid;
@@ -587,12 +588,12 @@ static DensityRoute lnr_route(const LnrNetSpec* spec, int64_t n_points, bool bac
         return done(LNR_ROUTE_WIDE, 1);
     }
     if (f16 && lnr_f16_supported(spec)) {          // 32-sample tiles
-        if (lnr_f16_fast_class(spec)) return done(LNR_ROUTE_F16_FAST, mlp_blocks(n_points, 32, 4, max_blocks));
+        if (lnr_f16_fast_class(spec)) return done(LNR_ROUTE_F16_FAST, blocks(32, 4, max_blocks));
         const bool compile_time_act = spec->activation == LNR_ACT_RELU || spec->activation == LNR_ACT_SINE;
         r.f16_part = compile_time_act ? 0 : (backward && spec->n_neurons > 64 ? 2 : 1);
         r.fused_enc = lnr_f16_fused_freq(spec);
         // backward: one workgroup per CU (LDS), persistent over the steps
-        return done(r.fused_enc ? LNR_ROUTE_F16_FREQ : LNR_ROUTE_F16_GEN, mlp_blocks(n_points, 32, 4, backward ? 256 : max_blocks));
+        return done(r.fused_enc ? LNR_ROUTE_F16_FREQ : LNR_ROUTE_F16_GEN, blocks(32, 4, backward ? 256 : max_blocks));
     }
     // (the register-resident kernels address up to 32 padded planes with 32-bit byte offsets: m_pad < 2^25, see lnr_bf3_class)
     if (spec->activation == LNR_ACT_RELU && spec->n_hidden == 1 && spec->in_dim == 32 && spec->enc_dim == 32 && spec->n_neurons <= 64 &&
@@ -600,8 +601,8 @@ static DensityRoute lnr_route(const LnrNetSpec* spec, int64_t n_points, bool bac
         r.w_lds = 1;
         r.lds = backward ? (2 * (size_t)spec->n_mlp_params + 4 * (size_t)spec->n_neurons * 20) * sizeof(float)
                          : (size_t)spec->n_mlp_params * sizeof(float);
-        if (lnr_bf3_class(spec, n_points)) return done(LNR_ROUTE_BF3, mlp_blocks(n_points, 32, 4, max_blocks));
-        return done(LNR_ROUTE_FAST32, mlp_blocks(n_points, 16, 4, max_blocks));
+        if (lnr_bf3_class(spec, n_points)) return done(LNR_ROUTE_BF3, blocks(32, 4, max_blocks));
+        return done(LNR_ROUTE_FAST32, blocks(16, 4, max_blocks));
     }
     // backward of a general network: the register-accumulating kernel (lnr_density_regs.h) for up to three hidden layers and 128 padded
     // inputs (256 neurons: one hidden layer) - four waves, their dZ / layer-input images in LDS, the weights too when they fit
@@ -614,7 +615,7 @@ static DensityRoute lnr_route(const LnrNetSpec* spec, int64_t n_points, bool bac
             const size_t hidden = (size_t)lnr_w_lds_floats(spec->n_neurons, spec->in_dim, spec->n_hidden, false) * sizeof(float);
             r.w_lds = scratch + weights <= (size_t)LNR_LDS_LIMIT ? 1 : (spec->n_hidden > 1 && scratch + hidden <= (size_t)LNR_LDS_LIMIT ? 2 : 0);
             r.lds = scratch + (r.w_lds == 1 ? weights : (r.w_lds == 2 ? hidden : 0));
-            return done(LNR_ROUTE_REGS, mlp_blocks(n_points, 16, 4, 256));            // one workgroup per CU (one wave per SIMD)
+            return done(LNR_ROUTE_REGS, blocks(16, 4, 256));            // one workgroup per CU (one wave per SIMD)
         }
     }
     // {weights in LDS, waves, 64-bit fixed-point weight-gradient accumulators}.  LDS-resident weights matter most (without
@@ -627,7 +628,7 @@ static DensityRoute lnr_route(const LnrNetSpec* spec, int64_t n_points, bool bac
         const size_t lds = backward ? bwd_lds(spec, w_lds, waves, dw64) : fwd_lds(spec, w_lds);
         if (lds > (size_t)LNR_LDS_LIMIT) continue;
         r.w_lds = w_lds; r.waves = waves; r.lds = lds; r.dw64 = backward ? dw64 : 0;
-        return done(LNR_ROUTE_LDS, mlp_blocks(n_points, 16, waves, max_blocks));
+        return done(LNR_ROUTE_LDS, blocks(16, waves, max_blocks));
     }
     DensityRoute none{};
     none.lds_misfit = 1;
@@ -652,7 +653,7 @@ extern "C" int lnr_density_route(const LnrNetSpec* spec, int64_t n_points, int32
     if (rc) return rc;
     LNR_REQUIRE(out != nullptr && n_points >= 0, "lnr_density_route: bad argument");
     const DensityRoute r = lnr_route(spec, n_points, backward != 0);
-    *out = LnrDensityRoute{r.kind, r.w_lds, r.waves, r.dw64, r.f16_part};
+    *out = LnrDensityRoute{r.kind, r.w_lds, r.waves, r.dw64, r.f16_part, r.kind == LNR_ROUTE_UNSUPPORTED ? 0 : r.grid, r.tile};
     return LNR_OK;
 }
 

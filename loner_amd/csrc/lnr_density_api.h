@@ -137,6 +137,7 @@ struct DensityRoute {
     int kind;            // LNR_ROUTE_* (include/loner_hip.h)
     int lds_misfit;      // LNR_ROUTE_UNSUPPORTED: 1 = no tier of the fp32 kernels fits the LDS, 0 = fp16 mode does not cover the shape
     int grid;            // workgroups of the MLP launch (general fp16 forward: at most; its kernels cap it at what the chip holds)
+    int tile;            // samples a wave takes per step of its loop (32 or 16; 0: the 256 x n route sizes its own launches)
     int waves;           // waves per workgroup (1, 2 or 4)
     int w_lds;           // 1: MLP matrices staged in LDS, 0: read from global memory (regs kernel also 2: all but the first layer's in LDS)
     int dw64;            // LNR_ROUTE_LDS backward: weight gradients accumulate in LDS in 64-bit fixed point (1) or fp32 (0)

@@ -64,7 +64,8 @@ ROUTE_KINDS = ("unsupported", "wide", "f16_fast", "f16_freq", "f16_gen", "bf3", 
 
 
 class DensityRoute(C.Structure):        # LnrDensityRoute
-    _fields_ = [("kind", C.c_int32), ("w_lds", C.c_int32), ("waves", C.c_int32), ("dw64", C.c_int32), ("f16_part", C.c_int32)]
+    _fields_ = [("kind", C.c_int32), ("w_lds", C.c_int32), ("waves", C.c_int32), ("dw64", C.c_int32), ("f16_part", C.c_int32),
+                ("grid", C.c_int32), ("tile", C.c_int32)]
 
 
 class LossConfig(C.Structure):

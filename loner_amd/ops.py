@@ -95,16 +95,25 @@ def density_clipped_count(device) -> int:
     return ent["clipped_before"] + int(ent["buf"][hip.STATUS_CLIPPED:hip.STATUS_CLIPPED + 1].view(torch.int32).item())
 
 
-def density_forward(spec, params, pts=None, rays=None, z=None, n_rays_dev=None, forward_only=False):
+def _sigma_out(out, shape, device):
+    if out is None:
+        return torch.empty(*shape, device=device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == tuple(shape) and out.device == device
+    return out
+
+
+def density_forward(spec, params, pts=None, rays=None, z=None, n_rays_dev=None, forward_only=False, out=None):
     """forward_only: the caller will not call density_backward(reuse_features=True) on these points - the workspace is sized
-    for the forward alone (rendering / inference: no record regions)."""
+    for the forward alone (rendering / inference: no record regions).
+    out: a contiguous float32 tensor of the result's shape to write sigma into instead of a new one (rays form: the rows from
+    *n_rays_dev on keep what they held)."""
     require_device(params, pts, rays, z)
     params = _f32c(params)
     if pts is not None:
         pts = _f32c(pts).reshape(-1, 3)
         n = pts.shape[0]
         ent, need = _workspace(spec, params.device, n, forward_only)
-        sigma = torch.empty(n, device=params.device, dtype=torch.float32)
+        sigma = _sigma_out(out, (n,), params.device)
         check(load().lnr_density_forward(C.byref(spec), _ptr(params), _ptr(pts), n, None, None, 0, 0, None,
                                          _ptr(sigma), _ptr(ent["buf"]), need, _stream()), "lnr_density_forward")
         ent["features_of"] = None if forward_only else (params.data_ptr(), pts.data_ptr(), 0, n)
@@ -112,7 +121,7 @@ def density_forward(spec, params, pts=None, rays=None, z=None, n_rays_dev=None, 
     rays, z = _f32c(rays), _f32c(z)
     n, s = z.shape
     ent, need = _workspace(spec, params.device, n * s, forward_only)
-    sigma = torch.empty(n, s, device=params.device, dtype=torch.float32)      # rows >= *n_rays_dev are never read
+    sigma = _sigma_out(out, (n, s), params.device)      # rows >= *n_rays_dev are never read
     check(load().lnr_density_forward(C.byref(spec), _ptr(params), None, 0, _ptr(rays), _ptr(z), n, s,
                                      _ptr(n_rays_dev), _ptr(sigma), _ptr(ent["buf"]), need, _stream()), "lnr_density_forward")
     ent["features_of"] = None if forward_only else (params.data_ptr(), rays.data_ptr(), z.data_ptr(), n * s)

@@ -186,6 +186,20 @@ def encode(grid, table_flat, p, dtype, d_feat=None, live=None):
     return out
 
 
+def encode_gradients_of_live(grid, table_flat, p, dtype, d_feat, live):
+    """`encode` with d_feat, evaluated on the rows of `live` (bool [n]) only, for a d_feat that is zero on all other rows: those add zeros
+    to the table gradient (which leave a sum as it is, in any dtype), count as no contribution and have a zero input gradient.
+    -> dict(tgrad, A, cnt per level [size,F]; dpts per level [n,3], zero outside `live`)"""
+    assert not bool(d_feat[~live].any())
+    r = encode(grid, table_flat, p[live], dtype, d_feat[live])
+    full = []
+    for d in r["dpts"]:
+        out = torch.zeros(p.shape[0], 3, dtype=d.dtype)
+        out[live] = d
+        full.append(out)
+    return dict(tgrad=r["tgrad"], A=r["A"], cnt=r["cnt"], dpts=full)
+
+
 def ray_sums(dpts, z):
     """d_pts [n,S,3], z [n,S] -> [n,6]: origin columns sum_s g, direction columns sum_s z g"""
     return torch.cat([dpts.sum(dim=1), (z[..., None].to(dpts.dtype) * dpts).sum(dim=1)], dim=1)
@@ -475,6 +489,13 @@ def input_magnitude(grid, table_flat, p, d_feat, live=None):
     return total if live is None else total * live.double()
 
 
+def input_magnitude_of_live(grid, table_flat, p, d_feat, live):
+    """input_magnitude for a d_feat that is zero outside the rows of `live`, evaluated on those rows only"""
+    out = torch.zeros(p.shape[0], dtype=torch.float64)
+    out[live] = input_magnitude(grid, table_flat, p[live], d_feat[live])
+    return out
+
+
 class EncodeLedger(Ledger):
     """Ledger with two more kinds of rows: blocks held to bound() + a budget, and element-wise bounds"""
 
@@ -525,3 +546,40 @@ class EncodeLedger(Ledger):
 def table_entry_limit(A, cnt, ref, record_rel):
     """A_e x record_rel + n_e x 2^-42 + 4 ulp of |ref_e|"""
     return A.double() * record_rel + cnt.double() * FIX_STEP + 4.0 * F32_EPS * ref.double().abs()
+
+
+def check_table(led, case, grid, grad, r32, r64, record_rel=RECORD_REL, scale=1.0, base=None, entries=True):
+    """grad: a kernel's whole gradient vector; its table part level by level against scale x the reference runs of `encode` (scale: a
+    power of two), on top of `base` (what the buffer held before an accumulating call: one more fp32 rounding of the sum per entry).
+    Per level one block held to bound() plus the record budget at the level's largest A_e, and every entry to table_entry_limit
+    (entries=False: not that - the entry limit holds for a d_feature that is exact, as the selector networks' and the lattices' are)."""
+    F = grid.n_features
+    n_mlp = grad.numel() - grid.n_entries * F
+    g = grad.detach().cpu()
+    for l, lv in enumerate(grid.levels):
+        kind = "x-pair" if uses_xpairs(grid, l) else ("hashed" if lv.hashed else "dense")
+        got = g[n_mlp + lv.offset * F:n_mlp + (lv.offset + lv.size) * F].reshape(lv.size, F)
+        t32, t64, A = r32["tgrad"][l].double() * scale, r64["tgrad"][l] * scale, r64["A"][l] * scale
+        limit = table_entry_limit(A, r64["cnt"][l], t64, record_rel)
+        budget = float(A.max()) * record_rel + float(r64["cnt"][l].max()) * FIX_STEP
+        if base is not None:
+            b = base[n_mlp + lv.offset * F:n_mlp + (lv.offset + lv.size) * F].reshape(lv.size, F).double()
+            t32, t64 = t32 + b, t64 + b
+            limit = limit + F32_EPS * t64.abs()
+            budget = budget + F32_EPS * float(t64.abs().max())
+        where = f"level {l} ({kind}, scale {lv.scale:.0f})"
+        led.budget_block(f"{case}: table gradient, level {l:2d} {kind}", got, t32, t64, budget, where)
+        if entries:
+            led.elements(f"{case}: table entries, level {l:2d} {kind}", got, t64, limit, where)
+
+
+def check_points(led, case, d_pts, r32, r64, mag, scale=1.0, live=None):
+    """d_pts [n,3] of a kernel against the summed per-level input gradients of the reference runs: one block, and per point
+    INPUT_ROUNDINGS x 2^-23 x `mag` (input_magnitude)"""
+    got = d_pts.detach().cpu().reshape(-1, 3)
+    p32, p64 = sum(r32["dpts"]).double() * scale, sum(r64["dpts"]) * scale
+    if live is not None:
+        got, p32, p64, mag = got[live], p32[live], p64[live], mag[live]
+    led.block(f"{case}: d_pts", got, p32, p64)
+    limit = (INPUT_ROUNDINGS * F32_EPS * mag * scale)[:, None].expand(-1, 3)
+    led.elements(f"{case}: d_pts per point", got, p64, limit)

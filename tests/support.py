@@ -27,8 +27,9 @@ def small_settings(n_rays, n_samples, voxel=32, n_test=None):
 # then fails a test instead of silently moving coverage elsewhere).  The decision lives in one place, lnr_route of
 # loner_amd/csrc/lnr_density.hip, which the launch path reads; this asks the library for it (lnr_density_route).  No GPU.
 # ---------------------------------------------------------------------------------------------------------------------------
-def density_route(enc, net, n_points, backward=True):
-    """-> dict(route=..., ...) for the tinycudann-style configs `enc`, `net` at `n_points` samples.
+def density_route(enc, net, n_points, backward=True, shape=False):
+    """-> dict(route=..., ...) for the tinycudann-style configs `enc`, `net` at `n_points` samples; shape: with the launch shape of the MLP
+    kernels as well, `grid` workgroups and `tile` samples per wave step (wave w of workgroup b runs tiles 4 b + w, + 4 grid, ...).
     routes: "wide" (256 x 2..3 layer by layer, both precisions); fp32: "bf3" / "fast32" (the default shape class), "regs" (register-
     accumulating backward, `w_lds` 1 all weights / 2 hidden matrices / 0 none in LDS), "lds" (LDS-accumulating kernels, tier `w_lds`,
     `waves`, `dw64`); fp16: "f16_fast" (the default shape class), "f16_freq" (fused frequency kernels) and "f16_gen" (features from pair
@@ -37,13 +38,14 @@ def density_route(enc, net, n_points, backward=True):
     from loner_amd import hip, ops
     r = ops.density_route(hip.make_net_spec(enc, net), n_points, backward)
     route = hip.ROUTE_KINDS[r.kind]
+    more = dict(grid=r.grid, tile=r.tile) if shape else {}
     if route in ("f16_freq", "f16_gen"):
-        return dict(route=route, obj=r.f16_part or None)
+        return dict(route=route, obj=r.f16_part or None, **more)
     if route == "regs":
-        return dict(route=route, w_lds=r.w_lds)
+        return dict(route=route, w_lds=r.w_lds, **more)
     if route == "lds":
-        return dict(route=route, w_lds=r.w_lds, waves=r.waves, dw64=r.dw64)
-    return dict(route=route)
+        return dict(route=route, w_lds=r.w_lds, waves=r.waves, dw64=r.dw64, **more)
+    return dict(route=route, **more)
 
 
 ACTIVATION_NAMES = ["None", "ReLU", "Sine", "LeakyReLU", "Exponential", "Sigmoid", "Squareplus", "Softplus", "Tanh"]   # loner_amd/hip.py

@@ -136,36 +136,11 @@ def _reference(name, which):
 
 
 def _check_table(led, case, name, grad, r32, r64, scale=1.0, base=None):
-    """grad: the kernel's whole gradient vector; its table part level by level against scale x the reference (scale: a power of two),
-    on top of `base` (what the buffer held before an accumulating call: one more fp32 rounding of the sum per entry)"""
-    grid, _ = _grid_table(name)
-    F = grid.n_features
-    n_mlp = grad.numel() - grid.n_entries * F
-    g = grad.detach().cpu()
-    for l, lv in enumerate(grid.levels):
-        kind = "x-pair" if ER.uses_xpairs(grid, l) else ("hashed" if lv.hashed else "dense")
-        got = g[n_mlp + lv.offset * F:n_mlp + (lv.offset + lv.size) * F].reshape(lv.size, F)
-        t32, t64, A = r32["tgrad"][l].double() * scale, r64["tgrad"][l] * scale, r64["A"][l] * scale
-        limit = ER.table_entry_limit(A, r64["cnt"][l], t64, _record_rel(name))
-        budget = float(A.max()) * _record_rel(name) + float(r64["cnt"][l].max()) * ER.FIX_STEP
-        if base is not None:
-            b = base[n_mlp + lv.offset * F:n_mlp + (lv.offset + lv.size) * F].reshape(lv.size, F).double()
-            t32, t64 = t32 + b, t64 + b
-            limit = limit + ER.F32_EPS * t64.abs()
-            budget = budget + ER.F32_EPS * float(t64.abs().max())
-        where = f"level {l} ({kind}, scale {lv.scale:.0f})"
-        led.budget_block(f"{case}: table gradient, level {l:2d} {kind}", got, t32, t64, budget, where)
-        led.elements(f"{case}: table entries, level {l:2d} {kind}", got, t64, limit, where)
+    """ER.check_table on the grid of `name` with its record precision"""
+    ER.check_table(led, case, _grid_table(name)[0], grad, r32, r64, _record_rel(name), scale, base)
 
 
-def _check_points(led, case, d_pts, r32, r64, mag, scale=1.0, live=None):
-    got = d_pts.detach().cpu().reshape(-1, 3)
-    p32, p64 = sum(r32["dpts"]).double() * scale, sum(r64["dpts"]) * scale
-    if live is not None:
-        got, p32, p64, mag = got[live], p32[live], p64[live], mag[live]
-    led.block(f"{case}: d_pts", got, p32, p64)
-    limit = (ER.INPUT_ROUNDINGS * ER.F32_EPS * mag * scale)[:, None].expand(-1, 3)
-    led.elements(f"{case}: d_pts per point", got, p64, limit)
+_check_points = ER.check_points
 
 
 # ------------------------------------------------------------------------------------------- a. forward, per feature

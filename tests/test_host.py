@@ -285,6 +285,14 @@ def test_library_reports_the_hand_worked_density_routes(lib_path):
     assert density_route(Hg(16), N(64, 1, "ReLU", "fp32_chain"), 1000) == dict(route="fast32")
     assert density_route(Hg(16), N(64, 1, "ReLU", "fp16"), 1000) == dict(route="f16_fast")
     assert density_route(Hg(16), N(64, 1, "Tanh"), 1000) == dict(route="regs", w_lds=1)
+    # their launch shapes: mlp_blocks = ceil(ceil(n / tile) / 4 waves), capped at 1024 workgroups forward and 512 backward.  1000 points:
+    # 32 tiles of 32 -> 8 workgroups, 63 tiles of 16 -> 16; 300 000 points: 9375 tiles of 32 -> 2344, 18 750 tiles of 16 -> 4688: capped
+    for prec, route, tile, small in (("fp32", "bf3", 32, 8), ("fp32_chain", "fast32", 16, 16), ("fp16", "f16_fast", 32, 8)):
+        for backward, cap in ((False, 1024), (True, 512)):
+            assert density_route(Hg(16), N(64, 1, "ReLU", prec), 1000, backward, shape=True) == dict(route=route, grid=small, tile=tile)
+            assert density_route(Hg(16), N(64, 1, "ReLU", prec), 300000, backward, shape=True) == dict(route=route, grid=cap, tile=tile)
+    assert density_route(F(6), N(256, 3, prec="fp16"), 1000, shape=True) == dict(route="wide", grid=1, tile=0)
+    assert density_route(Hg(10, 1), N(16, 1, prec="fp16"), 1000, shape=True) == dict(route="unsupported", grid=0, tile=0)
     # register-accumulating backward: 64 x 1 all weights in LDS (20 480 + 35 840 B); 128 x 2: scratch 81 920 + hidden 75 776 B; 128 x 3: none
     assert density_route(F(8), N(64, 1), 1000) == dict(route="regs", w_lds=1)
     assert density_route(F(8), N(128, 2), 1000) == dict(route="regs", w_lds=2)
