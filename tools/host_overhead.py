@@ -18,7 +18,7 @@ def timeit(fn, n=200):
     return (t1 - t0) / n * 1e6
 print("density_forward  host us:", round(timeit(lambda: ops.density_forward(spec, p, rays=rays, z=z)), 1))
 print("density_backward host us:", round(timeit(lambda: (ops.density_forward(spec, p, rays=rays, z=z), ops.density_backward(spec, p, ds, g, rays=rays, z=z, reuse_features=True, d_rays=dr))), 1), "(incl. forward)")
-print("workspace query  host us:", round(timeit(lambda: ops._workspace(spec, p.device, N * S)), 1))
+print("workspace query  host us:", round(timeit(lambda: ops.density._workspace(spec, p.device, N * S)), 1))
 print("torch.empty      host us:", round(timeit(lambda: torch.empty(N, S, device='cuda')), 1))
 ops.profile_enable(True)
 print("density_forward (profiling on) host us:", round(timeit(lambda: ops.density_forward(spec, p, rays=rays, z=z)), 1))
