@@ -20,30 +20,26 @@
 // The nearest-neighbour query walks Chebyshev shells of cells around the query's cell and stops when its best squared distance is
 // below a rounding-safe lower bound on every unvisited cell; queries still open after NN_MAX_SHELL shells stream every target
 // through LDS.  The walk and that exact pass are lnr_cloud_grid.h's, shared with the kNN normals and the ICP of lnr_icp.hip.
-// The scan and the sort are lnr_radix_sort.h's, shared with the scan ingestion of lnr_scan.hip.  The bound, the parameters and the key
+// The scan, the sort and its workspace layout are lnr_radix_sort.h's, shared with every tool that sorts.  The bound, the parameters and the key
 // are lnr_cloud_keys.h's, shared with the vertex clustering of lnr_mesh_filters.hip.
 #include "lnr_cloud_keys.h"
 
 namespace {
 
 // ------------------------------------------------------------------------------------------------ segments
-__device__ inline const uint64_t* sorted_keys(const CloudParams* p, const uint64_t* a, const uint64_t* b) { return (p->npasses & 1) ? b : a; }
-__device__ inline const uint32_t* sorted_idx(const CloudParams* p, const uint32_t* a, const uint32_t* b) { return (p->npasses & 1) ? b : a; }
-
-__global__ __launch_bounds__(CL_BLOCK) void segment_heads(const uint64_t* __restrict__ ka, const uint64_t* __restrict__ kb,
-                                                          const CloudParams* __restrict__ p, uint32_t n_cap, uint32_t* __restrict__ flags) {
+__global__ __launch_bounds__(CL_BLOCK) void segment_heads(SortedPairs sp, const CloudParams* __restrict__ p, uint32_t n_cap,
+                                                          uint32_t* __restrict__ flags) {
     const uint32_t i = blockIdx.x * CL_BLOCK + threadIdx.x;
     if (i >= n_cap) return;
-    const uint64_t* k = sorted_keys(p, ka, kb);
+    const uint64_t* k = sp.keys(p->npasses);
     flags[i] = (i < p->n && (i == 0 || k[i] != k[i - 1])) ? 1u : 0u;
 }
 
-__global__ __launch_bounds__(CL_BLOCK) void segment_starts(const uint64_t* __restrict__ ka, const uint64_t* __restrict__ kb,
-                                                           const CloudParams* __restrict__ p, const uint32_t* __restrict__ seg,
-                                                           uint32_t* __restrict__ starts) {
+__global__ __launch_bounds__(CL_BLOCK) void segment_starts(SortedPairs sp, const CloudParams* __restrict__ p,
+                                                           const uint32_t* __restrict__ seg, uint32_t* __restrict__ starts) {
     const uint32_t i = blockIdx.x * CL_BLOCK + threadIdx.x;
     if (i >= p->n) return;
-    const uint64_t* k = sorted_keys(p, ka, kb);
+    const uint64_t* k = sp.keys(p->npasses);
     if (i == 0 || k[i] != k[i - 1]) starts[seg[i]] = i;
 }
 
@@ -54,7 +50,7 @@ __global__ __launch_bounds__(CL_BLOCK) void voxel_average(const double* __restri
     const uint32_t s = blockIdx.x * CL_BLOCK + threadIdx.x;
     const uint32_t n_seg = p->n_seg;
     if (s >= n_seg) return;
-    const uint32_t* idx = sorted_idx(p, ia, ib);
+    const uint32_t* idx = sorted_idx(p->npasses, ia, ib);
     const uint32_t j0 = starts[s], j1 = s + 1 < n_seg ? starts[s + 1] : p->n;
     double sx = 0.0, sy = 0.0, sz = 0.0;
     for (uint32_t j = j0; j < j1; ++j) {
@@ -71,16 +67,14 @@ __global__ __launch_bounds__(CL_BLOCK) void voxel_average(const double* __restri
 
 // the grid: targets in key order with their input index (ascending within a cell: the sort is stable), one (key, first target) per
 // occupied cell, and the end sentinel
-__global__ __launch_bounds__(CL_BLOCK) void grid_fill(const double* __restrict__ pts, const uint64_t* __restrict__ ka,
-                                                      const uint64_t* __restrict__ kb, const uint32_t* __restrict__ ia,
-                                                      const uint32_t* __restrict__ ib, const CloudParams* __restrict__ p,
+__global__ __launch_bounds__(CL_BLOCK) void grid_fill(const double* __restrict__ pts, SortedPairs sp, const CloudParams* __restrict__ p,
                                                       const uint32_t* __restrict__ starts, double* __restrict__ sorted,
                                                       uint64_t* __restrict__ cell_key, uint32_t* __restrict__ cell_start,
                                                       uint32_t* __restrict__ orig) {
     const uint32_t i = blockIdx.x * CL_BLOCK + threadIdx.x;
     const uint32_t n = p->n, n_seg = p->n_seg;
     if (i < n) {
-        const uint32_t o = sorted_idx(p, ia, ib)[i];
+        const uint32_t o = sp.idx(p->npasses)[i];
         const size_t q = 3 * (size_t)o;
         orig[i] = o;
         sorted[3 * (size_t)i] = pts[q];
@@ -89,7 +83,7 @@ __global__ __launch_bounds__(CL_BLOCK) void grid_fill(const double* __restrict__
     }
     if (i < n_seg) {
         cell_start[i] = starts[i];
-        cell_key[i] = sorted_keys(p, ka, kb)[starts[i]];
+        cell_key[i] = sp.keys(p->npasses)[starts[i]];
     }
     if (i == 0) cell_start[n_seg] = n;
 }
@@ -203,27 +197,21 @@ __global__ __launch_bounds__(CL_BLOCK) void nn_brute(GridView g, const double* _
 }
 
 // ------------------------------------------------------------------------------------------------ host
+// the parameters, the bound partials, the sort over n pairs (its sums also scan the n segment flags), the flags and the run starts
 struct CloudLayout {
-    uint32_t n_cap, sort_blocks, scan_len;
-    size_t params, part, ka, kb, ia, ib, counts, flags, starts, sums, total;
+    uint32_t n_cap;
+    size_t params, part, flags, starts, total;
+    SortLayout sort;
 };
 CloudLayout cloud_layout(int64_t n) {
     CloudLayout l;
     l.n_cap = (uint32_t)n;
-    l.sort_blocks = radix_sort_blocks(n);
-    const uint64_t count_len = (uint64_t)CL_RADIX * l.sort_blocks;
-    l.scan_len = (uint32_t)(count_len > (uint64_t)n ? count_len : (uint64_t)n);
     l.params = 0;
     l.part = align256(sizeof(CloudParams));
-    l.ka = align256(l.part + 6 * sizeof(double) * CL_BOUND_BLOCKS);
-    l.kb = align256(l.ka + 8 * (size_t)n);
-    l.ia = align256(l.kb + 8 * (size_t)n);
-    l.ib = align256(l.ia + 4 * (size_t)n);
-    l.counts = align256(l.ib + 4 * (size_t)n);
-    l.flags = align256(l.counts + 4 * count_len);
+    l.sort = sort_layout(l.part + 6 * sizeof(double) * CL_BOUND_BLOCKS, n, (uint64_t)n);
+    l.flags = l.sort.end;
     l.starts = align256(l.flags + 4 * (size_t)n);
-    l.sums = align256(l.starts + 4 * ((size_t)n + 1));
-    l.total = align256(l.sums + 4 * ((size_t)scan_tiles(l.scan_len) + 1));
+    l.total = align256(l.starts + 4 * ((size_t)n + 1));
     return l;
 }
 
@@ -238,20 +226,18 @@ int sort_cloud(const char* what, const double* pts, int64_t n, const int32_t* n_
     }
     const uint32_t n_cap = l.n_cap;
     const int nbr = (int)(blocks_for(n) < CL_BOUND_BLOCKS ? blocks_for(n) : CL_BOUND_BLOCKS);
-    uint64_t *ka = (uint64_t*)(ws + l.ka), *kb = (uint64_t*)(ws + l.kb);
-    uint32_t *ia = (uint32_t*)(ws + l.ia), *ib = (uint32_t*)(ws + l.ib);
-    uint32_t* counts = (uint32_t*)(ws + l.counts);
-    uint32_t* sums = (uint32_t*)(ws + l.sums);
+    const RadixBuffers r = radix_buffers(ws, l.sort);
     hipLaunchKernelGGL(bound_partial, dim3(nbr), dim3(CL_BLOCK), 0, st, pts, n_dev, n_cap, (double*)(ws + l.part), p);
     hipLaunchKernelGGL(cloud_params, dim3(1), dim3(CL_BLOCK), 0, st, (const double*)(ws + l.part), nbr, n_dev, n_cap, mode, edge, p);
-    hipLaunchKernelGGL(cloud_keys, dim3(blocks_for(n_cap)), dim3(CL_BLOCK), 0, st, pts, p, ka, ia);
+    hipLaunchKernelGGL(cloud_keys, dim3(blocks_for(n_cap)), dim3(CL_BLOCK), 0, st, pts, p, r.ka, r.ia);
     LNR_CHECK_LAUNCH(what);
-    enqueue_radix_sort(RadixBuffers{ka, kb, ia, ib, counts, sums, l.sort_blocks}, &p->n, &p->npasses, st);
+    enqueue_radix_sort(r, &p->n, &p->npasses, st);
     LNR_CHECK_LAUNCH(what);
     uint32_t* flags = (uint32_t*)(ws + l.flags);
-    hipLaunchKernelGGL(segment_heads, dim3(blocks_for(n_cap)), dim3(CL_BLOCK), 0, st, ka, kb, p, n_cap, flags);
-    enqueue_scan(flags, n_cap, sums, &p->n_seg, nullptr, 0, st);
-    hipLaunchKernelGGL(segment_starts, dim3(blocks_for(n_cap)), dim3(CL_BLOCK), 0, st, ka, kb, p, flags, (uint32_t*)(ws + l.starts));
+    hipLaunchKernelGGL(segment_heads, dim3(blocks_for(n_cap)), dim3(CL_BLOCK), 0, st, sorted_pairs(r), p, n_cap, flags);
+    enqueue_scan(flags, n_cap, r.sums, &p->n_seg, nullptr, 0, st);
+    hipLaunchKernelGGL(segment_starts, dim3(blocks_for(n_cap)), dim3(CL_BLOCK), 0, st, sorted_pairs(r), p, flags,
+                       (uint32_t*)(ws + l.starts));
     LNR_CHECK_LAUNCH(what);
     return LNR_OK;
 }
@@ -285,7 +271,7 @@ extern "C" int lnr_lidar_scan_points(const float* depth, const float* variance, 
     uint32_t* flags = (uint32_t*)(ws + l.flags);
     const uint32_t m = (uint32_t)n_rays;
     hipLaunchKernelGGL(scan_flags, dim3(blocks_for(m)), dim3(CL_BLOCK), 0, st, depth, variance, m, scale, var_max, depth_max, flags);
-    enqueue_scan(flags, m, (uint32_t*)(ws + l.sums), (uint32_t*)n_points_dev, nullptr, 0, st);
+    enqueue_scan(flags, m, (uint32_t*)(ws + l.sort.sums), (uint32_t*)n_points_dev, nullptr, 0, st);
     hipLaunchKernelGGL(scan_emit, dim3(blocks_for(m)), dim3(CL_BLOCK), 0, st, depth, variance, ray_index, directions, n_directions, m, scale,
                        var_max, depth_max, flags, points);
     LNR_CHECK_LAUNCH("lnr_lidar_scan_points");
@@ -305,8 +291,8 @@ extern "C" int lnr_voxel_down_sample(const double* points, int64_t n_points, con
     CloudParams* p = (CloudParams*)(ws + l.params);
     if (int rc = sort_cloud("lnr_voxel_down_sample", points, n_points, n_points_dev, CL_MODE_VOXEL, voxel_size, ws, l, p, st)) return rc;
     if (n_points > 0) {
-        hipLaunchKernelGGL(voxel_average, dim3(blocks_for(n_points)), dim3(CL_BLOCK), 0, st, points, (const uint32_t*)(ws + l.ia),
-                           (const uint32_t*)(ws + l.ib), p, (const uint32_t*)(ws + l.starts), out);
+        hipLaunchKernelGGL(voxel_average, dim3(blocks_for(n_points)), dim3(CL_BLOCK), 0, st, points, (const uint32_t*)(ws + l.sort.ia),
+                           (const uint32_t*)(ws + l.sort.ib), p, (const uint32_t*)(ws + l.starts), out);
     }
     hipLaunchKernelGGL(cloud_info, dim3(1), dim3(1), 0, st, p, info_dev);
     LNR_CHECK_LAUNCH("lnr_voxel_down_sample");
@@ -342,8 +328,7 @@ extern "C" int lnr_nn_grid_build(const double* targets, int64_t n_targets, doubl
     CloudParams* p = (CloudParams*)(gb + g.params);
     if (int rc = sort_cloud("lnr_nn_grid_build", targets, n_targets, nullptr, CL_MODE_GRID, cell_edge > 0.0 ? cell_edge : 0.0, ws, l, p, st))
         return rc;
-    hipLaunchKernelGGL(grid_fill, dim3(blocks_for(n_targets + 1)), dim3(CL_BLOCK), 0, st, targets, (const uint64_t*)(ws + l.ka),
-                       (const uint64_t*)(ws + l.kb), (const uint32_t*)(ws + l.ia), (const uint32_t*)(ws + l.ib), p,
+    hipLaunchKernelGGL(grid_fill, dim3(blocks_for(n_targets + 1)), dim3(CL_BLOCK), 0, st, targets, sorted_pairs(radix_buffers(ws, l.sort)), p,
                        (const uint32_t*)(ws + l.starts), (double*)(gb + g.pts), (uint64_t*)(gb + g.cell_key), (uint32_t*)(gb + g.cell_start),
                        (uint32_t*)(gb + g.orig));
     hipLaunchKernelGGL(cloud_info, dim3(1), dim3(1), 0, st, p, info_dev);

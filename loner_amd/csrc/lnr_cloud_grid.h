@@ -10,6 +10,8 @@
 //              1e-14 of the coordinates' magnitude, which covers the rounding of both cell assignments; the caller's stop rule compares
 //              its best (or k-th best) d2 against it
 // Queries still open after NN_MAX_SHELL shells stream every target through LDS in tiles of NN_FB_TILE (nn_brute, knn_brute).
+// It is also the lowest header of the tools' family (lnr_radix_sort.h, lnr_mesh_args.h and lnr_traj.h include it), so the pieces every
+// tool may need live here and define no kernel: align256, finite3, dot3, the block sum and the block scan, the count checks.
 // Everything is internal to its translation unit (the anonymous namespace), like the kernels that use it.
 #pragma once
 #include "lnr_common.h"
@@ -77,6 +79,8 @@ __device__ inline double sq_dist(double qx, double qy, double qz, const double* 
     const double dx = qx - t[0], dy = qy - t[1], dz = qz - t[2];
     return (dx * dx + dy * dy) + dz * dz;
 }
+
+__device__ inline double dot3(const double a[3], const double b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
 
 // (d2, index) order: the lower input index wins a tie
 __device__ inline bool pair_less(double ad, uint32_t ai, double bd, uint32_t bi) { return ad < bd || (ad == bd && ai < bi); }
@@ -166,6 +170,29 @@ __device__ inline double block_sum(double v, double* lds) {   // lds: CL_BLOCK /
 #pragma unroll
     for (int w = 1; w < CL_BLOCK / 64; ++w) t = t + lds[w];
     return t;
+}
+
+// exclusive prefix of v over a 256-thread block; *total gets the block's sum.  lds: 4 words.
+__device__ inline uint32_t block_exclusive_scan(uint32_t v, uint32_t* lds, uint32_t* total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t x = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t y = __shfl_up(x, o, 64);
+        if (lane >= o) x += y;
+    }
+    if (lane == 63) lds[w] = x;
+    __syncthreads();
+    uint32_t pre = 0, tot = 0;
+#pragma unroll
+    for (int k = 0; k < CL_BLOCK / 64; ++k) {
+        const uint32_t s = lds[k];
+        pre += k < w ? s : 0u;
+        tot += s;
+    }
+    __syncthreads();
+    *total = tot;
+    return pre + x - v;
 }
 
 // ------------------------------------------------------------------------------------------------ the affine transform

@@ -54,8 +54,6 @@ __global__ __launch_bounds__(CL_BLOCK) void bound_partial(const double* __restri
     }
 }
 
-__device__ inline uint32_t bit_length(int64_t v) { return v <= 0 ? 0u : 64u - (uint32_t)__clzll((unsigned long long)v); }
-
 // one workgroup: folds the partial bounds, sets the call's parameters.  Voxel mode (open3d's VoxelDownSample): origin = min - 0.5 v,
 // the too-small test on max + 0.5 v.  Grid mode: origin = min, edge = the caller's or the default, doubled until the key fits 63 bits.
 __global__ __launch_bounds__(CL_BLOCK) void cloud_params(const double* __restrict__ part, int n_part, const int32_t* n_dev, uint32_t n_cap,

@@ -18,6 +18,7 @@
 //   trajectory a count per block of kept points, one workgroup's scan of the counts, and the emit that recomputes the (cheap) keep test
 //              and ranks its points within the block by ballots: input order is kept without a sort
 #include "lnr_cloud_knn.h"
+#include "lnr_traj.h"
 
 namespace {
 
@@ -117,7 +118,7 @@ __global__ __launch_bounds__(CL_BLOCK) void mesh_areas(const double* __restrict_
     const int64_t i0 = tri[3 * (size_t)t], i1 = tri[3 * (size_t)t + 1], i2 = tri[3 * (size_t)t + 2];
     double a = 0.0;
     uint32_t st = 0;
-    if (i0 < 0 || i0 >= n_verts || i1 < 0 || i1 >= n_verts || i2 < 0 || i2 >= n_verts) {
+    if (i0 < 0 || i0 >= n_verts || i1 < 0 || i1 >= n_verts || i2 < 0 || i2 >= n_verts) {      // (own test: lnr_mesh_args.h's cost 2 VGPRs)
         st = MS_ST_BAD_INDEX;
     } else {
         const double *p0 = v + 3 * (size_t)i0, *p1 = v + 3 * (size_t)i1, *p2 = v + 3 * (size_t)i2;
@@ -297,14 +298,6 @@ __global__ __launch_bounds__(CL_BLOCK) void outlier_fold(const double* __restric
 // ------------------------------------------------------------------------------------------------ trajectory transform
 enum { TJ_KEEP = 0, TJ_NONFINITE = 1, TJ_BELOW = 2, TJ_OUTSIDE = 3 };
 
-struct TrajView {
-    const double* __restrict__ T;       // [K] times
-    const double* __restrict__ P;       // [K,3] positions
-    const double* __restrict__ R;       // [K,9] rotations, row-major
-    const double* __restrict__ W;       // [K-1,3] log(R_k^T R_k+1)
-    uint32_t K;
-};
-
 __device__ inline int traj_class(const double* __restrict__ pts, const double* __restrict__ stamps, uint32_t i, const TrajView& tv,
                                  double min_range) {
     const double x = pts[3 * (size_t)i], y = pts[3 * (size_t)i + 1], z = pts[3 * (size_t)i + 2], tau = stamps[i];
@@ -340,28 +333,13 @@ __global__ __launch_bounds__(CL_BLOCK) void traj_count(const double* __restrict_
 // one workgroup: count becomes its exclusive prefix, 256 blocks at a time with a running carry; then the outcome
 __global__ __launch_bounds__(CL_BLOCK) void traj_scan(uint32_t* __restrict__ count, uint32_t n_blocks, const unsigned long long* __restrict__ tally,
                                                       int64_t* __restrict__ info) {
-    __shared__ uint32_t wave_tot[CL_BLOCK / 64];
-    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    __shared__ uint32_t lds[CL_BLOCK / 64];
     uint32_t carry = 0;
     for (uint32_t base = 0; base < n_blocks; base += CL_BLOCK) {
         const uint32_t b = base + threadIdx.x;
-        const uint32_t v = b < n_blocks ? count[b] : 0u;
-        uint32_t inc = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t t = __shfl_up(inc, o, 64);
-            if ((int)lane >= o) inc += t;
-        }
-        __syncthreads();
-        if (lane == 63) wave_tot[w] = inc;
-        __syncthreads();
-        uint32_t before = 0, all = 0;
-#pragma unroll
-        for (uint32_t u = 0; u < CL_BLOCK / 64; ++u) {
-            before += u < w ? wave_tot[u] : 0u;
-            all += wave_tot[u];
-        }
-        if (b < n_blocks) count[b] = carry + before + (inc - v);
+        uint32_t all;
+        const uint32_t before = block_exclusive_scan(b < n_blocks ? count[b] : 0u, lds, &all);
+        if (b < n_blocks) count[b] = carry + before;
         carry += all;
     }
     if (threadIdx.x == 0) {
@@ -374,39 +352,17 @@ __global__ __launch_bounds__(CL_BLOCK) void traj_scan(uint32_t* __restrict__ cou
     }
 }
 
-// the pose at tau applied to one point (include/loner_hip.h states every rounding)
+__device__ inline void libm_sincos(double theta, double* s, double* c) {
+    *s = sin(theta);
+    *c = cos(theta);
+}
+
+// the pose at tau (lnr_traj.h, with the library's sine) applied to one point
 __device__ inline void traj_apply(const TrajView& tv, double x, double y, double z, double tau, double* __restrict__ out) {
-    uint32_t lo = 0, hi = tv.K;                                 // the first knot above tau
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (tv.T[mid] <= tau) lo = mid + 1; else hi = mid;
-    }
-    const uint32_t k = lo - 1 < tv.K - 2 ? lo - 1 : tv.K - 2;   // T_0 <= tau: lo >= 1
-    const double alpha = (tau - tv.T[k]) / (tv.T[k + 1] - tv.T[k]);
-    const double *Pk = tv.P + 3 * (size_t)k, *Rk = tv.R + 9 * (size_t)k, *Wk = tv.W + 3 * (size_t)k;
-    const double wx = alpha * Wk[0], wy = alpha * Wk[1], wz = alpha * Wk[2];
-    const double theta = sqrt((wx * wx + wy * wy) + wz * wz);
-    double R[9];
-    if (theta < 1e-9) {
+    double R[9], trans[3];
+    traj_pose<libm_sincos>(tv, tau, R, trans);
 #pragma unroll
-        for (int e = 0; e < 9; ++e) R[e] = Rk[e];
-    } else {
-        const double ax = wx / theta, ay = wy / theta, az = wz / theta;
-        const double s = sin(theta), v = 1.0 - cos(theta);
-        // Rodrigues: I + s K + v K^2, as lnr_motion_compensate writes it
-        const double E[9] = {1.0 - v * (ay * ay + az * az), v * ax * ay - s * az, v * ax * az + s * ay,
-                             v * ax * ay + s * az, 1.0 - v * (ax * ax + az * az), v * ay * az - s * ax,
-                             v * ax * az - s * ay, v * ay * az + s * ax, 1.0 - v * (ax * ax + ay * ay)};
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int b = 0; b < 3; ++b) R[3 * a + b] = (Rk[3 * a] * E[b] + Rk[3 * a + 1] * E[3 + b]) + Rk[3 * a + 2] * E[6 + b];
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double trans = Pk[a] + alpha * (Pk[3 + a] - Pk[a]);
-        out[a] = ((R[3 * a] * x + R[3 * a + 1] * y) + R[3 * a + 2] * z) + trans;
-    }
+    for (int a = 0; a < 3; ++a) out[a] = ((R[3 * a] * x + R[3 * a + 1] * y) + R[3 * a + 2] * z) + trans[a];
 }
 
 // kept point i of block b goes to out[count[b] + (kept points of the block before i)]
@@ -428,9 +384,9 @@ __global__ __launch_bounds__(CL_BLOCK) void traj_emit(const double* __restrict__
 
 // ------------------------------------------------------------------------------------------------ host
 // one workspace for the three cloud entries: the partials or the tallies, then n words (the exact pass's list, or the block counts)
-struct ToolsLayout { size_t part, words, total; };
-ToolsLayout tools_layout(int64_t n) {
-    ToolsLayout l;
+struct CloudToolsLayout { size_t part, words, total; };
+CloudToolsLayout cloud_tools_layout(int64_t n) {
+    CloudToolsLayout l;
     l.part = 0;
     l.words = align256(sizeof(double) * OT_MAX_BLOCKS);
     l.total = align256(l.words + 4 * ((size_t)n + 1));
@@ -481,7 +437,7 @@ extern "C" int lnr_mesh_sample_points(const double* vertices, int64_t n_vertices
 
 extern "C" size_t lnr_cloud_tools_workspace(int64_t n_points) {
     if (!count_ok(n_points)) return 0;
-    return tools_layout(n_points).total;
+    return cloud_tools_layout(n_points).total;
 }
 
 extern "C" int lnr_cloud_knn_mean_distance(const void* grid, int64_t n_points, int32_t nb_neighbors, double* mean_distance,
@@ -490,7 +446,7 @@ extern "C" int lnr_cloud_knn_mean_distance(const void* grid, int64_t n_points, i
     LNR_REQUIRE(nb_neighbors >= 1 && nb_neighbors <= LNR_KNN_MAX, "lnr_cloud_knn_mean_distance: nb_neighbors must be in [1, %d], got %d",
                 LNR_KNN_MAX, (int)nb_neighbors);
     LNR_REQUIRE(grid && counters_dev && workspace && (n_points == 0 || mean_distance), "lnr_cloud_knn_mean_distance: null argument");
-    const ToolsLayout l = tools_layout(n_points);
+    const CloudToolsLayout l = cloud_tools_layout(n_points);
     LNR_REQUIRE(workspace_bytes >= l.total, "lnr_cloud_knn_mean_distance: workspace of %zu bytes, %zu needed", workspace_bytes, l.total);
     hipStream_t st = (hipStream_t)stream;
     if (int rc = clear_words(counters_dev, 4 * sizeof(int64_t), st, "lnr_cloud_knn_mean_distance", "counters")) return rc;
@@ -507,7 +463,7 @@ extern "C" int lnr_cloud_outlier_threshold(const void* grid, const double* mean_
     CL_REQUIRE_COUNT("lnr_cloud_outlier_threshold", n_points, "points");
     LNR_REQUIRE(isfinite(std_ratio), "lnr_cloud_outlier_threshold: std_ratio must be finite, got %g", std_ratio);
     LNR_REQUIRE(grid && workspace && result_dev && (n_points == 0 || mean_distance), "lnr_cloud_outlier_threshold: null argument");
-    const ToolsLayout l = tools_layout(n_points);
+    const CloudToolsLayout l = cloud_tools_layout(n_points);
     LNR_REQUIRE(workspace_bytes >= l.total, "lnr_cloud_outlier_threshold: workspace of %zu bytes, %zu needed", workspace_bytes, l.total);
     hipStream_t st = (hipStream_t)stream;
     LnrProfScope prof("cloud_outlier_threshold", st);
@@ -533,7 +489,7 @@ extern "C" int lnr_cloud_trajectory_transform(const double* points, const double
     LNR_REQUIRE(traj_times && traj_positions && traj_rotations && traj_rotvecs && workspace && info_dev &&
                     (n_points == 0 || (points && timestamps && out)),
                 "lnr_cloud_trajectory_transform: null argument");
-    const ToolsLayout l = tools_layout(n_points);
+    const CloudToolsLayout l = cloud_tools_layout(n_points);
     LNR_REQUIRE(workspace_bytes >= l.total, "lnr_cloud_trajectory_transform: workspace of %zu bytes, %zu needed", workspace_bytes, l.total);
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;

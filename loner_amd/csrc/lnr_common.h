@@ -68,6 +68,16 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+// Adds the number of lanes of the wave with `on` set to *counter: one atomic per wave, issued by lane 0, none when no lane is set.
+// Must be reached by every lane of the wave.
+__device__ __forceinline__ void wave_count_add(bool on, uint32_t* counter) {
+    const unsigned long long m = __ballot(on);
+    if (m && (threadIdx.x & 63) == 0) atomicAdd(counter, (uint32_t)__popcll(m));
+}
+__device__ __forceinline__ void wave_count_add(bool on, unsigned long long* counter) {
+    const unsigned long long m = __ballot(on);
+    if (m && (threadIdx.x & 63) == 0) atomicAdd(counter, (unsigned long long)__popcll(m));
+}
 // Sum over the 64 lanes with DPP only (quad swaps, half-row and row mirrors: plain VALU operands) plus four readlanes
 // for the rows; __shfl_xor lowers to ds_bpermute (an LDS round trip per step).  The result is wave-uniform.  Must be
 // called with all lanes active.  Association differs from wave_sum (mirror tree instead of xor butterfly).

@@ -27,8 +27,6 @@ __device__ inline void cross3(const double a[3], const double b[3], double out[3
     out[2] = a[0] * b[1] - a[1] * b[0];
 }
 
-__device__ inline double dot3(const double a[3], const double b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-
 // open3d's ComputeEigenvector0: the row cross product of largest norm, normalised
 __device__ inline void eigvec0(const double A[3][3], double e, double out[3]) {
     const double r0[3] = {A[0][0] - e, A[0][1], A[0][2]}, r1[3] = {A[0][1], A[1][1] - e, A[1][2]}, r2[3] = {A[0][2], A[1][2], A[2][2] - e};

@@ -17,68 +17,35 @@
 //              neighbour, the exclusive scan of those flags its place, and one binary search per vertex its row's start
 //   smooth     one thread per vertex walks its row; one launch per step, ping-ponging so that the last step writes the caller's array
 #include "lnr_cloud_keys.h"
+#include "lnr_mesh_head.h"
 
 namespace {
 
+// the head's words here: status MF_ST_*, n_a the kept triangles or the neighbours, n_b the degenerate triangles; npasses2 is the second
+// sort of the unique triangles
 enum { MF_ST_BAD_INDEX = 1 };
-
-// the call's words on the device, written by mf_head before anything else runs
-struct FiltersHead {
-    uint32_t n;                     // pairs the sort works on
-    int32_t npasses;                // digit passes of the (first) sort
-    int32_t npasses2;               // digit passes of the second sort (unique triangles)
-    uint32_t status;                // MF_ST_*
-    uint32_t n_a;                   // kept triangles, or neighbours
-    uint32_t n_b;                   // degenerate triangles
-};
-
-__global__ void mf_head(FiltersHead* h, uint32_t n, int32_t npasses, int32_t npasses2) {
-    h->n = n;
-    h->npasses = npasses;
-    h->npasses2 = npasses2;
-    h->status = 0;
-    h->n_a = 0;
-    h->n_b = 0;
-}
-
-__global__ void mf_info(const FiltersHead* __restrict__ h, int64_t* __restrict__ info) {
-    info[0] = h->status;
-    info[1] = h->n_a;
-    info[2] = h->n_b;
-    info[3] = 0;
-}
-
-// adds the number of lanes of the wave with `on` set to *counter, one atomic per wave
-__device__ inline void wave_count(bool on, uint32_t* counter) {
-    const unsigned long long m = __ballot(on);
-    if (on && (int)(threadIdx.x & 63) == __ffsll((long long)m) - 1) atomicAdd(counter, (uint32_t)__popcll(m));
-}
 
 // ------------------------------------------------------------------------------------------------ vertex clusters
 // first[v] = 1 where v heads a voxel's run: the voxel's lowest vertex index
-__global__ __launch_bounds__(CL_BLOCK) void vc_first(const uint64_t* __restrict__ ka, const uint64_t* __restrict__ kb,
-                                                     const uint32_t* __restrict__ ia, const uint32_t* __restrict__ ib,
-                                                     const CloudParams* __restrict__ p, uint32_t* __restrict__ first) {
+__global__ __launch_bounds__(CL_BLOCK) void vc_first(SortedPairs sp, const CloudParams* __restrict__ p, uint32_t* __restrict__ first) {
     const uint32_t j = blockIdx.x * CL_BLOCK + threadIdx.x;
     if (j >= p->n) return;
-    const uint64_t* k = sorted_keys(p->npasses, ka, kb);
-    if (j == 0 || k[j] != k[j - 1]) first[sorted_idx(p->npasses, ia, ib)[j]] = 1u;
+    const uint64_t* k = sp.keys(p->npasses);
+    if (j == 0 || k[j] != k[j - 1]) first[sp.idx(p->npasses)[j]] = 1u;
 }
 
 // rank: the exclusive scan of first.  The thread at the head of a run: the cluster is its vertex's rank; every vertex of the run gets
 // the label, and the run is summed in its order (ascending vertex index) and divided by the count
-__global__ __launch_bounds__(CL_BLOCK) void vc_walk(const double* __restrict__ v, const uint64_t* __restrict__ ka,
-                                                    const uint64_t* __restrict__ kb, const uint32_t* __restrict__ ia,
-                                                    const uint32_t* __restrict__ ib, const CloudParams* __restrict__ p,
+__global__ __launch_bounds__(CL_BLOCK) void vc_walk(const double* __restrict__ v, SortedPairs sp, const CloudParams* __restrict__ p,
                                                     const uint32_t* __restrict__ rank, int32_t* __restrict__ vertex_cluster,
                                                     double* __restrict__ cluster_vertices) {
     const uint32_t j = blockIdx.x * CL_BLOCK + threadIdx.x;
     const uint32_t n = p->n;
     if (j >= n) return;
-    const uint64_t* k = sorted_keys(p->npasses, ka, kb);
+    const uint64_t* k = sp.keys(p->npasses);
     const uint64_t key = k[j];
     if (j > 0 && k[j - 1] == key) return;
-    const uint32_t* idx = sorted_idx(p->npasses, ia, ib);
+    const uint32_t* idx = sp.idx(p->npasses);
     const uint32_t c = rank[idx[j]];
     double sx = 0.0, sy = 0.0, sz = 0.0;
     uint32_t jj = j;
@@ -107,19 +74,19 @@ __global__ void vc_info(const CloudParams* __restrict__ p, int64_t* __restrict__
 __global__ __launch_bounds__(CL_BLOCK) void ut_keys(const int32_t* __restrict__ tri, uint32_t n_tris, int64_t n_verts,
                                                     const int32_t* __restrict__ vertex_map, int64_t n_mapped,
                                                     int32_t* __restrict__ canonical, uint64_t* __restrict__ keys,
-                                                    uint32_t* __restrict__ idx, FiltersHead* h) {
+                                                    uint32_t* __restrict__ idx, MeshSortHead* h) {
     const uint32_t t = blockIdx.x * CL_BLOCK + threadIdx.x;
     const bool active = t < n_tris;
     bool ok = false, degenerate = false;
     if (active) {
         int64_t m[3];
-        ok = true;
+        ok = load_corners(tri, t, n_verts, m);
+        if (ok) {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            m[k] = tri[3 * (size_t)t + k];
-            if (m[k] < 0 || m[k] >= n_verts) { ok = false; continue; }
-            if (vertex_map) m[k] = vertex_map[m[k]];
-            if (m[k] < 0 || m[k] >= n_mapped) ok = false;
+            for (int k = 0; k < 3; ++k) {
+                if (vertex_map) m[k] = vertex_map[m[k]];
+                if (m[k] < 0 || m[k] >= n_mapped) ok = false;
+            }
         }
         int64_t a = -1, b = -1, c = -1;
         if (ok) {
@@ -137,13 +104,13 @@ __global__ __launch_bounds__(CL_BLOCK) void ut_keys(const int32_t* __restrict__ 
         idx[t] = t;
         if (!ok) atomicOr(&h->status, (uint32_t)MF_ST_BAD_INDEX);
     }
-    wave_count(degenerate, &h->n_b);
+    wave_count_add(degenerate, &h->n_b);
 }
 
 // the second sort's input, in the first sort's order: key (a << shift | b) and the triangle, into the a buffers.  Entry j is read and
 // written by thread j only
 __global__ __launch_bounds__(CL_BLOCK) void ut_rekey(const int32_t* __restrict__ canonical, uint64_t* ka, uint32_t* ia, const uint32_t* ib,
-                                                     const FiltersHead* __restrict__ h, uint32_t shift) {
+                                                     const MeshSortHead* __restrict__ h, uint32_t shift) {
     const uint32_t j = blockIdx.x * CL_BLOCK + threadIdx.x;
     if (j >= h->n) return;
     const uint32_t t = (h->npasses & 1) ? ib[j] : ia[j];
@@ -153,13 +120,12 @@ __global__ __launch_bounds__(CL_BLOCK) void ut_rekey(const int32_t* __restrict__
 }
 
 // after both sorts equal triples are neighbours, the lowest triangle index first
-__global__ __launch_bounds__(CL_BLOCK) void ut_mark(const int32_t* __restrict__ canonical, const uint32_t* __restrict__ ia,
-                                                    const uint32_t* __restrict__ ib, FiltersHead* h, int drop_degenerate,
+__global__ __launch_bounds__(CL_BLOCK) void ut_mark(const int32_t* __restrict__ canonical, SortedPairs sp, MeshSortHead* h, int drop_degenerate,
                                                     uint8_t* __restrict__ keep) {
     const uint32_t j = blockIdx.x * CL_BLOCK + threadIdx.x;
     bool kept = false;
     if (j < h->n) {
-        const uint32_t* idx = sorted_idx(h->npasses2, ia, ib);
+        const uint32_t* idx = sp.idx(h->npasses2);
         const uint32_t t = idx[j];
         const int32_t a = canonical[3 * (size_t)t], b = canonical[3 * (size_t)t + 1], c = canonical[3 * (size_t)t + 2];
         kept = h->status == 0;
@@ -170,23 +136,18 @@ __global__ __launch_bounds__(CL_BLOCK) void ut_mark(const int32_t* __restrict__ 
         if (kept && drop_degenerate) kept = a != b && b != c && c != a;
         keep[t] = kept ? 1 : 0;
     }
-    wave_count(kept, &h->n_a);
+    wave_count_add(kept, &h->n_a);
 }
 
 // ------------------------------------------------------------------------------------------------ vertex adjacency
 // six keys per triangle: (i << shift | j) for both directions of its three edges; the key of row n_verts (past every real row) for a
 // pair (i, i) and for a triangle with a corner out of range
 __global__ __launch_bounds__(CL_BLOCK) void va_keys(const int32_t* __restrict__ tri, uint32_t n_tris, int64_t n_verts, uint32_t shift,
-                                                    uint64_t* __restrict__ keys, uint32_t* __restrict__ idx, FiltersHead* h) {
+                                                    uint64_t* __restrict__ keys, uint32_t* __restrict__ idx, MeshSortHead* h) {
     const uint32_t t = blockIdx.x * CL_BLOCK + threadIdx.x;
     if (t >= n_tris) return;
     int64_t i[3];
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        i[k] = tri[3 * (size_t)t + k];
-        ok = ok && i[k] >= 0 && i[k] < n_verts;
-    }
+    const bool ok = load_corners(tri, t, n_verts, i);
     const uint64_t none = (uint64_t)n_verts << shift;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -205,7 +166,7 @@ __device__ inline bool va_is_head(const uint64_t* keys, uint32_t j, uint64_t n_v
 }
 
 __global__ __launch_bounds__(CL_BLOCK) void va_heads(const uint64_t* __restrict__ ka, const uint64_t* __restrict__ kb,
-                                                     const FiltersHead* __restrict__ h, uint64_t n_verts, uint32_t shift,
+                                                     const MeshSortHead* __restrict__ h, uint64_t n_verts, uint32_t shift,
                                                      uint32_t* __restrict__ flags) {
     const uint32_t j = blockIdx.x * CL_BLOCK + threadIdx.x;
     if (j >= h->n) return;
@@ -214,7 +175,7 @@ __global__ __launch_bounds__(CL_BLOCK) void va_heads(const uint64_t* __restrict_
 
 // rank: the exclusive scan of the flags
 __global__ __launch_bounds__(CL_BLOCK) void va_emit(const uint64_t* __restrict__ ka, const uint64_t* __restrict__ kb,
-                                                    const FiltersHead* __restrict__ h, uint64_t n_verts, uint32_t shift,
+                                                    const MeshSortHead* __restrict__ h, uint64_t n_verts, uint32_t shift,
                                                     const uint32_t* __restrict__ rank, int32_t* __restrict__ neighbours) {
     const uint32_t j = blockIdx.x * CL_BLOCK + threadIdx.x;
     if (j >= h->n) return;
@@ -223,12 +184,11 @@ __global__ __launch_bounds__(CL_BLOCK) void va_emit(const uint64_t* __restrict__
 }
 
 // row_start[r], r in [0, n_verts]: the neighbours of lower rows = the rank at the first sorted key not below (r << shift)
-__global__ __launch_bounds__(CL_BLOCK) void va_rows(const uint64_t* __restrict__ ka, const uint64_t* __restrict__ kb,
-                                                    const FiltersHead* __restrict__ h, uint64_t n_verts, uint32_t shift,
+__global__ __launch_bounds__(CL_BLOCK) void va_rows(SortedPairs sp, const MeshSortHead* __restrict__ h, uint64_t n_verts, uint32_t shift,
                                                     const uint32_t* __restrict__ rank, int32_t* __restrict__ row_start) {
     const uint64_t r = (uint64_t)blockIdx.x * CL_BLOCK + threadIdx.x;
     if (r > n_verts) return;
-    const uint64_t* keys = sorted_keys(h->npasses, ka, kb);
+    const uint64_t* keys = sp.keys(h->npasses);
     const uint64_t k0 = r << shift;
     const uint32_t n = h->n;
     uint32_t lo = 0, hi = n;
@@ -298,50 +258,25 @@ __global__ __launch_bounds__(CL_BLOCK) void sm_step(const double* __restrict__ s
 }
 
 // ------------------------------------------------------------------------------------------------ host
-// One workspace for the three sorting entries: the voxel parameters and bound partials, the sort's buffers over max(V, 6 F) pairs, and
-// as many words.
+// One workspace for the three sorting entries: the voxel parameters, the head, the bound partials, the sort over n = max(V, 6 F) pairs
+// (its sums also scan n flags), and n words.
 struct FiltersLayout {
-    size_t params, head, part, ka, kb, ia, ib, counts, sums, words, total;
+    size_t params, head, part, words, total;
+    SortLayout sort;
 };
 FiltersLayout filters_layout(int64_t n_verts, int64_t n_tris) {
     FiltersLayout l;
-    const uint64_t n = (uint64_t)n_verts > 6 * (uint64_t)n_tris ? (uint64_t)n_verts : 6 * (uint64_t)n_tris;
-    const uint64_t count_len = (uint64_t)CL_RADIX * radix_sort_blocks((int64_t)n);
-    const uint64_t scan_len = count_len > n ? count_len : n;
+    const int64_t n = n_verts > 6 * n_tris ? n_verts : 6 * n_tris;
     l.params = 0;
     l.head = align256(sizeof(CloudParams));
-    l.part = align256(l.head + sizeof(FiltersHead));
-    l.ka = align256(l.part + 6 * sizeof(double) * CL_BOUND_BLOCKS);
-    l.kb = align256(l.ka + 8 * n);
-    l.ia = align256(l.kb + 8 * n);
-    l.ib = align256(l.ia + 4 * n);
-    l.counts = align256(l.ib + 4 * n);
-    l.sums = align256(l.counts + 4 * count_len);
-    l.words = align256(l.sums + 4 * ((size_t)scan_tiles(scan_len) + 1));
-    l.total = align256(l.words + 4 * n);
+    l.part = align256(l.head + sizeof(MeshSortHead));
+    l.sort = sort_layout(l.part + 6 * sizeof(double) * CL_BOUND_BLOCKS, n, (uint64_t)n);
+    l.words = l.sort.end;
+    l.total = align256(l.words + 4 * (size_t)n);
     return l;
 }
 
-const int64_t MF_MAX_TRIANGLES = CL_MAX_POINTS / 6;
-
-bool filters_counts_ok(int64_t n_verts, int64_t n_tris) {
-    return n_verts >= 0 && n_verts <= INT32_MAX && n_tris >= 0 && n_tris <= MF_MAX_TRIANGLES;
-}
-
-int bits_for(uint64_t x) {
-    int b = 0;
-    while (x) { ++b; x >>= 1; }
-    return b;
-}
-
-RadixBuffers filters_radix(char* ws, const FiltersLayout& l, int64_t n) {
-    return RadixBuffers{(uint64_t*)(ws + l.ka), (uint64_t*)(ws + l.kb), (uint32_t*)(ws + l.ia), (uint32_t*)(ws + l.ib),
-                        (uint32_t*)(ws + l.counts), (uint32_t*)(ws + l.sums), radix_sort_blocks(n)};
-}
-
-#define MF_REQUIRE_COUNTS(fn, v, f)                                                                                                  \
-    LNR_REQUIRE(filters_counts_ok(v, f), fn ": %lld vertices, %lld triangles, the limits are %d and %lld", (long long)(v), (long long)(f), \
-                INT32_MAX, (long long)MF_MAX_TRIANGLES)
+const int64_t MF_MAX_TRIANGLES = CL_MAX_POINTS / 6;     // six pairs per triangle (adjacency)
 
 }  // namespace
 
@@ -369,7 +304,7 @@ extern "C" int lnr_mesh_vertex_clusters(const double* vertices, int64_t n_vertic
         hipLaunchKernelGGL(cloud_params, dim3(1), dim3(CL_BLOCK), 0, st, (const double*)(ws + l.part), 0, (const int32_t*)nullptr, 0u,
                            (int)CL_MODE_VOXEL, voxel_size, p);
     } else {
-        const RadixBuffers r = filters_radix(ws, l, V);
+        const RadixBuffers r = radix_buffers(ws, l.sort);
         uint32_t* first = (uint32_t*)(ws + l.words);
         const int nbr = (int)(blocks_for(V) < CL_BOUND_BLOCKS ? blocks_for(V) : CL_BOUND_BLOCKS);
         if (int rc = clear_words(first, 4 * (size_t)V, st, "lnr_mesh_vertex_clusters", "first-occurrence flags")) return rc;
@@ -379,12 +314,10 @@ extern "C" int lnr_mesh_vertex_clusters(const double* vertices, int64_t n_vertic
         hipLaunchKernelGGL(cloud_keys, dim3(blocks_for(V)), dim3(CL_BLOCK), 0, st, vertices, (const CloudParams*)p, r.ka, r.ia);
         LNR_CHECK_LAUNCH("lnr_mesh_vertex_clusters");
         enqueue_radix_sort(r, &p->n, &p->npasses, st);
-        hipLaunchKernelGGL(vc_first, dim3(blocks_for(V)), dim3(CL_BLOCK), 0, st, (const uint64_t*)r.ka, (const uint64_t*)r.kb,
-                           (const uint32_t*)r.ia, (const uint32_t*)r.ib, (const CloudParams*)p, first);
+        hipLaunchKernelGGL(vc_first, dim3(blocks_for(V)), dim3(CL_BLOCK), 0, st, sorted_pairs(r), (const CloudParams*)p, first);
         enqueue_scan(first, V, r.sums, &p->n_seg, nullptr, 0, st);
-        hipLaunchKernelGGL(vc_walk, dim3(blocks_for(V)), dim3(CL_BLOCK), 0, st, vertices, (const uint64_t*)r.ka, (const uint64_t*)r.kb,
-                           (const uint32_t*)r.ia, (const uint32_t*)r.ib, (const CloudParams*)p, (const uint32_t*)first, vertex_cluster,
-                           cluster_vertices);
+        hipLaunchKernelGGL(vc_walk, dim3(blocks_for(V)), dim3(CL_BLOCK), 0, st, vertices, sorted_pairs(r), (const CloudParams*)p,
+                           (const uint32_t*)first, vertex_cluster, cluster_vertices);
     }
     hipLaunchKernelGGL(vc_info, dim3(1), dim3(1), 0, st, (const CloudParams*)p, info_dev);
     LNR_CHECK_LAUNCH("lnr_mesh_vertex_clusters");
@@ -394,7 +327,7 @@ extern "C" int lnr_mesh_vertex_clusters(const double* vertices, int64_t n_vertic
 extern "C" int lnr_mesh_unique_triangles(const int32_t* triangles, int64_t n_triangles, int64_t n_vertices, const int32_t* vertex_map,
                                          int64_t n_mapped, int32_t drop_degenerate, void* workspace, size_t workspace_bytes,
                                          int32_t* canonical, uint8_t* triangle_keep, int64_t* info_dev, void* stream) {
-    MF_REQUIRE_COUNTS("lnr_mesh_unique_triangles", n_vertices, n_triangles);
+    MESH_REQUIRE_COUNTS("lnr_mesh_unique_triangles", n_vertices, n_triangles, MF_MAX_TRIANGLES);
     LNR_REQUIRE(n_mapped >= 0 && n_mapped <= INT32_MAX && (vertex_map || n_mapped == n_vertices),
                 "lnr_mesh_unique_triangles: n_mapped = %lld (0 .. 2^31 - 1; n_vertices = %lld without a map)", (long long)n_mapped,
                 (long long)n_vertices);
@@ -405,30 +338,30 @@ extern "C" int lnr_mesh_unique_triangles(const int32_t* triangles, int64_t n_tri
     hipStream_t st = (hipStream_t)stream;
     LnrProfScope prof("mesh_unique_triangles", st);
     char* ws = (char*)workspace;
-    FiltersHead* h = (FiltersHead*)(ws + l.head);
+    MeshSortHead* h = (MeshSortHead*)(ws + l.head);
     const uint32_t F = (uint32_t)n_triangles;
-    const int shift = bits_for(n_mapped > 0 ? (uint64_t)n_mapped - 1 : 0);
-    hipLaunchKernelGGL(mf_head, dim3(1), dim3(1), 0, st, h, F, (int32_t)((shift + 7) / 8), (int32_t)((2 * shift + 7) / 8));
+    const int shift = (int)bit_length(n_mapped - 1);
+    hipLaunchKernelGGL(mesh_head_init, dim3(1), dim3(1), 0, st, h, F, (int32_t)((shift + 7) / 8), (int32_t)((2 * shift + 7) / 8));
     if (F) {
-        const RadixBuffers r = filters_radix(ws, l, F);
+        const RadixBuffers r = radix_buffers(ws, l.sort, F);            // F pairs in buffers laid out for 6 F
         hipLaunchKernelGGL(ut_keys, dim3(blocks_for(F)), dim3(CL_BLOCK), 0, st, triangles, F, n_vertices, vertex_map, n_mapped, canonical,
                            r.ka, r.ia, h);
         LNR_CHECK_LAUNCH("lnr_mesh_unique_triangles");
         enqueue_radix_sort(r, &h->n, &h->npasses, st);
         hipLaunchKernelGGL(ut_rekey, dim3(blocks_for(F)), dim3(CL_BLOCK), 0, st, (const int32_t*)canonical, r.ka, r.ia, (const uint32_t*)r.ib,
-                           (const FiltersHead*)h, (uint32_t)shift);
+                           (const MeshSortHead*)h, (uint32_t)shift);
         enqueue_radix_sort(r, &h->n, &h->npasses2, st);
-        hipLaunchKernelGGL(ut_mark, dim3(blocks_for(F)), dim3(CL_BLOCK), 0, st, (const int32_t*)canonical, (const uint32_t*)r.ia,
-                           (const uint32_t*)r.ib, h, (int)drop_degenerate, triangle_keep);
+        hipLaunchKernelGGL(ut_mark, dim3(blocks_for(F)), dim3(CL_BLOCK), 0, st, (const int32_t*)canonical, sorted_pairs(r), h,
+                           (int)drop_degenerate, triangle_keep);
     }
-    hipLaunchKernelGGL(mf_info, dim3(1), dim3(1), 0, st, (const FiltersHead*)h, info_dev);
+    hipLaunchKernelGGL(mesh_head_info, dim3(1), dim3(1), 0, st, (const MeshSortHead*)h, info_dev, (int64_t)0);
     LNR_CHECK_LAUNCH("lnr_mesh_unique_triangles");
     return LNR_OK;
 }
 
 extern "C" int lnr_mesh_vertex_adjacency(const int32_t* triangles, int64_t n_triangles, int64_t n_vertices, void* workspace,
                                          size_t workspace_bytes, int32_t* row_start, int32_t* neighbours, int64_t* info_dev, void* stream) {
-    MF_REQUIRE_COUNTS("lnr_mesh_vertex_adjacency", n_vertices, n_triangles);
+    MESH_REQUIRE_COUNTS("lnr_mesh_vertex_adjacency", n_vertices, n_triangles, MF_MAX_TRIANGLES);
     LNR_REQUIRE(info_dev && workspace && row_start && (n_triangles == 0 || (triangles && neighbours)),
                 "lnr_mesh_vertex_adjacency: null argument");
     const FiltersLayout l = filters_layout(0, n_triangles);
@@ -436,26 +369,26 @@ extern "C" int lnr_mesh_vertex_adjacency(const int32_t* triangles, int64_t n_tri
     hipStream_t st = (hipStream_t)stream;
     LnrProfScope prof("mesh_vertex_adjacency", st);
     char* ws = (char*)workspace;
-    FiltersHead* h = (FiltersHead*)(ws + l.head);
+    MeshSortHead* h = (MeshSortHead*)(ws + l.head);
     const uint32_t F = (uint32_t)n_triangles, n = 6 * F;
     const uint64_t V = (uint64_t)n_vertices;
-    const int shift = bits_for(V > 0 ? V - 1 : 0);
-    const RadixBuffers r = filters_radix(ws, l, n);
+    const int shift = (int)bit_length(n_vertices - 1);
+    const RadixBuffers r = radix_buffers(ws, l.sort);
     uint32_t* rank = (uint32_t*)(ws + l.words);
-    hipLaunchKernelGGL(mf_head, dim3(1), dim3(1), 0, st, h, n, (int32_t)((bits_for(V) + shift + 7) / 8), 0);
+    hipLaunchKernelGGL(mesh_head_init, dim3(1), dim3(1), 0, st, h, n, (int32_t)(((int)bit_length(n_vertices) + shift + 7) / 8), 0);
     if (F) {
         hipLaunchKernelGGL(va_keys, dim3(blocks_for(F)), dim3(CL_BLOCK), 0, st, triangles, F, n_vertices, (uint32_t)shift, r.ka, r.ia, h);
         LNR_CHECK_LAUNCH("lnr_mesh_vertex_adjacency");
         enqueue_radix_sort(r, &h->n, &h->npasses, st);
         hipLaunchKernelGGL(va_heads, dim3(blocks_for(n)), dim3(CL_BLOCK), 0, st, (const uint64_t*)r.ka, (const uint64_t*)r.kb,
-                           (const FiltersHead*)h, V, (uint32_t)shift, rank);
+                           (const MeshSortHead*)h, V, (uint32_t)shift, rank);
         enqueue_scan(rank, n, r.sums, &h->n_a, nullptr, 0, st);
         hipLaunchKernelGGL(va_emit, dim3(blocks_for(n)), dim3(CL_BLOCK), 0, st, (const uint64_t*)r.ka, (const uint64_t*)r.kb,
-                           (const FiltersHead*)h, V, (uint32_t)shift, (const uint32_t*)rank, neighbours);
+                           (const MeshSortHead*)h, V, (uint32_t)shift, (const uint32_t*)rank, neighbours);
     }
-    hipLaunchKernelGGL(va_rows, dim3(blocks_for(V + 1)), dim3(CL_BLOCK), 0, st, (const uint64_t*)r.ka, (const uint64_t*)r.kb,
-                       (const FiltersHead*)h, V, (uint32_t)shift, (const uint32_t*)rank, row_start);
-    hipLaunchKernelGGL(mf_info, dim3(1), dim3(1), 0, st, (const FiltersHead*)h, info_dev);
+    hipLaunchKernelGGL(va_rows, dim3(blocks_for(V + 1)), dim3(CL_BLOCK), 0, st, sorted_pairs(r), (const MeshSortHead*)h, V, (uint32_t)shift,
+                       (const uint32_t*)rank, row_start);
+    hipLaunchKernelGGL(mesh_head_info, dim3(1), dim3(1), 0, st, (const MeshSortHead*)h, info_dev, (int64_t)0);
     LNR_CHECK_LAUNCH("lnr_mesh_vertex_adjacency");
     return LNR_OK;
 }

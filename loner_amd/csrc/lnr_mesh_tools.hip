@@ -16,51 +16,20 @@
 //              64-ary tree in place: level l sums 64 partials 64^l apart, left to right
 //   select     keep flags per triangle and vertex, their exclusive scans, and the emit through the vertex scan
 //   normals    keys (vertex << 2 | corner) with the triangle as payload, sorted; the thread at the head of a vertex's run walks it
-#include "lnr_radix_sort.h"
+#include "lnr_mesh_head.h"
 
 namespace {
 
+// the head's words here: status MT_ST_*, n_a a scan's total (clusters, or surviving vertices), n_b the surviving triangles
 enum { MT_ST_BAD_INDEX = 1, MT_ST_BAD_CLUSTER = 2 };
 
 #define MT_ARITY 64
 #define MT_NONE 0xFFFFFFFFu
 
-// the call's words on the device, written by mt_head before anything else runs
-struct ToolsHead {
-    uint32_t n;                     // pairs the sort works on
-    int32_t npasses;                // digit passes of the sort
-    uint32_t status;                // MT_ST_*
-    uint32_t n_a;                   // a scan's total: clusters, or surviving vertices
-    uint32_t n_b;                   // surviving triangles
-};
-
-__global__ void mt_head(ToolsHead* h, uint32_t n, int32_t npasses) {
-    h->n = n;
-    h->npasses = npasses;
-    h->status = 0;
-    h->n_a = 0;
-    h->n_b = 0;
-}
-
-__global__ void mt_info(const ToolsHead* __restrict__ h, int64_t* __restrict__ info) {
-    info[0] = h->status;
-    info[1] = h->n_a;
-    info[2] = h->n_b;
-    info[3] = h->npasses;
-}
-
-// the three corners of triangle t; false when one lies outside [0, V)
-__device__ inline bool load_corners(const int32_t* __restrict__ tri, uint32_t t, int64_t n_verts, int64_t* i) {
-    i[0] = tri[3 * (size_t)t];
-    i[1] = tri[3 * (size_t)t + 1];
-    i[2] = tri[3 * (size_t)t + 2];
-    return i[0] >= 0 && i[0] < n_verts && i[1] >= 0 && i[1] < n_verts && i[2] >= 0 && i[2] < n_verts;
-}
-
 // ------------------------------------------------------------------------------------------------ connected components
 __global__ __launch_bounds__(CL_BLOCK) void cc_keys(const int32_t* __restrict__ tri, uint32_t n_tris, int64_t n_verts, uint32_t shift,
                                                     uint64_t* __restrict__ keys, uint32_t* __restrict__ idx, uint32_t* __restrict__ parent,
-                                                    ToolsHead* h) {
+                                                    MeshSortHead* h) {
     const uint32_t t = blockIdx.x * CL_BLOCK + threadIdx.x;
     if (t >= n_tris) return;
     int64_t i[3];
@@ -103,14 +72,12 @@ __device__ inline void uf_unite(uint32_t* parent, uint32_t a, uint32_t b) {
     }
 }
 
-__global__ __launch_bounds__(CL_BLOCK) void cc_link(const uint64_t* __restrict__ ka, const uint64_t* __restrict__ kb,
-                                                    const uint32_t* __restrict__ ia, const uint32_t* __restrict__ ib,
-                                                    uint32_t* __restrict__ parent, const ToolsHead* __restrict__ h) {
+__global__ __launch_bounds__(CL_BLOCK) void cc_link(SortedPairs sp, uint32_t* __restrict__ parent, const MeshSortHead* __restrict__ h) {
     const uint64_t j = (uint64_t)blockIdx.x * CL_BLOCK + threadIdx.x;
     if (j == 0 || j >= h->n || h->status) return;
-    const uint64_t* keys = sorted_keys(h->npasses, ka, kb);
+    const uint64_t* keys = sp.keys(h->npasses);
     if (keys[j] != keys[j - 1]) return;
-    const uint32_t* idx = sorted_idx(h->npasses, ia, ib);
+    const uint32_t* idx = sp.idx(h->npasses);
     uf_unite(parent, idx[j], idx[j - 1]);
 }
 
@@ -153,7 +120,7 @@ __device__ inline double triangle_area(const double* __restrict__ v, const int64
 
 __global__ __launch_bounds__(CL_BLOCK) void ca_keys(const int32_t* __restrict__ tri, uint32_t n_tris, int64_t n_verts,
                                                     const int32_t* __restrict__ cluster, int64_t n_clusters, uint64_t* __restrict__ keys,
-                                                    uint32_t* __restrict__ idx, ToolsHead* h) {
+                                                    uint32_t* __restrict__ idx, MeshSortHead* h) {
     const uint32_t t = blockIdx.x * CL_BLOCK + threadIdx.x;
     if (t >= n_tris) return;
     int64_t i[3];
@@ -169,7 +136,7 @@ __global__ __launch_bounds__(CL_BLOCK) void ca_keys(const int32_t* __restrict__ 
 __global__ __launch_bounds__(CL_BLOCK) void ca_gather(const double* __restrict__ v, int64_t n_verts, const int32_t* __restrict__ tri,
                                                       const uint64_t* __restrict__ ka, const uint64_t* __restrict__ kb,
                                                       const uint32_t* __restrict__ ia, const uint32_t* __restrict__ ib,
-                                                      const ToolsHead* __restrict__ h, double* __restrict__ part,
+                                                      const MeshSortHead* __restrict__ h, double* __restrict__ part,
                                                       uint32_t* __restrict__ start) {
     const uint32_t j = blockIdx.x * CL_BLOCK + threadIdx.x;
     if (j >= h->n || h->status) return;
@@ -184,13 +151,12 @@ __global__ __launch_bounds__(CL_BLOCK) void ca_gather(const double* __restrict__
 // one level of the tree: the thread at run position r, r a multiple of 64 stride, sums the partials at r, r + stride, ... (at most 64,
 // within its run) left to right into part[r].  No thread of a level reads what another one writes: the targets are multiples of
 // 64 stride, the other terms are not
-__global__ __launch_bounds__(CL_BLOCK) void ca_level(const uint64_t* __restrict__ ka, const uint64_t* __restrict__ kb,
-                                                     const ToolsHead* __restrict__ h, const uint32_t* __restrict__ start,
+__global__ __launch_bounds__(CL_BLOCK) void ca_level(SortedPairs sp, const MeshSortHead* __restrict__ h, const uint32_t* __restrict__ start,
                                                      double* __restrict__ part, uint64_t stride) {
     const uint32_t j = blockIdx.x * CL_BLOCK + threadIdx.x;
     const uint32_t n = h->n;
     if (j >= n || h->status) return;
-    const uint64_t* keys = sorted_keys(h->npasses, ka, kb);
+    const uint64_t* keys = sp.keys(h->npasses);
     const uint64_t c = keys[j];
     if ((uint64_t)(j - start[c]) % (MT_ARITY * stride)) return;
     double s = part[j];
@@ -202,7 +168,7 @@ __global__ __launch_bounds__(CL_BLOCK) void ca_level(const uint64_t* __restrict_
     part[j] = s;
 }
 
-__global__ __launch_bounds__(CL_BLOCK) void ca_out(const ToolsHead* __restrict__ h, const uint32_t* __restrict__ start,
+__global__ __launch_bounds__(CL_BLOCK) void ca_out(const MeshSortHead* __restrict__ h, const uint32_t* __restrict__ start,
                                                    const double* __restrict__ part, uint32_t n_clusters, double* __restrict__ area) {
     const uint32_t c = blockIdx.x * CL_BLOCK + threadIdx.x;
     if (c >= n_clusters) return;
@@ -214,7 +180,7 @@ __global__ __launch_bounds__(CL_BLOCK) void ca_out(const ToolsHead* __restrict__
 __global__ __launch_bounds__(CL_BLOCK) void sel_triangles(const int32_t* __restrict__ tri, uint32_t n_tris, int64_t n_verts,
                                                           const uint8_t* __restrict__ tri_keep, const uint8_t* __restrict__ vert_keep,
                                                           int drop_unreferenced, uint32_t* __restrict__ tflag, uint32_t* __restrict__ vflag,
-                                                          ToolsHead* h) {
+                                                          MeshSortHead* h) {
     const uint32_t t = blockIdx.x * CL_BLOCK + threadIdx.x;
     if (t >= n_tris) return;
     int64_t i[3];
@@ -240,7 +206,7 @@ __global__ __launch_bounds__(CL_BLOCK) void sel_vertices(uint32_t n_verts, const
 
 // vrank / trank: the exclusive scans of the flags; an element survives when the next rank (or the total) is larger
 __global__ __launch_bounds__(CL_BLOCK) void sel_emit_vertices(const uint32_t* __restrict__ vrank, uint32_t n_verts,
-                                                              const ToolsHead* __restrict__ h, int32_t* __restrict__ vertex_map) {
+                                                              const MeshSortHead* __restrict__ h, int32_t* __restrict__ vertex_map) {
     const uint32_t i = blockIdx.x * CL_BLOCK + threadIdx.x;
     if (i >= n_verts) return;
     const uint32_t r = vrank[i], next = i + 1 < n_verts ? vrank[i + 1] : h->n_a;
@@ -249,7 +215,7 @@ __global__ __launch_bounds__(CL_BLOCK) void sel_emit_vertices(const uint32_t* __
 
 __global__ __launch_bounds__(CL_BLOCK) void sel_emit_triangles(const int32_t* __restrict__ tri, const uint32_t* __restrict__ trank,
                                                                uint32_t n_tris, const uint32_t* __restrict__ vrank,
-                                                               const ToolsHead* __restrict__ h, int32_t* __restrict__ out) {
+                                                               const MeshSortHead* __restrict__ h, int32_t* __restrict__ out) {
     const uint32_t t = blockIdx.x * CL_BLOCK + threadIdx.x;
     if (t >= n_tris) return;
     const uint32_t r = trank[t], next = t + 1 < n_tris ? trank[t + 1] : h->n_b;
@@ -260,7 +226,7 @@ __global__ __launch_bounds__(CL_BLOCK) void sel_emit_triangles(const int32_t* __
 
 // ------------------------------------------------------------------------------------------------ vertex normals
 __global__ __launch_bounds__(CL_BLOCK) void vn_keys(const int32_t* __restrict__ tri, uint32_t n_tris, int64_t n_verts,
-                                                    uint64_t* __restrict__ keys, uint32_t* __restrict__ idx, ToolsHead* h) {
+                                                    uint64_t* __restrict__ keys, uint32_t* __restrict__ idx, MeshSortHead* h) {
     const uint32_t t = blockIdx.x * CL_BLOCK + threadIdx.x;
     if (t >= n_tris) return;
     int64_t i[3];
@@ -276,16 +242,14 @@ __global__ __launch_bounds__(CL_BLOCK) void vn_keys(const int32_t* __restrict__ 
 // the thread at the head of vertex v's run: the face normals of the run's triangles added one after the other to 0.0, in the run's
 // order (corner slot, then triangle index), then the division by the norm
 __global__ __launch_bounds__(CL_BLOCK) void vn_walk(const double* __restrict__ v, int64_t n_verts, const int32_t* __restrict__ tri,
-                                                    const uint64_t* __restrict__ ka, const uint64_t* __restrict__ kb,
-                                                    const uint32_t* __restrict__ ia, const uint32_t* __restrict__ ib,
-                                                    const ToolsHead* __restrict__ h, double* __restrict__ normals) {
+                                                    SortedPairs sp, const MeshSortHead* __restrict__ h, double* __restrict__ normals) {
     const uint64_t j = (uint64_t)blockIdx.x * CL_BLOCK + threadIdx.x;
     const uint32_t n = h->n;
     if (j >= n || h->status) return;
-    const uint64_t* keys = sorted_keys(h->npasses, ka, kb);
+    const uint64_t* keys = sp.keys(h->npasses);
     const uint64_t vert = keys[j] >> 2;
     if (j > 0 && (keys[j - 1] >> 2) == vert) return;
-    const uint32_t* idx = sorted_idx(h->npasses, ia, ib);
+    const uint32_t* idx = sp.idx(h->npasses);
     double sx = 0.0, sy = 0.0, sz = 0.0;
     for (uint64_t jj = j; jj < n && (keys[jj] >> 2) == vert; ++jj) {
         int64_t i[3];
@@ -305,24 +269,17 @@ __global__ __launch_bounds__(CL_BLOCK) void vn_walk(const double* __restrict__ v
 }
 
 // ------------------------------------------------------------------------------------------------ host
-// One workspace for the four entries: the sort's buffers over 3 F pairs, three arrays of F words or doubles, and V words.
+// One workspace for the four entries: the head, the sort over 3 F pairs (its sums also scan F and V flags), three arrays of F words or
+// doubles, and V words.
 struct ToolsLayout {
-    size_t head, ka, kb, ia, ib, counts, sums, wa, wb, dbl, vw, total;
+    size_t head, wa, wb, dbl, vw, total;
+    SortLayout sort;
 };
 ToolsLayout tools_layout(int64_t n_verts, int64_t n_tris) {
     ToolsLayout l;
-    const uint64_t n = 3 * (uint64_t)n_tris;
-    const uint64_t count_len = (uint64_t)CL_RADIX * radix_sort_blocks((int64_t)n);
-    uint64_t scan_len = count_len > (uint64_t)n_tris ? count_len : (uint64_t)n_tris;
-    if ((uint64_t)n_verts > scan_len) scan_len = (uint64_t)n_verts;
     l.head = 0;
-    l.ka = align256(sizeof(ToolsHead));
-    l.kb = align256(l.ka + 8 * n);
-    l.ia = align256(l.kb + 8 * n);
-    l.ib = align256(l.ia + 4 * n);
-    l.counts = align256(l.ib + 4 * n);
-    l.sums = align256(l.counts + 4 * count_len);
-    l.wa = align256(l.sums + 4 * ((size_t)scan_tiles(scan_len) + 1));
+    l.sort = sort_layout(sizeof(MeshSortHead), 3 * n_tris, (uint64_t)(n_tris > n_verts ? n_tris : n_verts));
+    l.wa = l.sort.end;
     l.wb = align256(l.wa + 4 * (size_t)n_tris);
     l.dbl = align256(l.wb + 4 * (size_t)n_tris);
     l.vw = align256(l.dbl + 8 * (size_t)n_tris);
@@ -330,36 +287,19 @@ ToolsLayout tools_layout(int64_t n_verts, int64_t n_tris) {
     return l;
 }
 
-bool mesh_counts_ok(int64_t n_verts, int64_t n_tris) {
-    return n_verts >= 0 && n_verts <= INT32_MAX && n_tris >= 0 && n_tris <= CL_MAX_POINTS / 3;
-}
-
-int bit_length(uint64_t x) {
-    int b = 0;
-    while (x) { ++b; x >>= 1; }
-    return b;
-}
-
-RadixBuffers radix_buffers(char* ws, const ToolsLayout& l, int64_t n) {
-    return RadixBuffers{(uint64_t*)(ws + l.ka), (uint64_t*)(ws + l.kb), (uint32_t*)(ws + l.ia), (uint32_t*)(ws + l.ib),
-                        (uint32_t*)(ws + l.counts), (uint32_t*)(ws + l.sums), radix_sort_blocks(n)};
-}
-
-#define MT_REQUIRE_COUNTS(fn, v, f)                                                                                                  \
-    LNR_REQUIRE(mesh_counts_ok(v, f), fn ": %lld vertices, %lld triangles, the limits are %d and %lld", (long long)(v), (long long)(f), \
-                INT32_MAX, (long long)(CL_MAX_POINTS / 3))
+const int64_t MT_MAX_TRIANGLES = CL_MAX_POINTS / 3;     // three pairs per triangle
 
 }  // namespace
 
 extern "C" size_t lnr_mesh_tools_workspace(int64_t n_vertices, int64_t n_triangles) {
-    if (!mesh_counts_ok(n_vertices, n_triangles)) return 0;
+    if (!mesh_counts_ok(n_vertices, n_triangles, MT_MAX_TRIANGLES)) return 0;
     return tools_layout(n_vertices, n_triangles).total;
 }
 
 extern "C" int lnr_mesh_connected_triangles(const int32_t* triangles, int64_t n_triangles, int64_t n_vertices, void* workspace,
                                             size_t workspace_bytes, int32_t* triangle_clusters, int32_t* cluster_n_triangles,
                                             int64_t* info_dev, void* stream) {
-    MT_REQUIRE_COUNTS("lnr_mesh_connected_triangles", n_vertices, n_triangles);
+    MESH_REQUIRE_COUNTS("lnr_mesh_connected_triangles", n_vertices, n_triangles, MT_MAX_TRIANGLES);
     LNR_REQUIRE(info_dev && workspace && (n_triangles == 0 || (triangles && triangle_clusters && cluster_n_triangles)),
                 "lnr_mesh_connected_triangles: null argument");
     const ToolsLayout l = tools_layout(0, n_triangles);
@@ -367,25 +307,25 @@ extern "C" int lnr_mesh_connected_triangles(const int32_t* triangles, int64_t n_
     hipStream_t st = (hipStream_t)stream;
     LnrProfScope prof("mesh_connected_triangles", st);
     char* ws = (char*)workspace;
-    ToolsHead* h = (ToolsHead*)(ws + l.head);
+    MeshSortHead* h = (MeshSortHead*)(ws + l.head);
     const uint32_t F = (uint32_t)n_triangles, n = 3 * F;
-    const int shift = bit_length(n_vertices > 0 ? (uint64_t)n_vertices - 1 : 0);
-    hipLaunchKernelGGL(mt_head, dim3(1), dim3(1), 0, st, h, n, (int32_t)((2 * shift + 7) / 8));
+    const int shift = (int)bit_length(n_vertices - 1);
+    const int32_t npasses = (2 * shift + 7) / 8;
+    hipLaunchKernelGGL(mesh_head_init, dim3(1), dim3(1), 0, st, h, n, npasses, 0);
     if (F) {
-        const RadixBuffers r = radix_buffers(ws, l, n);
+        const RadixBuffers r = radix_buffers(ws, l.sort);
         uint32_t *parent = (uint32_t*)(ws + l.wa), *root = (uint32_t*)(ws + l.wb), *flag = (uint32_t*)(ws + l.dbl);
         if (int rc = clear_words(cluster_n_triangles, 4 * (size_t)F, st, "lnr_mesh_connected_triangles", "cluster sizes")) return rc;
         hipLaunchKernelGGL(cc_keys, dim3(blocks_for(F)), dim3(CL_BLOCK), 0, st, triangles, F, n_vertices, (uint32_t)shift, r.ka, r.ia, parent, h);
         LNR_CHECK_LAUNCH("lnr_mesh_connected_triangles");
         enqueue_radix_sort(r, &h->n, &h->npasses, st);
-        hipLaunchKernelGGL(cc_link, dim3(blocks_for(n)), dim3(CL_BLOCK), 0, st, (const uint64_t*)r.ka, (const uint64_t*)r.kb,
-                           (const uint32_t*)r.ia, (const uint32_t*)r.ib, parent, (const ToolsHead*)h);
+        hipLaunchKernelGGL(cc_link, dim3(blocks_for(n)), dim3(CL_BLOCK), 0, st, sorted_pairs(r), parent, (const MeshSortHead*)h);
         hipLaunchKernelGGL(cc_flatten, dim3(blocks_for(F)), dim3(CL_BLOCK), 0, st, parent, F, root, flag);
         enqueue_scan(flag, F, r.sums, &h->n_a, nullptr, 0, st);
         hipLaunchKernelGGL(cc_labels, dim3(blocks_for(F)), dim3(CL_BLOCK), 0, st, (const uint32_t*)root, (const uint32_t*)flag, F,
                            triangle_clusters, cluster_n_triangles);
     }
-    hipLaunchKernelGGL(mt_info, dim3(1), dim3(1), 0, st, (const ToolsHead*)h, info_dev);
+    hipLaunchKernelGGL(mesh_head_info, dim3(1), dim3(1), 0, st, (const MeshSortHead*)h, info_dev, (int64_t)npasses);
     LNR_CHECK_LAUNCH("lnr_mesh_connected_triangles");
     return LNR_OK;
 }
@@ -393,7 +333,7 @@ extern "C" int lnr_mesh_connected_triangles(const int32_t* triangles, int64_t n_
 extern "C" int lnr_mesh_cluster_area(const double* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles,
                                      const int32_t* triangle_clusters, int64_t n_clusters, void* workspace, size_t workspace_bytes,
                                      double* cluster_area, int64_t* info_dev, void* stream) {
-    MT_REQUIRE_COUNTS("lnr_mesh_cluster_area", n_vertices, n_triangles);
+    MESH_REQUIRE_COUNTS("lnr_mesh_cluster_area", n_vertices, n_triangles, MT_MAX_TRIANGLES);
     LNR_REQUIRE(n_clusters >= 0 && n_clusters <= n_triangles, "lnr_mesh_cluster_area: %lld clusters of %lld triangles", (long long)n_clusters,
                 (long long)n_triangles);
     LNR_REQUIRE(info_dev && workspace && (n_triangles == 0 || (triangles && triangle_clusters)) && (n_vertices == 0 || vertices) &&
@@ -404,11 +344,12 @@ extern "C" int lnr_mesh_cluster_area(const double* vertices, int64_t n_vertices,
     hipStream_t st = (hipStream_t)stream;
     LnrProfScope prof("mesh_cluster_area", st);
     char* ws = (char*)workspace;
-    ToolsHead* h = (ToolsHead*)(ws + l.head);
+    MeshSortHead* h = (MeshSortHead*)(ws + l.head);
     const uint32_t F = (uint32_t)n_triangles, C = (uint32_t)n_clusters;
-    hipLaunchKernelGGL(mt_head, dim3(1), dim3(1), 0, st, h, F, (int32_t)((bit_length(C > 0 ? (uint64_t)C - 1 : 0) + 7) / 8));
+    const int32_t npasses = (int32_t)((bit_length(n_clusters - 1) + 7) / 8);
+    hipLaunchKernelGGL(mesh_head_init, dim3(1), dim3(1), 0, st, h, F, npasses, 0);
     if (F && C) {
-        const RadixBuffers r = radix_buffers(ws, l, F);
+        const RadixBuffers r = radix_buffers(ws, l.sort, F);            // F pairs in buffers laid out for 3 F
         uint32_t* start = (uint32_t*)(ws + l.wa);
         double* part = (double*)(ws + l.dbl);
         if (hipMemsetAsync(start, 0xFF, 4 * (size_t)F, st) != hipSuccess) {
@@ -420,14 +361,14 @@ extern "C" int lnr_mesh_cluster_area(const double* vertices, int64_t n_vertices,
         LNR_CHECK_LAUNCH("lnr_mesh_cluster_area");
         enqueue_radix_sort(r, &h->n, &h->npasses, st);
         hipLaunchKernelGGL(ca_gather, dim3(blocks_for(F)), dim3(CL_BLOCK), 0, st, vertices, n_vertices, triangles, (const uint64_t*)r.ka,
-                           (const uint64_t*)r.kb, (const uint32_t*)r.ia, (const uint32_t*)r.ib, (const ToolsHead*)h, part, start);
+                           (const uint64_t*)r.kb, (const uint32_t*)r.ia, (const uint32_t*)r.ib, (const MeshSortHead*)h, part, start);
         for (uint64_t stride = 1; stride < F; stride *= MT_ARITY)
-            hipLaunchKernelGGL(ca_level, dim3(blocks_for(F)), dim3(CL_BLOCK), 0, st, (const uint64_t*)r.ka, (const uint64_t*)r.kb,
-                               (const ToolsHead*)h, (const uint32_t*)start, part, stride);
-        hipLaunchKernelGGL(ca_out, dim3(blocks_for(C)), dim3(CL_BLOCK), 0, st, (const ToolsHead*)h, (const uint32_t*)start,
+            hipLaunchKernelGGL(ca_level, dim3(blocks_for(F)), dim3(CL_BLOCK), 0, st, sorted_pairs(r), (const MeshSortHead*)h,
+                               (const uint32_t*)start, part, stride);
+        hipLaunchKernelGGL(ca_out, dim3(blocks_for(C)), dim3(CL_BLOCK), 0, st, (const MeshSortHead*)h, (const uint32_t*)start,
                            (const double*)part, C, cluster_area);
     }
-    hipLaunchKernelGGL(mt_info, dim3(1), dim3(1), 0, st, (const ToolsHead*)h, info_dev);
+    hipLaunchKernelGGL(mesh_head_info, dim3(1), dim3(1), 0, st, (const MeshSortHead*)h, info_dev, (int64_t)npasses);
     LNR_CHECK_LAUNCH("lnr_mesh_cluster_area");
     return LNR_OK;
 }
@@ -435,7 +376,7 @@ extern "C" int lnr_mesh_cluster_area(const double* vertices, int64_t n_vertices,
 extern "C" int lnr_mesh_select(const int32_t* triangles, int64_t n_triangles, int64_t n_vertices, const uint8_t* triangle_keep,
                                const uint8_t* vertex_keep, int32_t drop_unreferenced, void* workspace, size_t workspace_bytes,
                                int32_t* triangles_out, int32_t* vertex_map, int64_t* info_dev, void* stream) {
-    MT_REQUIRE_COUNTS("lnr_mesh_select", n_vertices, n_triangles);
+    MESH_REQUIRE_COUNTS("lnr_mesh_select", n_vertices, n_triangles, MT_MAX_TRIANGLES);
     LNR_REQUIRE(info_dev && workspace && (n_triangles == 0 || (triangles && triangles_out)) && (n_vertices == 0 || vertex_map),
                 "lnr_mesh_select: null argument");
     const ToolsLayout l = tools_layout(n_vertices, n_triangles);
@@ -443,10 +384,10 @@ extern "C" int lnr_mesh_select(const int32_t* triangles, int64_t n_triangles, in
     hipStream_t st = (hipStream_t)stream;
     LnrProfScope prof("mesh_select", st);
     char* ws = (char*)workspace;
-    ToolsHead* h = (ToolsHead*)(ws + l.head);
+    MeshSortHead* h = (MeshSortHead*)(ws + l.head);
     const uint32_t F = (uint32_t)n_triangles, V = (uint32_t)n_vertices;
-    uint32_t *tflag = (uint32_t*)(ws + l.wa), *vflag = (uint32_t*)(ws + l.vw), *sums = (uint32_t*)(ws + l.sums);
-    hipLaunchKernelGGL(mt_head, dim3(1), dim3(1), 0, st, h, 0u, 0);
+    uint32_t *tflag = (uint32_t*)(ws + l.wa), *vflag = (uint32_t*)(ws + l.vw), *sums = (uint32_t*)(ws + l.sort.sums);
+    hipLaunchKernelGGL(mesh_head_init, dim3(1), dim3(1), 0, st, h, 0u, 0, 0);
     if (V) {
         if (int rc = clear_words(vflag, 4 * (size_t)V, st, "lnr_mesh_select", "vertex flags")) return rc;
     }
@@ -456,22 +397,22 @@ extern "C" int lnr_mesh_select(const int32_t* triangles, int64_t n_triangles, in
     if (V) {
         hipLaunchKernelGGL(sel_vertices, dim3(blocks_for(V)), dim3(CL_BLOCK), 0, st, V, vertex_keep, (int)drop_unreferenced, vflag);
         enqueue_scan(vflag, V, sums, &h->n_a, nullptr, 0, st);
-        hipLaunchKernelGGL(sel_emit_vertices, dim3(blocks_for(V)), dim3(CL_BLOCK), 0, st, (const uint32_t*)vflag, V, (const ToolsHead*)h,
+        hipLaunchKernelGGL(sel_emit_vertices, dim3(blocks_for(V)), dim3(CL_BLOCK), 0, st, (const uint32_t*)vflag, V, (const MeshSortHead*)h,
                            vertex_map);
     }
     if (F) {
         enqueue_scan(tflag, F, sums, &h->n_b, nullptr, 0, st);
         hipLaunchKernelGGL(sel_emit_triangles, dim3(blocks_for(F)), dim3(CL_BLOCK), 0, st, triangles, (const uint32_t*)tflag, F,
-                           (const uint32_t*)vflag, (const ToolsHead*)h, triangles_out);
+                           (const uint32_t*)vflag, (const MeshSortHead*)h, triangles_out);
     }
-    hipLaunchKernelGGL(mt_info, dim3(1), dim3(1), 0, st, (const ToolsHead*)h, info_dev);
+    hipLaunchKernelGGL(mesh_head_info, dim3(1), dim3(1), 0, st, (const MeshSortHead*)h, info_dev, (int64_t)0);
     LNR_CHECK_LAUNCH("lnr_mesh_select");
     return LNR_OK;
 }
 
 extern "C" int lnr_mesh_vertex_normals(const double* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles,
                                        void* workspace, size_t workspace_bytes, double* normals, int64_t* info_dev, void* stream) {
-    MT_REQUIRE_COUNTS("lnr_mesh_vertex_normals", n_vertices, n_triangles);
+    MESH_REQUIRE_COUNTS("lnr_mesh_vertex_normals", n_vertices, n_triangles, MT_MAX_TRIANGLES);
     LNR_REQUIRE(info_dev && workspace && (n_triangles == 0 || triangles) && (n_vertices == 0 || (vertices && normals)),
                 "lnr_mesh_vertex_normals: null argument");
     const ToolsLayout l = tools_layout(0, n_triangles);
@@ -479,22 +420,22 @@ extern "C" int lnr_mesh_vertex_normals(const double* vertices, int64_t n_vertice
     hipStream_t st = (hipStream_t)stream;
     LnrProfScope prof("mesh_vertex_normals", st);
     char* ws = (char*)workspace;
-    ToolsHead* h = (ToolsHead*)(ws + l.head);
+    MeshSortHead* h = (MeshSortHead*)(ws + l.head);
     const uint32_t F = (uint32_t)n_triangles, n = 3 * F;
-    const int bits = bit_length(n_vertices > 0 ? (uint64_t)n_vertices - 1 : 0) + 2;
-    hipLaunchKernelGGL(mt_head, dim3(1), dim3(1), 0, st, h, n, (int32_t)((bits + 7) / 8));
+    const int32_t npasses = (int32_t)((bit_length(n_vertices - 1) + 2 + 7) / 8);
+    hipLaunchKernelGGL(mesh_head_init, dim3(1), dim3(1), 0, st, h, n, npasses, 0);
     if (n_vertices) {
         if (int rc = clear_words(normals, 24 * (size_t)n_vertices, st, "lnr_mesh_vertex_normals", "normals")) return rc;
     }
     if (F) {
-        const RadixBuffers r = radix_buffers(ws, l, n);
+        const RadixBuffers r = radix_buffers(ws, l.sort);
         hipLaunchKernelGGL(vn_keys, dim3(blocks_for(F)), dim3(CL_BLOCK), 0, st, triangles, F, n_vertices, r.ka, r.ia, h);
         LNR_CHECK_LAUNCH("lnr_mesh_vertex_normals");
         enqueue_radix_sort(r, &h->n, &h->npasses, st);
-        hipLaunchKernelGGL(vn_walk, dim3(blocks_for(n)), dim3(CL_BLOCK), 0, st, vertices, n_vertices, triangles, (const uint64_t*)r.ka,
-                           (const uint64_t*)r.kb, (const uint32_t*)r.ia, (const uint32_t*)r.ib, (const ToolsHead*)h, normals);
+        hipLaunchKernelGGL(vn_walk, dim3(blocks_for(n)), dim3(CL_BLOCK), 0, st, vertices, n_vertices, triangles, sorted_pairs(r),
+                           (const MeshSortHead*)h, normals);
     }
-    hipLaunchKernelGGL(mt_info, dim3(1), dim3(1), 0, st, (const ToolsHead*)h, info_dev);
+    hipLaunchKernelGGL(mesh_head_info, dim3(1), dim3(1), 0, st, (const MeshSortHead*)h, info_dev, (int64_t)npasses);
     LNR_CHECK_LAUNCH("lnr_mesh_vertex_normals");
     return LNR_OK;
 }

@@ -1,11 +1,15 @@
-// The device-wide stable sort of (uint64 key, uint32 payload) pairs and the exclusive scan it is built on, shared by lnr_cloud.hip
-// (voxel and grid keys) and lnr_scan.hip (time keys of a LiDAR scan).
+// The device-wide stable sort of (uint64 key, uint32 payload) pairs and the exclusive scan it is built on, shared by every tool that
+// sorts: lnr_cloud.hip (voxel and grid keys), lnr_scan.hip (time keys of a LiDAR scan), lnr_raycast.hip (Morton codes of the BVH),
+// lnr_mesh_tools.hip and lnr_mesh_filters.hip (edge, vertex, cluster and triangle keys).
 //   scan       in place over uint32 words: per-tile sums, one workgroup scans the sums, per-tile apply
 //   sort       LSD radix, 8-bit digits: count (per-block histograms), exclusive scan of the [digit][block] table, stable scatter
 //              (rank within a 256-element chunk from eight ballots per wave).  The host enqueues all CL_MAX_PASSES passes; the number
 //              of points and of passes the key needs live on the device (*n_dev, *npasses_dev), and a pass at or above *npasses_dev
 //              returns at once, so the host never waits for either.  After the call the sorted pairs are in the b buffers when
-//              *npasses_dev is odd, in the a buffers otherwise (sorted_keys / sorted_idx)
+//              *npasses_dev is odd, in the a buffers otherwise (SortedPairs::keys / ::idx, or sorted_keys / sorted_idx on separate pointers)
+//   workspace  SortLayout places the six arrays of one sort in a caller's workspace (sort_layout), radix_buffers turns the offsets into
+//              pointers, sorted_pairs is the read-only view a kernel takes to walk the result.  A caller's own layout states only what
+//              it adds around them
 // Everything is internal to its translation unit (the anonymous namespace), like the kernels that use it.
 #pragma once
 #include "lnr_cloud_grid.h"
@@ -16,29 +20,6 @@
 #define CL_MAX_PASSES 8
 
 namespace {
-
-// exclusive prefix of v over a 256-thread block; *total gets the block's sum.  lds: 4 words.
-__device__ inline uint32_t block_exclusive_scan(uint32_t v, uint32_t* lds, uint32_t* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) lds[w] = x;
-    __syncthreads();
-    uint32_t pre = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < CL_BLOCK / 64; ++k) {
-        const uint32_t s = lds[k];
-        pre += k < w ? s : 0u;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return pre + x - v;
-}
 
 // ------------------------------------------------------------------------------------------------ device-wide exclusive scan (uint32)
 // In place over a[0, L).  guard (nullable): the kernels return at once when pass >= *guard (a radix pass the key does not need).
@@ -175,6 +156,32 @@ struct RadixBuffers {
 
 uint32_t radix_sort_blocks(int64_t n) { return (uint32_t)((n + CL_SORT_TILE - 1) / CL_SORT_TILE); }
 
+// where the buffers of one sort over a capacity of n pairs lie in a workspace, from `base` up to `end`.  sums also serves the caller's
+// own scans (enqueue_scan over flags), so it is sized for the longer of the sort's count table and scan_len, the caller's longest scan
+struct SortLayout {
+    size_t ka, kb, ia, ib, counts, sums, end;
+    uint32_t sort_blocks;
+};
+SortLayout sort_layout(size_t base, int64_t n, uint64_t scan_len) {
+    SortLayout l;
+    l.sort_blocks = radix_sort_blocks(n);
+    const uint64_t count_len = (uint64_t)CL_RADIX * l.sort_blocks;
+    l.ka = align256(base);
+    l.kb = align256(l.ka + 8 * (size_t)n);
+    l.ia = align256(l.kb + 8 * (size_t)n);
+    l.ib = align256(l.ia + 4 * (size_t)n);
+    l.counts = align256(l.ib + 4 * (size_t)n);
+    l.sums = align256(l.counts + 4 * count_len);
+    l.end = align256(l.sums + 4 * ((size_t)scan_tiles(count_len > scan_len ? count_len : scan_len) + 1));
+    return l;
+}
+
+// n: the pairs this call sorts, where that is fewer than the layout's capacity (its blocks then cover n); default: the capacity
+RadixBuffers radix_buffers(char* ws, const SortLayout& l, int64_t n = -1) {
+    return RadixBuffers{(uint64_t*)(ws + l.ka), (uint64_t*)(ws + l.kb), (uint32_t*)(ws + l.ia), (uint32_t*)(ws + l.ib),
+                        (uint32_t*)(ws + l.counts), (uint32_t*)(ws + l.sums), n < 0 ? l.sort_blocks : radix_sort_blocks(n)};
+}
+
 // all CL_MAX_PASSES passes over (ka, ia), ping-ponging with (kb, ib); the caller checks the launches
 void enqueue_radix_sort(const RadixBuffers& r, const uint32_t* n_dev, const int32_t* npasses_dev, hipStream_t st) {
     for (int pass = 0; pass < CL_MAX_PASSES; ++pass) {
@@ -189,7 +196,24 @@ void enqueue_radix_sort(const RadixBuffers& r, const uint32_t* n_dev, const int3
     }
 }
 
+// the sorted side of a ping-pong pair, for the kernels that keep the buffers as separate pointer parameters: with the view below the
+// compiler indexes the argument block by the pass count (a dependent scalar load), which cost voxel_average, bvh_nodes, ca_gather,
+// va_heads and va_emit an instruction or a register (profiles/sort_plumbing_fold.txt)
 __device__ inline const uint64_t* sorted_keys(int32_t npasses, const uint64_t* a, const uint64_t* b) { return (npasses & 1) ? b : a; }
 __device__ inline const uint32_t* sorted_idx(int32_t npasses, const uint32_t* a, const uint32_t* b) { return (npasses & 1) ? b : a; }
+
+// what the other kernels that walk a sort's output take: both sides of the ping-pong, and the side the pass count on the device selects
+struct SortedPairs {
+    const uint64_t* __restrict__ ka;
+    const uint64_t* __restrict__ kb;
+    const uint32_t* __restrict__ ia;
+    const uint32_t* __restrict__ ib;
+    __device__ inline const uint64_t* keys(int32_t npasses) const { return (npasses & 1) ? kb : ka; }
+    __device__ inline const uint32_t* idx(int32_t npasses) const { return (npasses & 1) ? ib : ia; }
+};
+SortedPairs sorted_pairs(const RadixBuffers& r) { return SortedPairs{r.ka, r.kb, r.ia, r.ib}; }
+
+// bits of v (0 for v <= 0): what a key component that reaches v needs; a key of b bits sorts in (b + 7) / 8 passes
+__host__ __device__ inline uint32_t bit_length(int64_t v) { return v <= 0 ? 0u : 64u - (uint32_t)__builtin_clzll((unsigned long long)v); }
 
 }  // namespace

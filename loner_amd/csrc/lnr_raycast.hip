@@ -26,7 +26,9 @@
 //   closest    the same walk for a point: the child with the smaller bound first; a node is dropped only when a lower bound of the
 //              squared distance to its box is strictly greater than the best so far (box_bound)
 //   count      the cast's walk without a best t: every box whose padded slab meets the window is visited
+#include "lnr_mesh_args.h"
 #include "lnr_radix_sort.h"
+#include "lnr_traj.h"
 
 namespace {
 
@@ -70,20 +72,8 @@ BvhLayout bvh_layout(int64_t f) {
     return l;
 }
 
-struct BuildLayout { size_t ka, kb, ia, ib, counts, sums, total; uint32_t sort_blocks; };
-BuildLayout build_layout(int64_t f) {
-    BuildLayout l;
-    l.sort_blocks = radix_sort_blocks(f);
-    const uint64_t count_len = (uint64_t)CL_RADIX * l.sort_blocks;
-    l.ka = 0;
-    l.kb = align256(l.ka + 8 * (size_t)f);
-    l.ia = align256(l.kb + 8 * (size_t)f);
-    l.ib = align256(l.ia + 4 * (size_t)f);
-    l.counts = align256(l.ib + 4 * (size_t)f);
-    l.sums = align256(l.counts + 4 * count_len);
-    l.total = align256(l.sums + 4 * ((size_t)scan_tiles(count_len) + 1));
-    return l;
-}
+// the build's workspace is the sort over f pairs and nothing else
+SortLayout build_layout(int64_t f) { return sort_layout(0, f, 0); }
 
 // order-preserving 64-bit image of a double, and back
 __device__ inline unsigned long long dbl_image(double v) {
@@ -116,14 +106,14 @@ __global__ void bvh_head_init(BvhHead* h, uint32_t f) {
 
 // the corners of triangle t -> 0: usable (c holds the 9 coordinates), 1: a non-finite corner, 2: an index outside [0, V)
 __device__ inline int load_triangle(const double* __restrict__ v, int64_t n_verts, const int32_t* __restrict__ tri, uint32_t t, double* c) {
-    const int64_t i0 = tri[3 * (size_t)t], i1 = tri[3 * (size_t)t + 1], i2 = tri[3 * (size_t)t + 2];
-    if (!(i0 >= 0 && i0 < n_verts && i1 >= 0 && i1 < n_verts && i2 >= 0 && i2 < n_verts)) return 2;
+    int64_t i[3];
+    if (!load_corners(tri, t, n_verts, i)) return 2;
     bool fin = true;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        c[a] = v[3 * (size_t)i0 + a];
-        c[3 + a] = v[3 * (size_t)i1 + a];
-        c[6 + a] = v[3 * (size_t)i2 + a];
+        c[a] = v[3 * (size_t)i[0] + a];
+        c[3 + a] = v[3 * (size_t)i[1] + a];
+        c[6 + a] = v[3 * (size_t)i[2] + a];
         fin = fin && isfinite(c[a]) && isfinite(c[3 + a]) && isfinite(c[6 + a]);
     }
     return fin ? 0 : 1;
@@ -139,11 +129,8 @@ __global__ __launch_bounds__(CL_BLOCK) void bvh_bounds(const double* __restrict_
     const uint32_t t = blockIdx.x * CL_BLOCK + threadIdx.x;
     double c[9];
     const int cls = t < f ? load_triangle(v, n_verts, tri, t, c) : -1;
-    const unsigned long long bad1 = __ballot(cls == 1), bad2 = __ballot(cls == 2);
-    if ((threadIdx.x & 63) == 0) {
-        if (bad1) atomicAdd(&h->nonfinite, (uint32_t)__popcll(bad1));
-        if (bad2) atomicAdd(&h->bad_index, (uint32_t)__popcll(bad2));
-    }
+    wave_count_add(cls == 1, &h->nonfinite);
+    wave_count_add(cls == 2, &h->bad_index);
     if (cls != 0) return;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -198,12 +185,11 @@ __global__ __launch_bounds__(CL_BLOCK) void bvh_keys(const double* __restrict__ 
 }
 
 __global__ __launch_bounds__(CL_BLOCK) void bvh_leaves(const double* __restrict__ v, int64_t n_verts, const int32_t* __restrict__ tri,
-                                                       const BvhHead* __restrict__ h, const uint32_t* __restrict__ ia,
-                                                       const uint32_t* __restrict__ ib, double* __restrict__ leaf_v,
+                                                       const BvhHead* __restrict__ h, SortedPairs sp, double* __restrict__ leaf_v,
                                                        int32_t* __restrict__ leaf_id) {
     const uint32_t j = blockIdx.x * CL_BLOCK + threadIdx.x;
     if (j >= h->n) return;
-    const uint32_t t = sorted_idx(h->npasses, ia, ib)[j];
+    const uint32_t t = sp.idx(h->npasses)[j];
     double c[9];
     load_triangle(v, n_verts, tri, t, c);               // usable: it sorted in front of the keys of all ones
 #pragma unroll
@@ -529,8 +515,6 @@ __global__ void cast_info(const BvhHead* __restrict__ h, int64_t* __restrict__ i
 }
 
 // ------------------------------------------------------------------------------------------------ closest points
-__device__ inline double dot3(const double* x, const double* y) { return (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2]; }
-
 // Ericson's region walk as include/loner_hip.h states it, on the triangle at sorted position j: the candidate replaces the best when
 // the answer rule says so
 __device__ inline void closest_leaf(const double* p, double max_d2, const double* __restrict__ leaf_v, const int32_t* __restrict__ leaf_id,
@@ -694,14 +678,6 @@ __global__ __launch_bounds__(RC_WAVE) void count_intersections_kernel(const BvhH
 }
 
 // ------------------------------------------------------------------------------------------------ trajectory rays
-struct TrajView {
-    const double* __restrict__ T;       // [K] times
-    const double* __restrict__ P;       // [K,3] positions
-    const double* __restrict__ R;       // [K,9] rotations, row-major
-    const double* __restrict__ W;       // [K-1,3] log(R_k^T R_k+1)
-    uint32_t K;
-};
-
 // sin and cos of theta >= 0 as include/loner_hip.h states them: plain fp64 operations in a fixed order, so that the numpy restatement
 // gives the same bits on any host (a library sine is good to an ulp, and which ulp differs between libraries)
 __device__ inline void stated_sincos(double theta, double* s_out, double* c_out) {
@@ -720,7 +696,7 @@ __device__ inline void stated_sincos(double theta, double* s_out, double* c_out)
     *c_out = q == 0 ? C : (q == 1 ? -S : (q == 2 ? -C : S));
 }
 
-// the pose rule of lnr_cloud_trajectory_transform, applied to a direction; the origin is the interpolated translation
+// the pose rule of lnr_traj.h with the stated sine, applied to a direction; the origin is the interpolated translation
 __global__ __launch_bounds__(CL_BLOCK) void traj_rays(const float* __restrict__ dirs, const double* __restrict__ stamps, uint32_t n, TrajView tv,
                                                       double* __restrict__ rays, unsigned long long* __restrict__ tally) {
     const uint32_t i = blockIdx.x * CL_BLOCK + threadIdx.x;
@@ -735,47 +711,16 @@ __global__ __launch_bounds__(CL_BLOCK) void traj_rays(const float* __restrict__ 
 #pragma unroll
             for (int e = 0; e < 6; ++e) out[e] = NAN;
         } else {
-            uint32_t lo = 0, hi = tv.K;                         // the first knot above tau
-            while (lo < hi) {
-                const uint32_t mid = lo + ((hi - lo) >> 1);
-                if (tv.T[mid] <= tau) lo = mid + 1; else hi = mid;
-            }
-            const uint32_t k = lo - 1 < tv.K - 2 ? lo - 1 : tv.K - 2;
-            const double alpha = (tau - tv.T[k]) / (tv.T[k + 1] - tv.T[k]);
-            const double *Pk = tv.P + 3 * (size_t)k, *Rk = tv.R + 9 * (size_t)k, *Wk = tv.W + 3 * (size_t)k;
-            const double wx = alpha * Wk[0], wy = alpha * Wk[1], wz = alpha * Wk[2];
-            const double theta = sqrt((wx * wx + wy * wy) + wz * wz);
             double R[9];
-            if (theta < 1e-9) {
+            traj_pose<stated_sincos>(tv, tau, R, out);
 #pragma unroll
-                for (int e = 0; e < 9; ++e) R[e] = Rk[e];
-            } else {
-                const double ax = wx / theta, ay = wy / theta, az = wz / theta;
-                double s, cs;
-                stated_sincos(theta, &s, &cs);
-                const double c = 1.0 - cs;
-                const double E[9] = {1.0 - c * (ay * ay + az * az), c * ax * ay - s * az, c * ax * az + s * ay,
-                                     c * ax * ay + s * az, 1.0 - c * (ax * ax + az * az), c * ay * az - s * ax,
-                                     c * ax * az - s * ay, c * ay * az + s * ax, 1.0 - c * (ax * ax + ay * ay)};
-#pragma unroll
-                for (int a = 0; a < 3; ++a)
-#pragma unroll
-                    for (int b = 0; b < 3; ++b) R[3 * a + b] = (Rk[3 * a] * E[b] + Rk[3 * a + 1] * E[3 + b]) + Rk[3 * a + 2] * E[6 + b];
-            }
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                out[a] = Pk[a] + alpha * (Pk[3 + a] - Pk[a]);
-                out[3 + a] = (R[3 * a] * x + R[3 * a + 1] * y) + R[3 * a + 2] * z;
-            }
+            for (int a = 0; a < 3; ++a) out[3 + a] = (R[3 * a] * x + R[3 * a + 1] * y) + R[3 * a + 2] * z;
         }
 #pragma unroll
         for (int e = 0; e < 6; ++e) rays[6 * (size_t)i + e] = out[e];
     }
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const unsigned long long m = __ballot(cls == c);
-        if (m && (threadIdx.x & 63) == 0) atomicAdd(&tally[c], (unsigned long long)__popcll(m));
-    }
+    for (int c = 0; c < 3; ++c) wave_count_add(cls == c, &tally[c]);
 }
 
 // tally {rays, outside, non-finite} in words 1..3 -> the stated info
@@ -784,15 +729,11 @@ __global__ void traj_rays_info(int64_t* __restrict__ info) {
     for (int e = 4; e < 8; ++e) info[e] = 0;
 }
 
-bool mesh_counts_ok(int64_t n_vertices, int64_t n_triangles) {
-    return n_vertices >= 0 && n_vertices <= INT32_MAX && count_ok(n_triangles);
-}
-
 }  // namespace
 
 extern "C" size_t lnr_bvh_workspace(int64_t n_triangles) {
     if (!count_ok(n_triangles)) return 0;
-    return build_layout(n_triangles).total;
+    return build_layout(n_triangles).end;
 }
 
 extern "C" size_t lnr_bvh_bytes(int64_t n_triangles) {
@@ -802,13 +743,14 @@ extern "C" size_t lnr_bvh_bytes(int64_t n_triangles) {
 
 extern "C" int lnr_bvh_build(const double* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles, void* workspace,
                              size_t workspace_bytes, void* bvh, size_t bvh_bytes, int64_t* info_dev, void* stream) {
-    LNR_REQUIRE(mesh_counts_ok(n_vertices, n_triangles), "lnr_bvh_build: %lld vertices and %lld triangles, the limits are %d and %lld",
-                (long long)n_vertices, (long long)n_triangles, INT32_MAX, (long long)CL_MAX_POINTS);
+    LNR_REQUIRE(mesh_counts_ok(n_vertices, n_triangles, CL_MAX_POINTS),
+                "lnr_bvh_build: %lld vertices and %lld triangles, the limits are %d and %lld", (long long)n_vertices, (long long)n_triangles,
+                INT32_MAX, (long long)CL_MAX_POINTS);
     LNR_REQUIRE(info_dev && workspace && bvh && (n_triangles == 0 || triangles) && (n_vertices == 0 || vertices),
                 "lnr_bvh_build: null argument");
-    const BuildLayout l = build_layout(n_triangles);
+    const SortLayout l = build_layout(n_triangles);
     const BvhLayout b = bvh_layout(n_triangles);
-    LNR_REQUIRE(workspace_bytes >= l.total, "lnr_bvh_build: workspace of %zu bytes, %zu needed", workspace_bytes, l.total);
+    LNR_REQUIRE(workspace_bytes >= l.end, "lnr_bvh_build: workspace of %zu bytes, %zu needed", workspace_bytes, l.end);
     LNR_REQUIRE(bvh_bytes >= b.total, "lnr_bvh_build: a BVH buffer of %zu bytes, %zu needed", bvh_bytes, b.total);
     hipStream_t st = (hipStream_t)stream;
     LnrProfScope prof("bvh_build", st);
@@ -820,16 +762,15 @@ extern "C" int lnr_bvh_build(const double* vertices, int64_t n_vertices, const i
     const uint32_t f = (uint32_t)n_triangles;
     hipLaunchKernelGGL(bvh_head_init, dim3(1), dim3(1), 0, st, h, f);
     if (f > 0) {
-        const RadixBuffers r{(uint64_t*)(ws + l.ka), (uint64_t*)(ws + l.kb), (uint32_t*)(ws + l.ia), (uint32_t*)(ws + l.ib),
-                             (uint32_t*)(ws + l.counts), (uint32_t*)(ws + l.sums), l.sort_blocks};
+        const RadixBuffers r = radix_buffers(ws, l);
         const uint32_t nb = blocks_for(f);
         hipLaunchKernelGGL(bvh_bounds, dim3(nb), dim3(CL_BLOCK), 0, st, vertices, n_vertices, triangles, f, h);
         hipLaunchKernelGGL(bvh_params, dim3(1), dim3(1), 0, st, h);
         hipLaunchKernelGGL(bvh_keys, dim3(nb), dim3(CL_BLOCK), 0, st, vertices, n_vertices, triangles, f, (const BvhHead*)h, r.ka, r.ia);
         LNR_CHECK_LAUNCH("lnr_bvh_build");
         enqueue_radix_sort(r, &h->n_sort, &h->npasses, st);
-        hipLaunchKernelGGL(bvh_leaves, dim3(nb), dim3(CL_BLOCK), 0, st, vertices, n_vertices, triangles, (const BvhHead*)h,
-                           (const uint32_t*)r.ia, (const uint32_t*)r.ib, leaf_v, leaf_id);
+        hipLaunchKernelGGL(bvh_leaves, dim3(nb), dim3(CL_BLOCK), 0, st, vertices, n_vertices, triangles, (const BvhHead*)h, sorted_pairs(r),
+                           leaf_v, leaf_id);
         hipLaunchKernelGGL(bvh_nodes, dim3(nb), dim3(CL_BLOCK), 0, st, (const BvhHead*)h, (const uint64_t*)r.ka, (const uint64_t*)r.kb, nodes);
         for (int32_t round = 1; round <= LNR_BVH_STACK; ++round)
             hipLaunchKernelGGL(bvh_fit, dim3(nb), dim3(CL_BLOCK), 0, st, h, nodes, (const double*)leaf_v, round);

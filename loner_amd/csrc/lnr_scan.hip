@@ -163,14 +163,13 @@ __global__ __launch_bounds__(CL_BLOCK) void ingest_keys(const float* __restrict_
 }
 
 __global__ __launch_bounds__(CL_BLOCK) void ingest_gather(const float* __restrict__ xyz, const float* __restrict__ tin, int mode, float stamp,
-                                                          ScanParams* __restrict__ p, const uint32_t* __restrict__ ia,
-                                                          const uint32_t* __restrict__ ib, float* __restrict__ dirs,
+                                                          ScanParams* __restrict__ p, SortedPairs sp, float* __restrict__ dirs,
                                                           float* __restrict__ dist_out, float* __restrict__ times,
                                                           int64_t* __restrict__ order) {
     const uint32_t j = blockIdx.x * CL_BLOCK + threadIdx.x;
     const uint32_t m = p->m;
     if (j >= m) return;
-    const uint32_t* idx = sorted_idx(p->npasses, ia, ib);
+    const uint32_t* idx = sp.idx(p->npasses);
     const uint32_t i = idx[j];
     const uint32_t flags = p->flags;
     const float sn = p->sub_neg, sg = p->sub_global;
@@ -200,24 +199,17 @@ __global__ void ingest_info(const ScanParams* __restrict__ p, int64_t* __restric
     info[7] = 0;
 }
 
+// the parameters, the n keep words, and the sort over n pairs (its sums also scan the keep words)
 struct ScanLayout {
-    uint32_t sort_blocks;
-    size_t params, keep, ka, kb, ia, ib, counts, sums, total;
+    size_t params, keep, total;
+    SortLayout sort;
 };
 ScanLayout scan_layout(int64_t n) {
     ScanLayout l;
-    l.sort_blocks = radix_sort_blocks(n);
-    const uint64_t count_len = (uint64_t)CL_RADIX * l.sort_blocks;
-    const uint64_t scan_len = count_len > (uint64_t)n ? count_len : (uint64_t)n;
     l.params = 0;
     l.keep = align256(sizeof(ScanParams));
-    l.ka = align256(l.keep + 4 * (size_t)n);
-    l.kb = align256(l.ka + 8 * (size_t)n);
-    l.ia = align256(l.kb + 8 * (size_t)n);
-    l.ib = align256(l.ia + 4 * (size_t)n);
-    l.counts = align256(l.ib + 4 * (size_t)n);
-    l.sums = align256(l.counts + 4 * count_len);
-    l.total = align256(l.sums + 4 * ((size_t)scan_tiles(scan_len) + 1));
+    l.sort = sort_layout(l.keep + 4 * (size_t)n, n, (uint64_t)n);
+    l.total = l.sort.end;
     return l;
 }
 
@@ -259,18 +251,16 @@ extern "C" int lnr_scan_from_points(const float* xyz, const float* point_times, 
     if (n_points > 0) {
         const uint32_t n = (uint32_t)n_points;
         uint32_t* keep = (uint32_t*)(ws + l.keep);
-        uint32_t* sums = (uint32_t*)(ws + l.sums);
-        const RadixBuffers r{(uint64_t*)(ws + l.ka), (uint64_t*)(ws + l.kb), (uint32_t*)(ws + l.ia), (uint32_t*)(ws + l.ib),
-                             (uint32_t*)(ws + l.counts), sums, l.sort_blocks};
+        const RadixBuffers r = radix_buffers(ws, l.sort);
         hipLaunchKernelGGL(ingest_flag, dim3(blocks_for(n)), dim3(CL_BLOCK), 0, st, xyz, point_times, n, (int)time_mode, fov, min_range, keep, p);
-        enqueue_scan(keep, n, sums, &p->m, nullptr, 0, st);
+        enqueue_scan(keep, n, r.sums, &p->m, nullptr, 0, st);
         hipLaunchKernelGGL(ingest_params, dim3(1), dim3(1), 0, st, point_times, (int)time_mode, stamp, p);
         hipLaunchKernelGGL(ingest_keys, dim3(blocks_for(n)), dim3(CL_BLOCK), 0, st, point_times, (const uint32_t*)keep, n, (int)time_mode, stamp,
                            (const ScanParams*)p, r.ka, r.ia);
         LNR_CHECK_LAUNCH("lnr_scan_from_points");
         enqueue_radix_sort(r, &p->m, &p->npasses, st);
         hipLaunchKernelGGL(ingest_gather, dim3(blocks_for(n)), dim3(CL_BLOCK), 0, st, xyz, point_times, (int)time_mode, stamp, p,
-                           (const uint32_t*)r.ia, (const uint32_t*)r.ib, ray_directions, distances, timestamps, order);
+                           sorted_pairs(r), ray_directions, distances, timestamps, order);
     }
     hipLaunchKernelGGL(ingest_info, dim3(1), dim3(1), 0, st, (const ScanParams*)p, info_dev);
     LNR_CHECK_LAUNCH("lnr_scan_from_points");

@@ -30,10 +30,7 @@ struct TsdfGrid {
 // bumps tally[0..3] = {rays that updated a node, invalid rays, rays that miss the box, node updates}: one atomic per wave and word
 __device__ __forceinline__ void tsdf_tally(int cls, uint32_t updates, unsigned long long* __restrict__ tally) {
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const unsigned long long m = __ballot(cls == c);
-        if (m && (threadIdx.x & 63) == 0) atomicAdd(&tally[c], (unsigned long long)__popcll(m));
-    }
+    for (int c = 0; c < 3; ++c) wave_count_add(cls == c, &tally[c]);
     unsigned long long u = updates;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) u += __shfl_xor(u, o, 64);

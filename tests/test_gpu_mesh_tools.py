@@ -155,6 +155,8 @@ def _area_mesh(name):
         v, f = _mc_mesh()
     elif name == "random":                              # ~2500 clusters of one to a few triangles, some of zero area
         v, f = MT.random_shared_mesh()
+    elif name == "small fan":                           # 60 pairs: one sort block, the scan sums sized by the count table; one level
+        v, f = MT.fan(60)
     else:
         assert name == "fan"                            # one cluster of 10 000 > 64^2 triangles: three tree levels
         v, f = MT.fan(10000)
@@ -162,7 +164,7 @@ def _area_mesh(name):
     return v, f, labels, sizes, MT.cluster_areas_exact(v, f, labels, len(sizes)), MT.cluster_areas_tree(v, f, labels, len(sizes))
 
 
-@pytest.mark.parametrize("name", ["marching cubes", "random", "fan"])
+@pytest.mark.parametrize("name", ["marching cubes", "random", "fan", "small fan"])
 def test_cluster_areas_within_the_summation_band_and_in_the_stated_order(name):
     """|area_c - exact_c| <= n_c 2^-53 exact_c: the worst case of any order of summing n_c non-negative terms (exact_c: math.fsum of
     the restated triangle areas).  Beyond the band, the bits are those of the header's 64-ary order, and of a second run."""
@@ -230,11 +232,12 @@ def test_select_on_empty_inputs():
 
 
 # ---------------------------------------------------------------- vertex normals
-@pytest.mark.parametrize("name", ["random", "marching cubes", "fan"])
+@pytest.mark.parametrize("name", ["random", "marching cubes", "fan", "small fan"])
 def test_vertex_normals_are_the_bytes_of_the_numpy_route(name):
     from loner_amd import ops
     from loner_amd.analysis.mesher import TriangleMesh
-    v, f = {"random": MT.random_shared_mesh, "marching cubes": _mc_mesh, "fan": lambda: MT.fan(10000)}[name]()
+    v, f = {"random": MT.random_shared_mesh, "marching cubes": _mc_mesh, "fan": lambda: MT.fan(10000),
+            "small fan": lambda: MT.fan(60)}[name]()                # 180 pairs: one sort block
     want = TriangleMesh(v, f).compute_vertex_normals().vertex_normals
     got = ops.mesh_vertex_normals(_t(v), _tris(f)).cpu().numpy()
     differ = (got.view(np.uint64) != want.view(np.uint64)).any(1)
