@@ -43,7 +43,7 @@ SOURCES = [("lnr_density_ht.hip", f"lnr_density_ht{ht}.o", [f"-DLNR_HT={ht}"]) f
           [("lnr_density_f16_bwd.hip", f"lnr_density_f16_bwd{part}_fq{fq}.o", [f"-DLNR_BWD_PART={part}", f"-DLNR_BWD_FQ={fq}"]) for part in (2, 1, 0) for fq in (0, 1)] + \
           [("lnr_density_f16_fwd.hip", f"lnr_density_f16_fwd{part}_fq{fq}.o", [f"-DLNR_FWD_PART={part}", f"-DLNR_FWD_FQ={fq}"]) for part in (1, 0) for fq in (0, 1)] + \
           [(s, s.replace(".hip", ".o"), EXTRA.get(s, [])) for s in
-           ("lnr_core.hip", "lnr_density.hip", "lnr_density_f16.hip", "lnr_density_bf3.hip", "lnr_density_wide.hip", "lnr_encode.hip", "lnr_sampler.hip", "lnr_render.hip", "lnr_render_peak.hip", "lnr_mesh.hip", "lnr_cloud.hip", "lnr_icp.hip", "lnr_cloud_tools.hip", "lnr_mesh_tools.hip", "lnr_mesh_filters.hip", "lnr_raycast.hip", "lnr_tsdf.hip", "lnr_track.hip", "lnr_scan.hip", "lnr_rays.hip", "lnr_image.hip", "lnr_optim.hip", "lnr_pose.hip", "lnr_comm.hip")]
+           ("lnr_core.hip", "lnr_density.hip", "lnr_table_reduce.hip", "lnr_density_f16.hip", "lnr_density_bf3.hip", "lnr_density_wide.hip", "lnr_encode.hip", "lnr_sampler.hip", "lnr_render.hip", "lnr_render_peak.hip", "lnr_mesh.hip", "lnr_cloud.hip", "lnr_icp.hip", "lnr_cloud_tools.hip", "lnr_mesh_tools.hip", "lnr_mesh_filters.hip", "lnr_raycast.hip", "lnr_tsdf.hip", "lnr_track.hip", "lnr_scan.hip", "lnr_rays.hip", "lnr_image.hip", "lnr_optim.hip", "lnr_pose.hip", "lnr_comm.hip")]
 
 
 def _hipcc():
@@ -57,7 +57,7 @@ _INC = re.compile(r'^\s*#\s*include\s+"([^"]+)"', re.M)
 
 
 def _deps_digest(path, seen=None):
-    """Digest of the headers a source includes (transitively, quoted includes only): an edit rebuilds the objects that see it, not all 28."""
+    """Digest of the headers a source includes (transitively, quoted includes only): an edit rebuilds the objects that see it, not all 47."""
     seen = {} if seen is None else seen
     text = open(path, "rb").read()
     for inc in _INC.findall(text.decode("utf-8", "replace")):
@@ -71,7 +71,7 @@ def _deps_digest(path, seen=None):
 
 # the sources of the kernels profiles/traffic.json holds PMC traffic for (encode forward / backward, table-gradient reduce, the default
 # network's MLP kernels, Adam) and what they include
-TRAFFIC_SOURCES = ("lnr_encode.hip", "lnr_encoding.h", "lnr_density.hip", "lnr_density_api.h", "lnr_density_bf3.hip", "lnr_density_impl.h",
+TRAFFIC_SOURCES = ("lnr_encode.hip", "lnr_encoding.h", "lnr_density.hip", "lnr_table_reduce.hip", "lnr_density_api.h", "lnr_density_bf3.hip", "lnr_density_impl.h",
                    "lnr_common.h", "lnr_optim.hip")
 
 

@@ -1,21 +1,15 @@
 // Density network: host-side dispatch (C ABI) of the level-major pipeline
 //   forward : encode (level-major, lnr_encode.hip) -> feature planes -> MLP (fp32 MFMA, lnr_density_impl.h)
 //   backward: [encode] -> MLP backward (weight-gradient slabs + d_feature planes) -> encode backward (table-gradient
-//             records + d/dx planes) -> table_grad_reduce2 (per-owner LDS reduction) -> slab reduce
+//             records + d/dx planes) -> table_grad_reduce2 (per-owner LDS reduction) -> slab reduce (both: lnr_table_reduce.hip)
 // plus the MFMA layout self-test.
-#include <stdlib.h>
-
 #include "lnr_density_api.h"
 #include <vector>
-#include <cstdlib>
 #include <cstdio>
-
 #include <mutex>
 #include <unordered_map>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-#define LNR_ENC_BWD_MAX_BPG 2048
 
 // ------------------------------------------------------------------------------------------------
 // Host-side note per workspace (keyed by its address): which layout last used it, whether the 64-bit overflow accumulators of that layout
@@ -73,342 +67,6 @@ void ws_forget(const void* ws) {
 }
 }  // namespace
 
-// grad[i] += sum over workgroup slabs.  A 64 x 16 workgroup: 64 consecutive parameters, the slabs split over 16 thread rows
-// (a thousand threads share the reads instead of one per parameter), rows combined through LDS in a fixed order: no
-// atomics, bit-reproducible.
-#define LNR_SLAB_GROUPS 16
-// the fold of 64 consecutive parameters by one 1024-thread workgroup (`block` = which 64): reduce_slabs_kernel, and the extra workgroups
-// at the end of table_grad_reduce2_kernel's grid (one launch fewer per backward: ~4.5 us of a one-keyframe rank's 0.34 ms iteration)
-__device__ __forceinline__ void slab_fold_block(const float* __restrict__ slabs, int n_slabs, int n_mlp, float* __restrict__ grad, int overwrite, int block) {
-    __shared__ float part[LNR_SLAB_GROUPS][64];
-    const int px = threadIdx.x & 63, gy = threadIdx.x >> 6;
-    const int i = block * 64 + px;
-    const int per = (n_slabs + LNR_SLAB_GROUPS - 1) / LNR_SLAB_GROUPS;
-    int b = gy * per;
-    const int b_end = min(n_slabs, b + per);
-    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
-    if (i < n_mlp) {
-        for (; b + 3 < b_end; b += 4) {
-            s0 += slabs[(size_t)b * n_mlp + i]; s1 += slabs[(size_t)(b + 1) * n_mlp + i];
-            s2 += slabs[(size_t)(b + 2) * n_mlp + i]; s3 += slabs[(size_t)(b + 3) * n_mlp + i];
-        }
-        for (; b < b_end; ++b) s0 += slabs[(size_t)b * n_mlp + i];
-    }
-    part[gy][px] = (s0 + s1) + (s2 + s3);
-    __syncthreads();
-    if (gy == 0 && i < n_mlp) {
-        float s = 0.0f;
-#pragma unroll
-        for (int k = 0; k < LNR_SLAB_GROUPS; ++k) s += part[k][px];
-        grad[i] = overwrite ? s : grad[i] + s;
-    }
-}
-__global__ void __launch_bounds__(64 * LNR_SLAB_GROUPS)
-reduce_slabs_kernel(const float* __restrict__ slabs, int n_slabs, int n_mlp, float* __restrict__ grad, int overwrite) {
-    slab_fold_block(slabs, n_slabs, n_mlp, grad, overwrite, (int)blockIdx.x);
-}
-
-// Workgroup `o` owns floats [o << shift, (o+1) << shift) of the table gradient.  The encode-backward workgroups of
-// level l (bpg of them) wrote the records addressed to it into regions [l][o - first_owner(l)][chunk];
-// it streams them, sums them in LDS in 64-bit fixed point (LDS float atomics run at < 1 lane/clk/CU on CDNA4, integer
-// ones ~16x faster; 2^-42 resolution, exact and order-independent) and adds the slice to grad_table with coalesced
-// read-modify-writes (it is the only writer of that slice).  PAIR: packed pair records (n_features >= 2) or {idx, v}
-// records - see lnr_density_api.h.
-//
-// The kernel is bound by instruction issue and latency, not by bytes (ablations in docs/HISTORY.md 4.3): a region holds ~30-60 records,
-// so every wave instruction serves one short region.  Hence the shape of the loop: a wave takes a contiguous run of its owner's
-// regions, lane r holds region r's record count, and everything that depends only on the region - its count (v_readlane), its
-// address (scalar arithmetic), the trip count - stays on the scalar unit; the first piece (64 x-pair records or 128 8-byte
-// records, one load per lane) of RED_U regions is in flight while the previous RED_U are summed; the rare longer regions are
-// finished by a second loop.  64 VGPRs, so that two workgroups (2 x 64 KB of accumulators) share a CU.
-template <int PAIR>
-__device__ __forceinline__ void reduce_one(long long* acc, uint2 r, uint32_t base) {
-    if (PAIR) {
-        uint32_t pi; float v0, v1;
-        lnr_unpack_pair(r, pi, v0, v1);
-        // no test for zero: a record exists because one of its values is non-zero, and a branch per value costs more than adding 0
-        unsigned long long* a = reinterpret_cast<unsigned long long*>(acc) + 2 * pi;
-        if (__builtin_expect(__builtin_fmaxf(__builtin_fabsf(v0), __builtin_fabsf(v1)) < 256.0f, 1)) {
-            atomicAdd(a, (unsigned long long)lnr_to_fix_small(v0));
-            atomicAdd(a + 1, (unsigned long long)lnr_to_fix_small(v1));
-        } else {
-            atomicAdd(a, (unsigned long long)lnr_to_fix(v0));
-            atomicAdd(a + 1, (unsigned long long)lnr_to_fix(v1));
-        }
-    } else {
-        const float v = __uint_as_float(r.y);
-        if (v != 0.0f) atomicAdd(reinterpret_cast<unsigned long long*>(&acc[r.x - base]), (unsigned long long)lnr_to_fix(v));
-    }
-}
-__device__ __forceinline__ void reduce_xpair(long long* acc, const LnrXRec& r) {
-    uint32_t pi, t; float a0, a1, fx;
-    lnr_unpack_xpair(r, pi, t, a0, a1, fx);
-    const uint32_t pj = pi ^ ((2u << t) - 1u);                        // the (x+1) corner's entry: e ^ (2^(t+1) - 1)
-    long long q[4];
-    lnr_xpair_fix(a0, a1, fx, q);
-    unsigned long long* a = reinterpret_cast<unsigned long long*>(acc);
-    atomicAdd(a + 2 * pi, (unsigned long long)q[0]);
-    atomicAdd(a + 2 * pi + 1, (unsigned long long)q[1]);
-    atomicAdd(a + 2 * pj, (unsigned long long)q[2]);
-    atomicAdd(a + 2 * pj + 1, (unsigned long long)q[3]);
-}
-
-#ifdef LNR_PHASE_TIMING
-__device__ unsigned long long lnr_reduce_phase_cycles[LNR_N_PHASES];
-#endif
-#define RED_SLICE (1 << LNR_SLICE_SHIFT)
-
-// records are read once: streaming (nt) loads
-typedef uint32_t red_u32x3 __attribute__((ext_vector_type(3), aligned(4)));
-typedef uint32_t red_u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ LnrXRec load_xrec_stream(const char* p) {
-    const red_u32x3 v = __builtin_nontemporal_load(reinterpret_cast<const red_u32x3*>(p));
-    LnrXRec r; r.a = v.x; r.b = v.y; r.c = v.z;
-    return r;
-}
-__device__ __forceinline__ uint4 load_rec2_stream(const uint4* p) {
-    const red_u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const red_u32x4*>(p));
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-
-// One wave sums the records of n_regions consecutive regions (of one level and owner) into the workgroup's LDS accumulators.
-template <int PAIR, int RED_U>
-__device__ __forceinline__ void reduce_regions(long long* acc, const int* __restrict__ wave_counts, const char* __restrict__ wave_regions, int n_regions,
-                                               uint32_t region_bytes, bool xp, uint32_t base, int lane) {
-    for (int r0 = 0; r0 < n_regions; r0 += 64) {
-        const int nq = min(64, n_regions - r0);                                                      // regions of this round (wave-uniform)
-        const int my_n = lane < nq ? wave_counts[r0 + lane] : 0;
-        const char* round_regions = wave_regions + (size_t)r0 * region_bytes;
-        if (xp) {
-            // x-pair levels (lnr_density_api.h): 12-byte records, a piece = 64 records = one 12-byte load per lane; the first two pieces
-            // of a region go through the pipelined loop (an encode-backward workgroup leaves ~65 records per region)
-            LnrXRec cur[RED_U][2], nxt[RED_U][2];
-            auto loadx = [&](int q0, LnrXRec out[RED_U][2]) {
-#pragma unroll
-                for (int u = 0; u < RED_U; ++u) {
-                    const int q = q0 + u < nq ? q0 + u : nq - 1;                                     // clamp: unconditional loads
-                    const int n = __builtin_amdgcn_readlane(my_n, q);
-                    const char* rg = round_regions + (size_t)q * region_bytes;
-                    out[u][0] = load_xrec_stream(rg + (lane < n ? lane : 0) * 12);
-                    out[u][1] = load_xrec_stream(rg + (lane + 64 < n ? lane + 64 : 0) * 12);
-                }
-            };
-            loadx(0, nxt);
-            for (int q0 = 0; q0 < nq; q0 += RED_U) {
-#pragma unroll
-                for (int u = 0; u < RED_U; ++u) { cur[u][0] = nxt[u][0]; cur[u][1] = nxt[u][1]; }
-                if (q0 + RED_U < nq) loadx(q0 + RED_U, nxt);
-#pragma unroll
-                for (int u = 0; u < RED_U; ++u) {
-                    const int n = q0 + u < nq ? __builtin_amdgcn_readlane(my_n, q0 + u < 64 ? q0 + u : 63) : 0;
-                    if (lane < n) reduce_xpair(acc, cur[u][0]);
-                    if (lane + 64 < n) reduce_xpair(acc, cur[u][1]);
-                }
-            }
-            unsigned long long more = __ballot(my_n > 128);                                          // regions with further pieces: rare
-            while (more) {
-                const int q = __builtin_ctzll(more);
-                more &= more - 1ull;
-                const int n = __builtin_amdgcn_readlane(my_n, q);
-                const char* rg = round_regions + (size_t)q * region_bytes;
-                for (int off = 128; off < n; off += 64 * 4) {                                        // four pieces in flight
-                    LnrXRec r[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) { const int k = off + 64 * u + lane; r[u] = load_xrec_stream(rg + (size_t)(k < n ? k : n - 1) * 12); }
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) if (off + 64 * u + lane < n) reduce_xpair(acc, r[u]);
-                }
-            }
-            continue;
-        }
-        // 8-byte records: a piece = 128 records = one 16-byte load (two records) per lane
-        uint4 cur[RED_U], nxt[RED_U];
-        auto load4 = [&](int q0, uint4 out[RED_U]) {
-#pragma unroll
-            for (int u = 0; u < RED_U; ++u) {
-                const int q = q0 + u < nq ? q0 + u : nq - 1;
-                const int n = __builtin_amdgcn_readlane(my_n, q);
-                out[u] = load_rec2_stream(reinterpret_cast<const uint4*>(round_regions + (size_t)q * region_bytes) + (2 * lane < n ? lane : 0));   // regions are 16-byte aligned
-            }
-        };
-        load4(0, nxt);
-        for (int q0 = 0; q0 < nq; q0 += RED_U) {
-#pragma unroll
-            for (int u = 0; u < RED_U; ++u) cur[u] = nxt[u];
-            if (q0 + RED_U < nq) load4(q0 + RED_U, nxt);
-#pragma unroll
-            for (int u = 0; u < RED_U; ++u) {
-                const int n = q0 + u < nq ? __builtin_amdgcn_readlane(my_n, q0 + u < 64 ? q0 + u : 63) : 0;
-                if (2 * lane < n) reduce_one<PAIR>(acc, make_uint2(cur[u].x, cur[u].y), base);
-                if (2 * lane + 1 < n) reduce_one<PAIR>(acc, make_uint2(cur[u].z, cur[u].w), base);
-            }
-        }
-        unsigned long long more = __ballot(my_n > 128);
-        while (more) {
-            const int q = __builtin_ctzll(more);
-            more &= more - 1ull;
-            const int n = __builtin_amdgcn_readlane(my_n, q);
-            const uint2* rg = reinterpret_cast<const uint2*>(round_regions + (size_t)q * region_bytes);
-            for (int off = 128; off < n; off += 128 * 4) {                                           // four pieces (of 128 records) in flight
-                uint4 r[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) { const int k = off + 128 * u + 2 * lane; r[u] = load_rec2_stream(reinterpret_cast<const uint4*>(rg) + (k < n ? k : 0) / 2); }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int k = off + 128 * u + 2 * lane;
-                    if (k < n) reduce_one<PAIR>(acc, make_uint2(r[u].x, r[u].y), base);
-                    if (k + 1 < n) reduce_one<PAIR>(acc, make_uint2(r[u].z, r[u].w), base);
-                }
-            }
-        }
-    }
-}
-
-// float range of level l, its record-level bookkeeping (shared by the two reduce kernels)
-struct RedLevel { uint64_t lo, hi; };
-__device__ __forceinline__ RedLevel red_level(const LnrNetSpec& spec, int l) {
-    RedLevel r;
-    r.lo = (uint64_t)spec.level_offset[l] * spec.n_features;
-    r.hi = r.lo + (uint64_t)spec.level_size[l] * spec.n_features;
-    return r;
-}
-
-// Spatially coherent levels (RegionPlan::split > 1: dense-indexed ones, where an owner slice is a slab of cells and a scan pours most of
-// the level's records into two or three of them): `split` workgroups share an owner, each sums a run of the owner's regions in LDS and
-// adds its non-zero sums to the level's 64-bit overflow accumulators (integer atomics: exact, order-independent), which the owner's
-// workgroup of table_grad_reduce2_kernel folds in afterwards.  Without it those few owners were the whole kernel's critical path
-// (0.8 ms for level 1 of the default network against 0.2 ms for everything else).
-template <int PAIR, int RED_U, int MINW>
-__global__ void __launch_bounds__(1024, MINW)
-table_grad_reduce_split_kernel(const LnrNetSpec spec, const void* __restrict__ regions_v, const RegionPlan plan, const int* __restrict__ counts, int bpg,
-                               int maxo, long long* __restrict__ ovf) {
-    extern __shared__ long long acc[];
-    constexpr int slice = RED_SLICE, shift = LNR_SLICE_SHIFT;
-    int b = blockIdx.x, l = 0, span = 0;
-    int64_t my_ovf = 0;
-    RedLevel lv;
-    for (;; ++l) {                                                          // the host launched exactly sum(span * split) workgroups
-        lv = red_level(spec, l);
-        span = (int)(((lv.hi - 1) >> shift) - (lv.lo >> shift)) + 1;
-        const int n = plan.split[l] > 1 ? span * plan.split[l] : 0;
-        if (b < n) break;
-        b -= n;
-        my_ovf += (int64_t)(lv.hi - lv.lo);
-    }
-    const int parts = plan.split[l], local = b / parts, part = b % parts;
-    const uint32_t base = ((uint32_t)(lv.lo >> shift) + (uint32_t)local) << shift;
-    const uint32_t region_bytes = plan.bytes[l];
-    if (region_bytes == 0u) return;
-#pragma unroll
-    for (int i = threadIdx.x; i < slice; i += 1024) acc[i] = 0ll;
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int per_part = (bpg + parts - 1) / parts, part_first = part * per_part, part_n = min(per_part, bpg - part_first);
-    const int per_wave = (part_n + 15) / 16, first = part_first + wave * per_wave, n_regions = min(per_wave, part_first + part_n - first);
-    if (n_regions > 0)
-        reduce_regions<PAIR, RED_U>(acc, counts + ((size_t)l * maxo + local) * bpg + first,
-                                    reinterpret_cast<const char*>(regions_v) + plan.off[l] + ((size_t)local * bpg + first) * (size_t)region_bytes, n_regions,
-                                    region_bytes, PAIR && plan.xp[l] != 0, base, lane);
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < slice / 1024; ++k) {
-        const int i = threadIdx.x + k * 1024;
-        const uint64_t gi = (uint64_t)base + i;
-        const long long q = acc[i];
-        if (q != 0ll && gi >= lv.lo && gi < lv.hi) atomicAdd(reinterpret_cast<unsigned long long*>(ovf + my_ovf + (int64_t)(gi - lv.lo)), (unsigned long long)q);
-    }
-}
-
-template <int PAIR, int RED_U, int MINW>
-__global__ void __launch_bounds__(1024, MINW)   // HIP: (max threads, min waves per SIMD)
-table_grad_reduce2_kernel(const LnrNetSpec spec, const void* __restrict__ regions_v, const RegionPlan plan, const int* __restrict__ counts, int bpg,
-                          int maxo, long long* __restrict__ ovf, const int* __restrict__ ovf_flag, int epoch, float* __restrict__ grad_table,
-                          int64_t n_table_floats, int overwrite, const float* __restrict__ slabs, int n_slabs, int n_mlp, float* __restrict__ grad_mlp) {
-    extern __shared__ long long acc[];
-    // slabs != NULL: the last ceil(n_mlp / 64) workgroups of the grid fold the MLP backward's weight-gradient slabs (slab_fold_block)
-    const int slab_blocks = slabs != nullptr ? (n_mlp + 63) / 64 : 0;
-    const int owner_blocks = (int)gridDim.x - slab_blocks;
-    if ((int)blockIdx.x >= owner_blocks) {                                   // (workgroup-uniform)
-        slab_fold_block(slabs, n_slabs, n_mlp, grad_mlp, overwrite, (int)blockIdx.x - owner_blocks);
-        return;
-    }
-    // Owners in DESCENDING table order: the hardware starts workgroups in blockIdx order, the chip holds 512 of the ~900 at a time, and
-    // the owners of the fine (x-pair) levels - the heaviest, and with the default network exactly 512 of them - sit at the END of the
-    // table: started last they were the kernel's tail behind a half-empty chip; started first they fill it, and the lighter owners of
-    // the coarse levels follow.
-    const int o = owner_blocks - 1 - (int)blockIdx.x;
-    constexpr int slice = RED_SLICE, shift = LNR_SLICE_SHIFT;
-    const uint32_t base = (uint32_t)o << shift;
-    PHASE_INIT();
-#pragma unroll
-    for (int i = threadIdx.x; i < slice; i += 1024) acc[i] = 0ll;
-    __syncthreads();
-    PHASE(0);
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    constexpr int nwaves = 16;
-    int64_t ovf_off = 0;                                                   // running offset of the record levels' overflow accumulators
-    for (int l = 0; l < spec.n_levels; ++l) {
-        const RedLevel lv = red_level(spec, l);
-        const uint64_t lo = lv.lo, hi = lv.hi;
-        const int64_t my_ovf = ovf_off;
-        ovf_off += (int64_t)(hi - lo);                                      // every level has overflow accumulators
-        if (hi <= base || lo >= (uint64_t)base + slice) continue;
-        // records that did not fit their region were summed into 64-bit accumulators by the encode kernel (and, on split levels, all
-        // records by the split kernel): same fixed point, so region records + overflow add up exactly, whatever the (arrival-order
-        // dependent) split between the two was.  [r4] The accumulators are ALL ZERO between calls: a kernel that adds to a level's
-        // stores the call's epoch in the level's status word, only then are they read here - and put back to zero by this, their only,
-        // reader (no 59 MB memset per call, no 59 MB of reads for levels nothing overflowed on; split levels always carry sums)
-        if (plan.split[l] > 1 || ovf_flag[l] == epoch) {               // workgroup-uniform
-            long long v[slice / 1024];
-#pragma unroll
-            for (int k = 0; k < slice / 1024; ++k) {
-                const uint64_t gi = (uint64_t)base + threadIdx.x + k * 1024;
-                v[k] = (gi >= lo && gi < hi) ? ovf[my_ovf + (int64_t)(gi - lo)] : 0ll;
-            }
-#pragma unroll
-            for (int k = 0; k < slice / 1024; ++k) {
-                if (v[k] != 0ll) {
-                    acc[threadIdx.x + k * 1024] += v[k];
-                    ovf[my_ovf + (int64_t)((uint64_t)base + threadIdx.x + k * 1024 - lo)] = 0ll;
-                }
-            }
-            __syncthreads();
-            PHASE(1);
-        }
-        const int local = o - (int)(lo >> shift);
-        if (local < 0 || local >= maxo) continue;
-        const uint32_t region_bytes = plan.bytes[l];
-        if (region_bytes == 0u || plan.split[l] > 1) continue;              // every record of this level overflowed / went through the split kernel
-        const int per_wave = (bpg + nwaves - 1) / nwaves;
-        const int first = wave * per_wave;
-        const int n_regions = min(per_wave, bpg - first);
-        if (n_regions > 0)
-            reduce_regions<PAIR, RED_U>(acc, counts + ((size_t)l * maxo + local) * bpg + first,
-                                        reinterpret_cast<const char*>(regions_v) + plan.off[l] + ((size_t)local * bpg + first) * (size_t)region_bytes, n_regions,
-                                        region_bytes, PAIR && plan.xp[l] != 0, base, lane);
-        PHASE(3);
-    }
-    __syncthreads();
-    PHASE(5);
-    {
-        // LNR_BWD_OVERWRITE_GRAD (workgroup-uniform): the slice IS this call's gradient - every float is stored, none is read
-        float g[slice / 1024];
-#pragma unroll
-        for (int k = 0; k < slice / 1024; ++k) {
-            const int64_t gi = (int64_t)base + threadIdx.x + k * 1024;
-            g[k] = (!overwrite && gi < n_table_floats) ? grad_table[gi] : 0.0f;
-        }
-#pragma unroll
-        for (int k = 0; k < slice / 1024; ++k) {
-            const int64_t gi = (int64_t)base + threadIdx.x + k * 1024;
-            const long long q = acc[threadIdx.x + k * 1024];
-            if (gi < n_table_floats && (overwrite || q != 0ll)) grad_table[gi] = g[k] + (float)((double)q * (1.0 / (double)LNR_FIX_SCALE));
-        }
-    }
-    PHASE(6);
-    PHASE_FLUSH(lnr_reduce_phase_cycles, 0);
-}
-
 // ------------------------------------------------------------------------------------------------
 // workspace layout: [feat enc_dim x m_pad][dfeat enc_dim x m_pad][dxl groups x 3 x m_pad][slabs][counts][regions]
 // ------------------------------------------------------------------------------------------------
@@ -443,7 +101,7 @@ static Layout make_layout(const LnrNetSpec* spec, int64_t n_points, const Densit
     L.nown = (int)((n_table + (1 << L.shift) - 1) >> L.shift);
     int64_t bpg = (n_points + LNR_ENC_BWD_BLOCK * LNR_BATCHES_PER_WG - 1) / (LNR_ENC_BWD_BLOCK * LNR_BATCHES_PER_WG);   // batches per encode-backward workgroup
     if (bpg < 1) bpg = 1;
-    if (bpg > LNR_ENC_BWD_MAX_BPG) bpg = LNR_ENC_BWD_MAX_BPG;
+    if (bpg > LNR_ENC_MAX_BPG) bpg = LNR_ENC_MAX_BPG;
     bpg = (bpg + 3) & ~(int64_t)3;       // the wave-private partition runs 4 waves (= 4 chunks) per workgroup
     L.bpg = (int)bpg;
     L.maxo = 1;
@@ -459,8 +117,7 @@ static Layout make_layout(const LnrNetSpec* spec, int64_t n_points, const Densit
             region_total = 0; ovf_total = 0; L.maxo = 1; L.n_split = 0;
             for (int l = 0; l < spec->n_levels; ++l) {
                 ovf_total += (size_t)spec->level_size[l] * F;
-                const uint64_t lo = (uint64_t)spec->level_offset[l] * F, hi = lo + (uint64_t)spec->level_size[l] * F;
-                const int span = (int)(((hi - 1) >> L.shift) - (lo >> L.shift)) + 1;
+                const int span = lnr_level_span(spec, l, L.shift);
                 if (span > L.maxo) L.maxo = span;
                 // expected records per (owner, chunk): 8 corner updates per point (F/2 pair records each), spread over the level's owners
                 const bool xp = lnr_level_can_use_xpairs(*spec, l, LNR_XPAIR_SCALE_MIN);
@@ -520,8 +177,7 @@ static void report_regions(const LnrNetSpec* spec, const Layout& L, const Region
     for (int l = 0; l < spec->n_levels; ++l) {
         const int rec = plan.xp[l] ? 12 : 8, cap = (int)(plan.bytes[l] / rec);
         long long sum = 0, over = 0; int mx = 0;
-        const uint64_t lo = (uint64_t)spec->level_offset[l] * spec->n_features, hi = lo + (uint64_t)spec->level_size[l] * spec->n_features;
-        const int span = (int)(((hi - 1) >> L.shift) - (lo >> L.shift)) + 1;
+        const int span = lnr_level_span(spec, l, L.shift);
         for (int o = 0; o < span; ++o)
             for (int c = 0; c < L.bpg; ++c) {
                 const int v = h[((size_t)l * L.maxo + o) * L.bpg + c];
@@ -688,47 +344,6 @@ static int mlp_bwd_regs(const MlpArgs& a) {
 #undef LNR_REGS_CASE
 }
 
-namespace {
-struct ReduceCtx {
-    const LnrNetSpec* spec;
-    const void* regions; const int* counts; long long* ovf; const int* ovf_flag; int epoch; float* grad_table;
-    RegionPlan plan; int bpg, maxo, shift; int64_t n_table; int n_split; int overwrite;
-    const float* slabs; int n_slabs, n_mlp; float* grad_mlp;          // slabs != NULL: the weight-gradient fold rides in the reduce launch
-};
-
-template <int PAIR, int U, int W>
-static int launch_reduce_variant(const ReduceCtx& c, int n_owners, hipStream_t st) {
-    const size_t lds = (size_t)RED_SLICE * sizeof(long long);
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(table_grad_reduce2_kernel<PAIR, U, W>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(table_grad_reduce_split_kernel<PAIR, U, W>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        lnr_set_error("lnr_density_backward: hipFuncSetAttribute failed"); return LNR_ERR_LAUNCH;
-    }
-    if (c.n_split > 0) {
-        LnrProfScope prof("table_grad_reduce_split", st);
-        hipLaunchKernelGGL((table_grad_reduce_split_kernel<PAIR, U, W>), dim3(c.n_split), dim3(1024), lds, st, *c.spec, c.regions, c.plan, c.counts, c.bpg, c.maxo,
-                           c.ovf);
-    }
-    LnrProfScope prof("table_grad_reduce", st);
-    const int slab_blocks = c.slabs != nullptr ? (c.n_mlp + 63) / 64 : 0;
-    hipLaunchKernelGGL((table_grad_reduce2_kernel<PAIR, U, W>), dim3(n_owners + slab_blocks), dim3(1024), lds, st, *c.spec, c.regions, c.plan, c.counts, c.bpg, c.maxo,
-                       c.ovf, c.ovf_flag, c.epoch, c.grad_table, c.n_table, c.overwrite, c.slabs, c.n_slabs, c.n_mlp, c.grad_mlp);
-    return LNR_OK;
-}
-// 2 regions in flight per wave at 8 waves per SIMD (two workgroups per CU) measured best: 0.35 ms against 0.37 (4 in flight, 8 waves),
-// 0.40 (4, 4 waves) and 0.43 (8, 4 waves) on the bench workload
-#ifndef LNR_RED_U
-#define LNR_RED_U 2
-#endif
-#ifndef LNR_RED_W
-#define LNR_RED_W 8
-#endif
-int launch_table_reduce(const ReduceCtx& c, int n_owners, hipStream_t st) {
-    if (c.spec->n_features < 2) return launch_reduce_variant<0, LNR_RED_U, LNR_RED_W>(c, n_owners, st);
-    return launch_reduce_variant<1, LNR_RED_U, LNR_RED_W>(c, n_owners, st);
-}
-
-}  // namespace
-
 static int make_src(PointSrc* s, MlpPoints* mp, const float* pts, int64_t n_points, const float* rays, const float* z,
                     int32_t n_rays, int32_t n_samples, const int32_t* n_rays_dev, const char* who) {
     if (pts != nullptr) {
@@ -742,6 +357,41 @@ static int make_src(PointSrc* s, MlpPoints* mp, const float* pts, int64_t n_poin
         *mp = MlpPoints{(int64_t)n_rays * n_samples, n_rays_dev, n_rays, n_samples, nullptr};
     }
     return LNR_OK;
+}
+
+// The head of lnr_density_forward, lnr_density_backward and lnr_density_fold_weight_grads (`who`): everything that happens before
+// the first launch, in one order, so that a bad call fails with the same status and text whichever entry point it reaches.
+struct CallHead { PointSrc src; MlpPoints mp; int64_t cap; DensityRoute route; Layout L; };
+enum { HEAD_FORWARD, HEAD_BACKWARD, HEAD_FOLD };
+// route and layout for h->cap points, then the checks that need them: the 32-bit plane offsets, the workspace size, the route
+static int head_plan(const LnrNetSpec* spec, int kind, size_t workspace_bytes, const char* who, CallHead* h) {
+    h->route = lnr_route(spec, h->cap, kind != HEAD_FORWARD);          // (the fold: the route of the backward whose slabs these are)
+    h->L = make_layout(spec, h->cap, h->route);
+    const size_t need = kind == HEAD_FORWARD ? h->L.off_dfeat : h->L.total;
+    if (kind == HEAD_FOLD) LNR_REQUIRE(workspace_bytes >= need, "%s: workspace too small", who);
+    else {
+        // (the limit is on the PADDED plane stride - the sample count rounded up to 64, plus the skew: ADVICE r5)
+        LNR_REQUIRE(h->L.m_pad * (spec->n_features > 4 ? spec->n_features : 4) < (1ll << 30),
+                    "%s: too many points per call for 32-bit plane offsets (padded n_points * max(n_features, 4) must be < 2^30)", who);
+        if (workspace_bytes < need) {
+            lnr_set_error("%s: workspace %zu < %zu (%s)", who, workspace_bytes, need, kind == HEAD_FORWARD ? "lnr_density_workspace_forward" : "lnr_density_workspace");
+            return LNR_ERR_WORKSPACE;
+        }
+    }
+    return h->route.kind == LNR_ROUTE_UNSUPPORTED ? route_unsupported(spec, h->route, who) : LNR_OK;
+}
+// forward and backward: the spec, the points (h->cap == 0 with LNR_OK: an empty batch - nothing to do, nothing was checked), the entry
+// point's own argument check (bad_args: what is wrong with them, or NULL), then head_plan
+static int call_head(const LnrNetSpec* spec, int kind, const char* who, const float* pts, int64_t n_points, const float* rays, const float* z, int32_t n_rays,
+                     int32_t n_samples, const int32_t* n_rays_dev, const char* bad_args, size_t workspace_bytes, CallHead* h) {
+    h->cap = 0;
+    int rc = check_spec(spec, who);
+    if (rc || (n_points == 0 && (pts != nullptr || n_rays == 0))) return rc;
+    rc = make_src(&h->src, &h->mp, pts, n_points, rays, z, n_rays, n_samples, n_rays_dev, who);
+    if (rc || h->mp.n_points == 0) return rc;
+    LNR_REQUIRE(bad_args == nullptr, "%s: %s", who, bad_args);
+    h->cap = h->mp.n_points;
+    return head_plan(spec, kind, workspace_bytes, who, h);
 }
 
 extern "C" size_t lnr_density_workspace(const LnrNetSpec* spec, int64_t n_points) {
@@ -773,25 +423,11 @@ extern "C" int lnr_density_workspace_release(void* workspace) {
 extern "C" int lnr_density_forward(const LnrNetSpec* spec, const float* params, const float* pts, int64_t n_points,
                                    const float* rays, const float* z, int32_t n_rays, int32_t n_samples,
                                    const int32_t* n_rays_dev, float* sigma, void* workspace, size_t workspace_bytes, void* stream) {
-    int rc = check_spec(spec, "lnr_density_forward");
-    if (rc) return rc;
-    if (n_points == 0 && (pts != nullptr || n_rays == 0)) return LNR_OK;          // empty batch: nothing to do, nothing to check
-    PointSrc src; MlpPoints mp;
-    rc = make_src(&src, &mp, pts, n_points, rays, z, n_rays, n_samples, n_rays_dev, "lnr_density_forward");
-    if (rc) return rc;
-    const int64_t cap = mp.n_points;
-    if (cap == 0) return LNR_OK;
-    LNR_REQUIRE(params && sigma && workspace, "lnr_density_forward: null params/sigma/workspace");
-    const DensityRoute route = lnr_route(spec, cap, false);
-    const Layout L = make_layout(spec, cap, route);
-    // (the limit is on the PADDED plane stride - the sample count rounded up to 64, plus the skew: ADVICE r5)
-    LNR_REQUIRE(L.m_pad * (spec->n_features > 4 ? spec->n_features : 4) < (1ll << 30),
-                "lnr_density_forward: too many points per call for 32-bit plane offsets (padded n_points * max(n_features, 4) must be < 2^30)");
-    if (workspace_bytes < L.off_dfeat) {
-        lnr_set_error("lnr_density_forward: workspace %zu < %zu (lnr_density_workspace_forward)", workspace_bytes, L.off_dfeat);
-        return LNR_ERR_WORKSPACE;
-    }
-    if (route.kind == LNR_ROUTE_UNSUPPORTED) return route_unsupported(spec, route, "lnr_density_forward");
+    CallHead h;
+    int rc = call_head(spec, HEAD_FORWARD, "lnr_density_forward", pts, n_points, rays, z, n_rays, n_samples, n_rays_dev,
+                       params && sigma && workspace ? nullptr : "null params/sigma/workspace", workspace_bytes, &h);
+    if (rc || h.cap == 0) return rc;
+    const PointSrc& src = h.src; MlpPoints& mp = h.mp; const int64_t cap = h.cap; const DensityRoute& route = h.route; const Layout& L = h.L;
     hipStream_t st = (hipStream_t)stream;
     ws_touch(workspace, layout_signature(spec, cap));
     float* feat = (float*)((char*)workspace + L.off_feat);
@@ -821,35 +457,25 @@ extern "C" int lnr_density_backward(const LnrNetSpec* spec, const float* params,
                                     const int32_t* n_rays_dev, const float* d_sigma, float* grad_params, float* d_pts, float* d_rays,
                                     int32_t reuse_features, int32_t flags, void* workspace, size_t workspace_bytes, void* input_grad_event,
                                     void* stream) {
-    int rc = check_spec(spec, "lnr_density_backward");
-    if (rc) return rc;
-    // an empty batch has nothing to compute, but the input-gradient event is part of the contract of every successful call: a caller's
-    // second stream waits for it, and an unrecorded event would let that stream run against the PREVIOUS call's record
-    auto empty_batch = [&]() -> int {
-        if (input_grad_event != nullptr && hipEventRecord((hipEvent_t)input_grad_event, (hipStream_t)stream) != hipSuccess) {
+    hipStream_t st = (hipStream_t)stream;
+    // the input gradient (d_pts / d_rays) is complete where this is called; what follows only finishes grad_params.  A caller that
+    // continues with the input gradient on another stream (pose gradient, pose step, the next batch's rays and samples) waits for this
+    // event instead of for the whole call.  An empty batch has nothing to compute, but the event is part of the contract of every
+    // successful call: an unrecorded event would let that stream run against the PREVIOUS call's record
+    auto input_grad_done = [&]() -> int {
+        if (input_grad_event != nullptr && hipEventRecord((hipEvent_t)input_grad_event, st) != hipSuccess) {
             lnr_set_error("lnr_density_backward: hipEventRecord failed");
             return LNR_ERR_LAUNCH;
         }
         return LNR_OK;
     };
-    if (n_points == 0 && (pts != nullptr || n_rays == 0)) return empty_batch();
-    PointSrc src; MlpPoints mp;
-    rc = make_src(&src, &mp, pts, n_points, rays, z, n_rays, n_samples, n_rays_dev, "lnr_density_backward");
+    CallHead h;
+    int rc = call_head(spec, HEAD_BACKWARD, "lnr_density_backward", pts, n_points, rays, z, n_rays, n_samples, n_rays_dev,
+                       !(params && d_sigma && workspace) ? "null argument"
+                       : !(grad_params || d_pts || d_rays) ? "nothing to compute (no grad_params, d_pts or d_rays)" : nullptr, workspace_bytes, &h);
     if (rc) return rc;
-    const int64_t cap = mp.n_points;
-    if (cap == 0) return empty_batch();
-    LNR_REQUIRE(params && d_sigma && workspace, "lnr_density_backward: null argument");
-    LNR_REQUIRE(grad_params || d_pts || d_rays, "lnr_density_backward: nothing to compute (no grad_params, d_pts or d_rays)");
-    const DensityRoute route = lnr_route(spec, cap, true);
-    const Layout L = make_layout(spec, cap, route);
-    LNR_REQUIRE(L.m_pad * (spec->n_features > 4 ? spec->n_features : 4) < (1ll << 30),
-                "lnr_density_backward: too many points per call for 32-bit plane offsets (padded n_points * max(n_features, 4) must be < 2^30)");
-    if (workspace_bytes < L.total) {
-        lnr_set_error("lnr_density_backward: workspace %zu < %zu (lnr_density_workspace)", workspace_bytes, L.total);
-        return LNR_ERR_WORKSPACE;
-    }
-    if (route.kind == LNR_ROUTE_UNSUPPORTED) return route_unsupported(spec, route, "lnr_density_backward");
-    hipStream_t st = (hipStream_t)stream;
+    if (h.cap == 0) return input_grad_done();
+    const PointSrc& src = h.src; const MlpPoints& mp = h.mp; const int64_t cap = h.cap; const DensityRoute& route = h.route; const Layout& L = h.L;
     char* ws = (char*)workspace;
     float* feat = (float*)(ws + L.off_feat);
     float* dfeat = (float*)(ws + L.off_dfeat);
@@ -915,13 +541,12 @@ extern "C" int lnr_density_backward(const LnrNetSpec* spec, const float* params,
     }
     // the weight-gradient fold rides in the table reduce's launch whenever both run in this call
     const bool fold_in_reduce = want_grad && hash && L.nown > 0 && !(flags & LNR_BWD_DEFER_WEIGHT_FOLD);
-    ReduceCtx rctx{spec, regions, counts, ovf, ovf_flag, epoch, grad_table, rplan, L.bpg, L.maxo, L.shift, spec->n_params - spec->n_mlp_params,
-                   (flags & LNR_BWD_TABLE_ATOMICS) ? 0 : L.n_split, (flags & LNR_BWD_OVERWRITE_GRAD) ? 1 : 0,
-                   fold_in_reduce ? slabs : nullptr, route.n_slabs, spec->n_mlp_params, grad_params};
+    const TableGradSink sink{grad_table, want_grad ? regions : nullptr, rplan, counts, L.bpg, L.maxo, L.shift, ovf, ovf_flag, epoch};
+    const SlabFold fold{slabs, route.n_slabs, spec->n_mlp_params, grad_params};
+    const int overwrite = (flags & LNR_BWD_OVERWRITE_GRAD) ? 1 : 0;
     if (want_dfeat && !fused_freq) {
-        rc = lnr_encode_backward(spec, params, &src, cap, dfeat, dxl, L.m_pad, grad_table, want_grad ? regions : nullptr, &rplan, counts,
-                                 L.bpg, L.maxo, L.shift,
-                                 ovf, ovf_flag, epoch, d_pts_eff, ray_accum ? d_rays : nullptr, (long long*)(ws + L.off_rayacc), (flags & LNR_BWD_BINS_W8) != 0, st);
+        const InputGradOut out{dxl, d_pts_eff, ray_accum ? d_rays : nullptr, (long long*)(ws + L.off_rayacc)};
+        rc = lnr_encode_backward(spec, params, &src, cap, dfeat, L.m_pad, sink, out, (flags & LNR_BWD_BINS_W8) != 0, st);
         if (rc) return rc;
         LNR_CHECK_LAUNCH("lnr_density_backward(encode backward)");
     }
@@ -929,14 +554,8 @@ extern "C" int lnr_density_backward(const LnrNetSpec* spec, const float* params,
         rc = lnr_points_grad_to_rays(d_pts_eff, z, n_rays, n_rays_dev, n_samples, d_rays, stream);
         if (rc) return rc;
     }
-    // the input gradient (d_pts / d_rays) is complete here; what follows only finishes grad_params.  A caller that continues with
-    // the input gradient on another stream (pose gradient, pose step, the next batch's rays and samples) waits for this event
-    // instead of for the whole call
-    if (input_grad_event != nullptr && hipEventRecord((hipEvent_t)input_grad_event, st) != hipSuccess) {
-        lnr_set_error("lnr_density_backward: hipEventRecord failed");
-        return LNR_ERR_LAUNCH;
-    }
-    if (!want_grad) return LNR_OK;       // frozen parameters: no table reduce, no weight-gradient fold
+    rc = input_grad_done();
+    if (rc || !want_grad) return rc;       // frozen parameters: no table reduce, no weight-gradient fold
     if (want_dfeat) {
         if (hash && (flags & LNR_BWD_REPORT_REGIONS)) {           // diagnostic, call-time flag: synchronises the stream
             int64_t live = cap;
@@ -946,24 +565,17 @@ extern "C" int lnr_density_backward(const LnrNetSpec* spec, const float* params,
         }
     }
     if (hash && L.nown > 0) {          // also with cap_rec == 0 (all-atomic test path): it folds in the overflow accumulators
-        rc = launch_table_reduce(rctx, L.nown, st);
+        rc = lnr_launch_table_reduce(spec, sink, L.nown, (flags & LNR_BWD_TABLE_ATOMICS) ? 0 : L.n_split, fold_in_reduce ? fold : SlabFold{}, overwrite, st);
         if (rc) return rc;
         LNR_CHECK_LAUNCH("lnr_density_backward(table reduce)");
         ws_backward_done(workspace);                  // the reduce has put every accumulator it read back to zero
 #ifdef LNR_PHASE_TIMING
-        if (getenv("LNR_PHASE_TIMING")) {
-            static const char* names[LNR_N_PHASES] = {"zero LDS", "overflow fold", "-", "records", "-", "final barrier", "write-out"};
-            unsigned long long h[LNR_N_PHASES];
-            if (lnr_phase_fetch(HIP_SYMBOL(lnr_reduce_phase_cycles), h, LNR_N_PHASES, st)) lnr_phase_print("table_grad_reduce", names, h);
-        }
+        lnr_table_reduce_print_phases(st);
 #endif
     }
     // (folding the slabs right after the MLP backward instead was measured: +15 us in front of the encode backward, nothing gained)
     if ((flags & LNR_BWD_DEFER_WEIGHT_FOLD) || fold_in_reduce) return LNR_OK;      // the caller folds them (lnr_density_fold_weight_grads) / done above
-    const int n_mlp = spec->n_mlp_params;
-    LnrProfScope prof_slabs("reduce_slabs", st);
-    hipLaunchKernelGGL(reduce_slabs_kernel, dim3(lnr_div_up(n_mlp, 64)), dim3(64 * LNR_SLAB_GROUPS), 0, st, slabs, route.n_slabs, n_mlp, grad_params,
-                       (flags & LNR_BWD_OVERWRITE_GRAD) ? 1 : 0);
+    lnr_launch_slab_fold(fold, overwrite, st);
     LNR_CHECK_LAUNCH("lnr_density_backward(reduce)");
     return LNR_OK;
 }
@@ -973,15 +585,12 @@ extern "C" int lnr_density_fold_weight_grads(const LnrNetSpec* spec, int64_t n_p
     int rc = check_spec(spec, "lnr_density_fold_weight_grads");
     if (rc) return rc;
     LNR_REQUIRE(grad_params && workspace && n_points > 0, "lnr_density_fold_weight_grads: bad argument");
-    const DensityRoute route = lnr_route(spec, n_points, true);          // the route of the backward whose slabs these are
-    const Layout L = make_layout(spec, n_points, route);
-    LNR_REQUIRE(workspace_bytes >= L.total, "lnr_density_fold_weight_grads: workspace too small");
-    if (route.kind == LNR_ROUTE_UNSUPPORTED) return route_unsupported(spec, route, "lnr_density_fold_weight_grads");
-    const int n_mlp = spec->n_mlp_params;
-    hipStream_t st = (hipStream_t)stream;
-    LnrProfScope prof_slabs("reduce_slabs", st);
-    hipLaunchKernelGGL(reduce_slabs_kernel, dim3(lnr_div_up(n_mlp, 64)), dim3(64 * LNR_SLAB_GROUPS), 0, st,
-                       (const float*)((const char*)workspace + L.off_slabs), route.n_slabs, n_mlp, grad_params, (flags & LNR_BWD_OVERWRITE_GRAD) ? 1 : 0);
+    CallHead h;
+    h.cap = n_points;
+    rc = head_plan(spec, HEAD_FOLD, workspace_bytes, "lnr_density_fold_weight_grads", &h);
+    if (rc) return rc;
+    lnr_launch_slab_fold(SlabFold{(const float*)((const char*)workspace + h.L.off_slabs), h.route.n_slabs, spec->n_mlp_params, grad_params},
+                         (flags & LNR_BWD_OVERWRITE_GRAD) ? 1 : 0, (hipStream_t)stream);
     LNR_CHECK_LAUNCH("lnr_density_fold_weight_grads");
     return LNR_OK;
 }

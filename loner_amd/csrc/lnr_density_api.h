@@ -1,5 +1,7 @@
-// Internal interface between the density host dispatcher (lnr_density.hip) and the per-width kernel
-// translation units (lnr_density_ht.hip compiled with -DLNR_HT=1|2|4|8|16).
+// Internal interface of the density network: what the host dispatcher (lnr_density.hip: workspace layout, route, the C entry points)
+// shares with the translation units it calls - the MLP kernel families (lnr_density_ht.hip per width, lnr_density_regs.hip,
+// lnr_density_f16*.hip, lnr_density_bf3.hip, lnr_density_wide.hip), the level-major encoding (lnr_encode.hip) and the table-gradient
+// reduce with the weight-gradient fold (lnr_table_reduce.hip) - and the record formats the last two exchange.
 #pragma once
 #include "lnr_common.h"
 
@@ -212,6 +214,26 @@ struct RegionPlan {
     uint8_t binned[LNR_MAX_LEVELS];     // 1: partitioned by encode_backward_binned_kernel (fixed LDS bin per owner, whole-line appends)
 };
 
+#define LNR_ENC_MAX_BPG 2048        // most batches-per-group (chunks) of an encode launch, forward or backward
+static inline int lnr_level_span(const LnrNetSpec* s, int l, int shift) {          // owner slices (1 << shift floats each) level l's floats [lo, hi) touch
+    const uint64_t lo = (uint64_t)s->level_offset[l] * s->n_features, hi = lo + (uint64_t)s->level_size[l] * s->n_features;
+    return (int)(((hi - 1) >> shift) - (lo >> shift)) + 1;
+}
+
+// Where ONE backward's table gradient goes (host side): lnr_density_backward fills it once, after the flags LNR_BWD_TABLE_ATOMICS and
+// LNR_BWD_BINS have edited the plan; the encode backward writes records and overflow sums through it (it fills its kernels' EncSink
+// from it) and the reduce reads them back through it.  regions == grad_table == NULL: parameters frozen, no records.
+struct TableGradSink {
+    float* grad_table;
+    void* regions; RegionPlan plan; int* counts;      // record regions as laid out by `plan`, and their counts [level][maxo][bpg]
+    int bpg, maxo, shift;                             // chunks per level, the widest level's owner span, LNR_SLICE_SHIFT
+    long long* ovf; int* ovf_flag; int epoch;         // overflow accumulators, their per-level status words and this call's stamp
+};
+// the input-gradient outputs of the encode backward: d/dx planes -> d_pts, or per-ray sums (ray_acc) -> d_rays; both NULL: none
+struct InputGradOut { float* dxl; float* d_pts; float* d_rays; long long* ray_acc; };
+// the MLP backward's weight-gradient slabs and where their sum goes (slabs == NULL: nothing to fold)
+struct SlabFold { const float* slabs; int n_slabs, n_mlp; float* grad; };
+
 // level-major encoding (lnr_encode.hip)
 int lnr_encode_forward(const LnrNetSpec* spec, const float* params, const PointSrc* src, int64_t cap_points, float* feat,
                        int64_t m_pad, bool half_planes, hipStream_t st);
@@ -236,7 +258,12 @@ bool lnr_wide_class(const LnrNetSpec* spec);
 size_t lnr_wide_workspace(const LnrNetSpec* spec, int64_t n_points);     // bytes of chunk planes for calls of up to n_points points
 int lnr_mlp_fwd_wide(const MlpArgs& a);
 int lnr_mlp_bwd_wide(const MlpArgs& a);
-int lnr_encode_backward(const LnrNetSpec* spec, const float* params, const PointSrc* src, int64_t cap_points, const float* dfeat,
-                        float* dxl, int64_t m_pad, float* grad_table, void* regions, const RegionPlan* plan, int* counts, int bpg,
-                        int maxo, int shift, long long* ovf, int* ovf_flag, int epoch, float* d_pts, float* d_rays_acc, long long* ray_acc, bool bins_w8,
-                        hipStream_t st);
+int lnr_encode_backward(const LnrNetSpec* spec, const float* params, const PointSrc* src, int64_t cap_points, const float* dfeat, int64_t m_pad,
+                        const TableGradSink& sink, const InputGradOut& out, bool bins_w8, hipStream_t st);
+// lnr_table_reduce.hip: grad_table += the records and overflow sums of `sink` (n_owners reduce workgroups + n_split for the split levels);
+// fold.slabs != NULL: the weight-gradient fold rides in the same launch.  overwrite (LNR_BWD_OVERWRITE_GRAD): store instead of add
+int lnr_launch_table_reduce(const LnrNetSpec* spec, const TableGradSink& sink, int n_owners, int n_split, const SlabFold& fold, int overwrite, hipStream_t st);
+void lnr_launch_slab_fold(const SlabFold& fold, int overwrite, hipStream_t st);
+#ifdef LNR_PHASE_TIMING
+void lnr_table_reduce_print_phases(hipStream_t st);
+#endif

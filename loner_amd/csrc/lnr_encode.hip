@@ -12,7 +12,7 @@
 //
 // Backward: one thread per (sample, level) re-derives the cell, turns d_feature into table-gradient records
 // (run-length combined over consecutive samples of a ray on coarse levels), and writes its contribution to d/dx as
-// one plane per level; records are reduced by table_grad_reduce2_kernel (lnr_density.hip).
+// one plane per level; records are reduced by table_grad_reduce2_kernel (lnr_table_reduce.hip).
 #include "lnr_encoding.h"
 #include <cstdio>
 #include <cstdlib>
@@ -338,7 +338,7 @@ freq_forward_h16_kernel(const LnrNetSpec spec, const PointSrc src, uint32_t* __r
 // Instead each workgroup radix-partitions the records of a batch of 256 samples by owner slice IN LDS (histogram ->
 // scan -> scatter into a staging buffer) and then copies the staging buffer out linearly: records of one owner are
 // contiguous both in LDS and in that owner's (workgroup, owner) region in HBM, so the stores coalesce into full lines.
-// table_grad_reduce2_kernel (lnr_density.hip) sums each owner's regions in LDS.
+// table_grad_reduce2_kernel (lnr_table_reduce.hip) sums each owner's regions in LDS.
 struct EncSink {
     float* grad_table;      // fallback target for records beyond a region's capacity (float atomics) ...
     long long* ovf;         // the levels' 64-bit overflow accumulators (LevelList::slab_off)
@@ -1202,7 +1202,7 @@ int lnr_encode_forward(const LnrNetSpec* spec, const float* params, const PointS
     const int n_groups = hash ? spec->n_levels : (spec->enc_dim + 3) / 4;
     int64_t bpg = (cap_points + ENC_BLOCK * 4 - 1) / (ENC_BLOCK * 4);      // ~4 samples per thread
     if (bpg < 1) bpg = 1;
-    if (bpg > 2048) bpg = 2048;
+    if (bpg > LNR_ENC_MAX_BPG) bpg = LNR_ENC_MAX_BPG;
     const dim3 grid((unsigned)(n_groups * bpg)), block(ENC_BLOCK);
     if (!hash) {
         if (half_planes) {
@@ -1238,12 +1238,43 @@ int lnr_encode_forward(const LnrNetSpec* spec, const float* params, const PointS
     return LNR_OK;
 }
 
-int lnr_encode_backward(const LnrNetSpec* spec, const float* params, const PointSrc* src, int64_t cap_points, const float* dfeat,
-                        float* dxl, int64_t m_pad, float* grad_table, void* regions, const RegionPlan* plan, int* counts, int bpg,
-                        int maxo, int shift, long long* ovf, int* ovf_flag, int epoch, float* d_pts, float* d_rays_acc, long long* ray_acc, bool bins_w8,
-                        hipStream_t st) {
+// THE table of the encode-backward kernels: (partition, n_features, d/dx mode, x-pair records, waves of a binned workgroup) -> kernel.
+// 39 entries: the scan partition for F = 1, 2, 4, 8 and the x-pair form of F = 2, in the three d/dx modes (15); the binned partition
+// for F = 2, 4, 8 and the x-pair form, in the three modes, with 4 or 8 waves (24).  tests/test_gpu_encode_routes.py launches each.
+template <class K>
+static const void* pick_dxm(int dxm, K rays, K planes, K none) { return (const void*)(dxm == ENC_DX_RAYS ? rays : (dxm == ENC_DX_PLANES ? planes : none)); }
+template <int F, bool XP, int NW>
+static const void* binned_fn(int dxm) {
+    return pick_dxm(dxm, encode_backward_binned_kernel<F, ENC_DX_RAYS, XP, NW>, encode_backward_binned_kernel<F, ENC_DX_PLANES, XP, NW>, encode_backward_binned_kernel<F, ENC_DX_NONE, XP, NW>);
+}
+template <int F, bool XP>
+static const void* partition_fn(bool binned, int dxm, int nw) {
+    if constexpr (F >= 2) { if (binned) return nw == 8 ? binned_fn<F, XP, 8>(dxm) : binned_fn<F, XP, 4>(dxm); }          // (binned records are pair records)
+    return pick_dxm(dxm, encode_backward_kernel<F, ENC_DX_RAYS, XP>, encode_backward_kernel<F, ENC_DX_PLANES, XP>, encode_backward_kernel<F, ENC_DX_NONE, XP>);
+}
+static const void* encode_backward_fn(bool binned, int n_features, int dxm, bool xp, int nw) {
+    if (xp) return partition_fn<2, true>(binned, dxm, nw);
+    return n_features == 1 ? partition_fn<1, false>(binned, dxm, nw) : n_features == 2 ? partition_fn<2, false>(binned, dxm, nw)
+         : n_features == 4 ? partition_fn<4, false>(binned, dxm, nw) : partition_fn<8, false>(binned, dxm, nw);
+}
+// a launch with `lds` bytes of dynamic LDS; fail: the text of a failed launch (NULL: LNR_CHECK_LAUNCH's, for `what`)
+static int launch_with_lds(const void* fn, dim3 grid, dim3 block, size_t lds, void** args, hipStream_t st, const char* fail, const char* what) {
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+        lnr_set_error("lnr_density_backward: hipFuncSetAttribute(%zu) failed", lds); return LNR_ERR_LAUNCH;
+    }
+    const hipError_t e = hipLaunchKernel(fn, grid, block, args, lds, st);
+    if (e == hipSuccess) return LNR_OK;
+    if (fail != nullptr) lnr_set_error("%s", fail);
+    else { (void)hipGetLastError(); lnr_set_error("%s: launch failed: %s", what, hipGetErrorString(e)); }
+    return LNR_ERR_LAUNCH;
+}
+
+int lnr_encode_backward(const LnrNetSpec* spec, const float* params, const PointSrc* src, int64_t cap_points, const float* dfeat, int64_t m_pad,
+                        const TableGradSink& to, const InputGradOut& out, bool bins_w8, hipStream_t st) {
     const float* table = params + spec->n_mlp_params;
     const bool hash = spec->encoding == LNR_ENC_HASHGRID;
+    float* const dxl = out.dxl; float* const d_pts = out.d_pts; float* const d_rays_acc = out.d_rays; long long* const ray_acc = out.ray_acc;
+    int bpg = to.bpg;
     // d/dx mode: d_rays_acc (rays form, n_samples % 64 == 0, checked by the caller) > d_pts (planes) > none
     const int dxm = d_rays_acc ? ENC_DX_RAYS : (d_pts ? ENC_DX_PLANES : ENC_DX_NONE);
     float* dx_out = d_rays_acc ? reinterpret_cast<float*>(ray_acc) : dxl;
@@ -1252,94 +1283,42 @@ int lnr_encode_backward(const LnrNetSpec* spec, const float* params, const Point
         lnr_set_error("lnr_density_backward: hipMemsetAsync failed");
         return LNR_ERR_LAUNCH;
     }
-    int n_groups = 1;
-    if (hash) n_groups = spec->n_levels;
-    if (hash && (regions != nullptr || dxm != ENC_DX_NONE)) {
+    const int n_groups = hash ? spec->n_levels : 1;
+    if (hash && (to.regions != nullptr || dxm != ENC_DX_NONE)) {
         LevelList rec_levels, xp_levels, brec_levels, bxp_levels;          // 8-byte record levels, x-pair record levels, and their binned forms: one launch each
         rec_levels.n = xp_levels.n = brec_levels.n = bxp_levels.n = 0;
-        const bool allow_binned = regions != nullptr && maxo <= LNR_BIN_MAX_OWNERS;
+        const bool allow_binned = to.regions != nullptr && to.maxo <= LNR_BIN_MAX_OWNERS;
         int ovf_total = 0;
         for (int l = 0; l < spec->n_levels; ++l) {
             const int nfl = (int)spec->level_size[l] * spec->n_features;
-            const bool is_xp = spec->n_features == 2 && plan->xp[l] != 0;
-            const bool is_binned = allow_binned && plan->binned[l] != 0 && plan->bytes[l] != 0;
+            const bool is_xp = spec->n_features == 2 && to.plan.xp[l] != 0;
+            const bool is_binned = allow_binned && to.plan.binned[l] != 0 && to.plan.bytes[l] != 0;
             LevelList& ll = is_xp ? (is_binned ? bxp_levels : xp_levels) : (is_binned ? brec_levels : rec_levels);
             ll.lv[ll.n] = l; ll.slab_off[ll.n] = ovf_total; ll.n++;
             ovf_total += nfl;
         }
-        const dim3 block(ENC_BWD_BLOCK);
-#define LNR_LAUNCH_DXM(KERNEL, F, XP, ...)                                                                                    \
-        do {                                                                                                                  \
-            hipError_t e_ = hipSuccess;                                                                                       \
-            const void* fn_ = dxm == ENC_DX_RAYS ? reinterpret_cast<const void*>(KERNEL<F, ENC_DX_RAYS, XP>)                  \
-                            : dxm == ENC_DX_PLANES ? reinterpret_cast<const void*>(KERNEL<F, ENC_DX_PLANES, XP>)              \
-                                                   : reinterpret_cast<const void*>(KERNEL<F, ENC_DX_NONE, XP>);               \
-            e_ = hipFuncSetAttribute(fn_, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                              \
-            if (e_ != hipSuccess) { lnr_set_error("lnr_density_backward: hipFuncSetAttribute(%zu) failed", lds); return LNR_ERR_LAUNCH; } \
-            if (dxm == ENC_DX_RAYS) hipLaunchKernelGGL((KERNEL<F, ENC_DX_RAYS, XP>), grid, block, lds, st, __VA_ARGS__);   \
-            else if (dxm == ENC_DX_PLANES) hipLaunchKernelGGL((KERNEL<F, ENC_DX_PLANES, XP>), grid, block, lds, st, __VA_ARGS__); \
-            else hipLaunchKernelGGL((KERNEL<F, ENC_DX_NONE, XP>), grid, block, lds, st, __VA_ARGS__);                      \
-        } while (0)
-#define LNR_LAUNCH_F(KERNEL, ...)                                                   \
-        switch (spec->n_features) {                                                 \
-            case 1: LNR_LAUNCH_DXM(KERNEL, 1, false, __VA_ARGS__); break;           \
-            case 2: LNR_LAUNCH_DXM(KERNEL, 2, false, __VA_ARGS__); break;           \
-            case 4: LNR_LAUNCH_DXM(KERNEL, 4, false, __VA_ARGS__); break;           \
-            default: LNR_LAUNCH_DXM(KERNEL, 8, false, __VA_ARGS__); break;          \
-        }
         if (rec_levels.n + xp_levels.n + brec_levels.n + bxp_levels.n > 0) {
-            EncSink sink;
             // (the overflow accumulators are all-zero here: lnr_density_backward keeps them so between calls, lnr_density.hip)
-            sink.ovf_flag = ovf_flag; sink.epoch = epoch;
-            sink.grad_table = grad_table; sink.ovf = ovf; sink.regions = regions; sink.plan = *plan; sink.counts = counts; sink.maxo = maxo; sink.shift = shift;
-            sink.combine_scale_max = LNR_COMBINE_SCALE_MAX;
+            EncSink sink{to.grad_table, to.ovf, to.regions, to.plan, to.counts, to.maxo, to.shift, 0, to.ovf_flag, to.epoch, LNR_COMBINE_SCALE_MAX};
             LnrProfScope prof("encode_backward", st);
-            const int maxo4 = (maxo + 3) & ~3;
-            const size_t lds = (size_t)(2 * maxo4 + 4 * maxo) * sizeof(int) + (size_t)ENC_STAGE_RECORDS * (spec->n_features >= 2 ? 16 : 8);
-            if (rec_levels.n > 0) {
-                const dim3 grid((unsigned)(rec_levels.n * bpg));
-                sink.xcd_affine = lnr_xcd_affine(rec_levels.n, cap_points, false) ? 1 : 0;
-                LNR_LAUNCH_F(encode_backward_kernel, *spec, table, *src, dfeat, dx_out, m_pad, bpg, rec_levels, sink);
-            }
-            if (xp_levels.n > 0) {                                          // n_features == 2
-                const dim3 grid((unsigned)(xp_levels.n * bpg));
-                sink.xcd_affine = lnr_xcd_affine(xp_levels.n, cap_points, false) ? 1 : 0;
-                LNR_LAUNCH_DXM(encode_backward_kernel, 2, true, *spec, table, *src, dfeat, dx_out, m_pad, bpg, xp_levels, sink);
-            }
-            {
-                // binned partition: NW = 4 (256-thread workgroups, 512-byte bins) or 8 (512 threads, 1 KB bins)
-                const int nw = bins_w8 ? 8 : 4;
-                const size_t lds_b = 64 * sizeof(int) + (size_t)LNR_BIN_MAX_OWNERS * (size_t)(128 * nw);
-                const dim3 block_b(64 * nw);
-#define LNR_LAUNCH_BINNED(F, XP, LIST)                                                                                              \
-                do {                                                                                                                \
-                    const dim3 grid_b((unsigned)((LIST).n * bpg));                                                                  \
-                    sink.xcd_affine = lnr_xcd_affine((LIST).n, cap_points, false) ? 1 : 0;                                                             \
-                    const void* fn_ = nullptr;                                                                                      \
-                    if (nw == 8) fn_ = dxm == ENC_DX_RAYS ? (const void*)encode_backward_binned_kernel<F, ENC_DX_RAYS, XP, 8>       \
-                                     : dxm == ENC_DX_PLANES ? (const void*)encode_backward_binned_kernel<F, ENC_DX_PLANES, XP, 8>   \
-                                                            : (const void*)encode_backward_binned_kernel<F, ENC_DX_NONE, XP, 8>;    \
-                    else fn_ = dxm == ENC_DX_RAYS ? (const void*)encode_backward_binned_kernel<F, ENC_DX_RAYS, XP, 4>               \
-                             : dxm == ENC_DX_PLANES ? (const void*)encode_backward_binned_kernel<F, ENC_DX_PLANES, XP, 4>           \
-                                                    : (const void*)encode_backward_binned_kernel<F, ENC_DX_NONE, XP, 4>;            \
-                    if (hipFuncSetAttribute(fn_, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b) != hipSuccess) {           \
-                        lnr_set_error("lnr_density_backward: hipFuncSetAttribute(%zu) failed", lds_b); return LNR_ERR_LAUNCH;       \
-                    }                                                                                                               \
-                    void* args_[] = {(void*)spec, (void*)&table, (void*)src, (void*)&dfeat, (void*)&dx_out, (void*)&m_pad, (void*)&bpg, (void*)&(LIST), (void*)&sink}; \
-                    if (hipLaunchKernel(fn_, grid_b, block_b, args_, lds_b, st) != hipSuccess) {                                    \
-                        lnr_set_error("lnr_density_backward: launch of the binned partition failed"); return LNR_ERR_LAUNCH;         \
-                    }                                                                                                               \
-                } while (0)
-                if (brec_levels.n > 0) {
-                    switch (spec->n_features) {
-                        case 2: LNR_LAUNCH_BINNED(2, false, brec_levels); break;
-                        case 4: LNR_LAUNCH_BINNED(4, false, brec_levels); break;
-                        default: LNR_LAUNCH_BINNED(8, false, brec_levels); break;
-                    }
-                }
-                if (bxp_levels.n > 0) LNR_LAUNCH_BINNED(2, true, bxp_levels);
-#undef LNR_LAUNCH_BINNED
-            }
+            const int maxo4 = (to.maxo + 3) & ~3;
+            const size_t lds_scan = (size_t)(2 * maxo4 + 4 * to.maxo) * sizeof(int) + (size_t)ENC_STAGE_RECORDS * (spec->n_features >= 2 ? 16 : 8);
+            // binned partition: NW = 4 (256-thread workgroups, 512-byte bins) or 8 (512 threads, 1 KB bins)
+            const int nw = bins_w8 ? 8 : 4;
+            const size_t lds_binned = 64 * sizeof(int) + (size_t)LNR_BIN_MAX_OWNERS * (size_t)(128 * nw);
+            auto launch = [&](LevelList& list, bool xp, bool binned) -> int {          // one launch for the levels of `list`
+                if (list.n == 0) return LNR_OK;
+                sink.xcd_affine = lnr_xcd_affine(list.n, cap_points, false) ? 1 : 0;
+                void* args[] = {(void*)spec, (void*)&table, (void*)src, (void*)&dfeat, (void*)&dx_out, (void*)&m_pad, (void*)&bpg, (void*)&list, (void*)&sink};
+                return launch_with_lds(encode_backward_fn(binned, spec->n_features, dxm, xp, nw), dim3((unsigned)(list.n * bpg)), dim3(binned ? 64 * nw : ENC_BWD_BLOCK),
+                                       binned ? lds_binned : lds_scan, args, st, binned ? "lnr_density_backward: launch of the binned partition failed" : nullptr,
+                                       "lnr_density_backward(encode backward)");
+            };
+            int rc = launch(rec_levels, false, false);
+            if (!rc) rc = launch(xp_levels, true, false);                   // n_features == 2
+            if (!rc) rc = launch(brec_levels, false, true);
+            if (!rc) rc = launch(bxp_levels, true, true);
+            if (rc) return rc;
 #ifdef LNR_PHASE_TIMING
             if (getenv("LNR_PHASE_TIMING")) {
                 static const char* names[LNR_N_PHASES] = {"load inputs", "cell/entries/gather/weights", "A rank", "barrier 1", "B scan", "barrier 2",
@@ -1352,8 +1331,6 @@ int lnr_encode_backward(const LnrNetSpec* spec, const float* params, const Point
             }
 #endif
         }
-#undef LNR_LAUNCH_F
-#undef LNR_LAUNCH_DXM
     } else if (!hash && dxm != ENC_DX_NONE) {
         // frequency encoding: no table, one plane group; the per-ray mode is served through the planes by the caller
         int64_t blocks = (cap_points + ENC_BLOCK - 1) / ENC_BLOCK;
