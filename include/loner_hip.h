@@ -76,8 +76,6 @@ typedef enum LnrPosRounding { LNR_POS_FMA = 0, LNR_POS_MUL_ADD = 1 } LnrPosRound
 
 /* lnr_density_backward flags */
 #define LNR_BWD_TABLE_ATOMICS 1   /* test hook: every table-gradient record goes to the 64-bit overflow accumulators (atomics) */
-#define LNR_BWD_BINS 4            /* hashed levels take the binned partition (whole-line appends; same sums, measured ~3 % slower than the scan partition: DESIGN.md section 8) */
-#define LNR_BWD_BINS_W8 8         /* A-B hook: the binned partition with 512-thread workgroups / 1 KB bins instead of 256 / 512 bytes */
 #define LNR_BWD_DEFER_WEIGHT_FOLD 16 /* leave the per-workgroup weight-gradient slabs in the workspace: the caller adds them to grad_params
                                        with lnr_density_fold_weight_grads (same points capacity) - e.g. on another stream, beside the
                                        table-gradient reduce, instead of behind it */

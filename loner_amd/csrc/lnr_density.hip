@@ -107,7 +107,7 @@ static Layout make_layout(const LnrNetSpec* spec, int64_t n_points, const Densit
     L.maxo = 1;
     size_t ovf_total = 0;
     uint64_t region_total = 0;
-    for (int l = 0; l < LNR_MAX_LEVELS; ++l) { L.plan.off[l] = 0; L.plan.bytes[l] = 0; L.plan.xp[l] = 0; L.plan.split[l] = 1; L.plan.binned[l] = 0; }
+    for (int l = 0; l < LNR_MAX_LEVELS; ++l) { L.plan.off[l] = 0; L.plan.bytes[l] = 0; L.plan.xp[l] = 0; L.plan.split[l] = 1; }
     L.n_split = 0;
     if (hash) {
         const int F = spec->n_features;
@@ -129,13 +129,6 @@ static Layout make_layout(const LnrNetSpec* spec, int64_t n_points, const Densit
                 // so the capacity is generous (sweep in DESIGN.md 2; the reduce does not care how full a region is)
                 const double recs = (r * (xp ? LNR_REGION_HEADROOM_XP : LNR_REGION_HEADROOM) + LNR_REGION_SLACK) * shrink;
                 uint64_t bytes = (uint64_t)(recs * (xp ? 12.0 : 8.0));
-                // Binned partition (lnr_encode.hip): hashed levels, whose records spread evenly over the owners - a batch (one sample per
-                // thread) must be expected to fill at most half a bin, worst case (nothing dead, nothing combined)
-                const double bin_fill = (double)LNR_ENC_BWD_BLOCK * 8.0 * (xp ? 0.5 * 12.0 : 8.0) / (double)span;
-                const bool binned = F >= 2 && spec->level_hashed[l] != 0 && span <= LNR_BIN_MAX_OWNERS && bin_fill <= 0.5 * LNR_BIN_BYTES + 8.0 &&
-                                    LNR_ENC_BWD_BLOCK == 512 && shrink == 1.0;
-                L.plan.binned[l] = binned ? 1 : 0;
-                if (binned) bytes += LNR_BIN_BYTES + 128;
                 bytes = (bytes + 255u) & ~(uint64_t)255u;
                 // spatially coherent (dense-indexed) levels: several reduce workgroups per owner (table_grad_reduce_split_kernel)
                 int parts = spec->level_hashed[l] == 0 ? LNR_REDUCE_SPLIT : 1;
@@ -490,8 +483,6 @@ extern "C" int lnr_density_backward(const LnrNetSpec* spec, const float* params,
     RegionPlan rplan = L.plan;
     if (flags & LNR_BWD_TABLE_ATOMICS)                       // no room anywhere: every record takes the overflow path
         for (int l = 0; l < LNR_MAX_LEVELS; ++l) rplan.bytes[l] = 0;
-    if (!(flags & LNR_BWD_BINS))
-        for (int l = 0; l < LNR_MAX_LEVELS; ++l) rplan.binned[l] = 0;
     const bool want_grad = grad_params != nullptr;
 
     const bool fused_freq = route.fused_enc;          // encoding and its input gradient inside the MLP backward kernel
@@ -546,7 +537,7 @@ extern "C" int lnr_density_backward(const LnrNetSpec* spec, const float* params,
     const int overwrite = (flags & LNR_BWD_OVERWRITE_GRAD) ? 1 : 0;
     if (want_dfeat && !fused_freq) {
         const InputGradOut out{dxl, d_pts_eff, ray_accum ? d_rays : nullptr, (long long*)(ws + L.off_rayacc)};
-        rc = lnr_encode_backward(spec, params, &src, cap, dfeat, L.m_pad, sink, out, (flags & LNR_BWD_BINS_W8) != 0, st);
+        rc = lnr_encode_backward(spec, params, &src, cap, dfeat, L.m_pad, sink, out, st);
         if (rc) return rc;
         LNR_CHECK_LAUNCH("lnr_density_backward(encode backward)");
     }

@@ -41,8 +41,6 @@ struct PointSrc {
 #endif
 #define LNR_REDUCE_SPLIT 32         // reduce workgroups per owner of a dense-indexed record level
 #define LNR_FIX_SCALE 4398046511104.0f /* 2^42: LDS gradient accumulators are 64-bit fixed point */
-#define LNR_BIN_BYTES 1024            /* LDS bin of one owner in the binned partition (lnr_encode.hip) */
-#define LNR_BIN_MAX_OWNERS 64         /* 64 bins = 64 KB of LDS: two workgroups per CU */
 #ifndef LNR_XPAIR_SCALE_MIN
 #define LNR_XPAIR_SCALE_MIN 3000.0f   /* hashed power-of-two levels at least this fine take x-pair records (below: run-length combined 8-byte records) */
 #endif
@@ -195,23 +193,21 @@ struct LevelList {
     int slab_off[LNR_MAX_LEVELS];   // offset of the level's 64-bit overflow accumulators (see below)
 };
 // Every record level has 64-bit fixed-point overflow accumulators in the workspace (one per table float of the level): a
-// record that does not fit its staging bin or its region is added there (integer atomics: exact, order-independent) with
-// the same 26-bit rounding as a packed record, and the reduce folds the accumulators into the same fixed-point sum - so the
+// record that does not fit its region is added there (integer atomics: exact, order-independent) with the
+// same 26-bit rounding as a packed record, and the reduce folds the accumulators into the same fixed-point sum - so the
 // table gradient does not depend on which records happened to overflow.  Levels with dense (non-hashed) indexing overflow
 // routinely (they are spatially coherent: an owner slice is a slab of cells and a ray pours into a few of them), hashed
 // levels only by statistical accident.
 
 // Record regions, sized per level: [owner of the level][chunk (= encode-backward workgroup)] x bytes[l], back to back from off[l].
-// A region holds twice the level's expected records per (owner, chunk) plus 64 (LNR_REGION_HEADROOM / _SLACK; binned levels: plus
-// one bin and a line, the room a region must have left to stay open), in that level's record format (8-byte pair records, 12-byte
-// x-pair records), in 256-byte units.  The reduce reads only the records a region holds (its count), so capacity costs memory -
+// A region holds twice the level's expected records per (owner, chunk) plus 64 (LNR_REGION_HEADROOM / _SLACK), in that level's
+// record format (8-byte pair records, 12-byte x-pair records), in 256-byte units.  The reduce reads only the records a region holds (its count), so capacity costs memory -
 // several GB at the bench shape, lnr_density_workspace reports it - not bandwidth.
 struct RegionPlan {
     uint64_t off[LNR_MAX_LEVELS];       // byte offset of the level's regions
     uint32_t bytes[LNR_MAX_LEVELS];     // bytes per region (multiple of 16); 0: all records overflow (LNR_BWD_TABLE_ATOMICS)
     uint8_t xp[LNR_MAX_LEVELS];         // 1: the level's records are 12-byte x-pair records, 0: 8-byte records
     uint8_t split[LNR_MAX_LEVELS];      // > 1: the level's owners are reduced by this many workgroups each (table_grad_reduce_split_kernel)
-    uint8_t binned[LNR_MAX_LEVELS];     // 1: partitioned by encode_backward_binned_kernel (fixed LDS bin per owner, whole-line appends)
 };
 
 #define LNR_ENC_MAX_BPG 2048        // most batches-per-group (chunks) of an encode launch, forward or backward
@@ -220,8 +216,8 @@ static inline int lnr_level_span(const LnrNetSpec* s, int l, int shift) {       
     return (int)(((hi - 1) >> shift) - (lo >> shift)) + 1;
 }
 
-// Where ONE backward's table gradient goes (host side): lnr_density_backward fills it once, after the flags LNR_BWD_TABLE_ATOMICS and
-// LNR_BWD_BINS have edited the plan; the encode backward writes records and overflow sums through it (it fills its kernels' EncSink
+// Where ONE backward's table gradient goes (host side): lnr_density_backward fills it once, after the flag LNR_BWD_TABLE_ATOMICS
+// has edited the plan; the encode backward writes records and overflow sums through it (it fills its kernels' EncSink
 // from it) and the reduce reads them back through it.  regions == grad_table == NULL: parameters frozen, no records.
 struct TableGradSink {
     float* grad_table;
@@ -259,7 +255,7 @@ size_t lnr_wide_workspace(const LnrNetSpec* spec, int64_t n_points);     // byte
 int lnr_mlp_fwd_wide(const MlpArgs& a);
 int lnr_mlp_bwd_wide(const MlpArgs& a);
 int lnr_encode_backward(const LnrNetSpec* spec, const float* params, const PointSrc* src, int64_t cap_points, const float* dfeat, int64_t m_pad,
-                        const TableGradSink& sink, const InputGradOut& out, bool bins_w8, hipStream_t st);
+                        const TableGradSink& sink, const InputGradOut& out, hipStream_t st);
 // lnr_table_reduce.hip: grad_table += the records and overflow sums of `sink` (n_owners reduce workgroups + n_split for the split levels);
 // fold.slabs != NULL: the weight-gradient fold rides in the same launch.  overwrite (LNR_BWD_OVERWRITE_GRAD): store instead of add
 int lnr_launch_table_reduce(const LnrNetSpec* spec, const TableGradSink& sink, int n_owners, int n_split, const SlabFold& fold, int overwrite, hipStream_t st);

@@ -481,12 +481,6 @@ ray_grad_apply_kernel(const long long* __restrict__ ray_acc, int n_rays, const i
 }
 // (The input gradient as a kernel of its own, two lanes per sample, was measured slower than this fused form: docs/HISTORY.md 4.3.)
 
-__device__ __forceinline__ void store_stream_b128(uint64_t global_addr, uint4 v) {
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    const u32x4 q = {v.x, v.y, v.z, v.w};
-    asm volatile("global_store_dwordx4 %0, %1, off nt" :: "v"(global_addr), "v"(q) : "memory");
-}
-
 #define ENC_BWD_BLOCK LNR_ENC_BWD_BLOCK
 #define ENC_STAGE_RECORDS (ENC_BWD_BLOCK * 8)
 
@@ -848,303 +842,6 @@ encode_backward_kernel(const LnrNetSpec spec, const float* __restrict__ table, c
             sink.counts[region0 + i * region_step] = gcur[i] < cap_rec ? gcur[i] : cap_rec;
 }
 
-// ------------------------------------------------------------------------------------------------ binned partition
-// The same partition for HASHED levels, where the records of a batch spread evenly over the owners: every owner has a fixed BIN
-// of LDS, a record takes its place with one returning atomic on the bin's fill (no histogram pass, no scan, no OwnerSlot lookups:
-// two barriers per batch instead of three and no single-wave phase), and the bin IS the staging buffer - packed records, appended
-// in arrival order.  What leaves the workgroup is whole 128-byte lines: after the barrier wave w copies the full lines of its
-// eight owners' bins out (one ds_read_b128 + one global_store_dwordx4 per owner, region address and line count on the scalar
-// unit) and moves the unfinished line - the tail, < 128 bytes - to the front of the bin, where the next batch appends.  A region is
-// therefore a dense byte stream of records written line by line; only the last line of a region, flushed when the kernel ends, is
-// partial (round 2 measured the partial-line appends of the per-batch copy-out at 0.25-0.38 of 0.94 ms against 0.12 ms for the
-// same bytes as whole lines, and the per-owner bookkeeping of a first whole-line attempt as costlier than that gain: here the
-// bookkeeping is a lane-resident {position, tail} pair per owner and nothing is looked up per record).
-// A record that finds its bin full (BIN_BYTES covers > 5 sigma of a batch's records per owner plus the tail), or whose region is
-// closed (no room left for another worst-case batch), takes the overflow path with the rounding of a packed record, as before.
-#define ENC_BIN_BYTES LNR_BIN_BYTES
-#define ENC_BIN_CLOSED 0x40000000
-static_assert(LNR_BIN_BYTES == 64 * 16, "a wave copies a whole bin with one 16-byte load per lane");
-
-// NW = waves per workgroup (8: 512 threads, 1 KB bins; 4: 256 threads, 512-byte bins - twice as many independent barrier domains per CU
-// at the same LDS and wave count; a region only ever receives whole lines, so the batch size does not change what reaches HBM)
-template <int F, int DXM, bool XP, int NW>
-__global__ void __launch_bounds__(64 * NW, 4)
-encode_backward_binned_kernel(const LnrNetSpec spec, const float* __restrict__ table, const PointSrc src, const float* __restrict__ dfeat,
-                              float* __restrict__ dxl, int64_t m_pad, int bpg, const LevelList list, const EncSink sink) {
-    constexpr bool WANT_DX = DXM != ENC_DX_NONE;
-    static_assert(F >= 2, "binned records are pair records");
-    static_assert(NW == 8 || NW == 4, "8 waves x 8 owners or 4 waves x 16 owners");
-    constexpr int BLK = 64 * NW;                                  // threads = samples of a batch
-    constexpr int BIN = 128 * NW;                                 // bytes of an owner's bin: tail (< 128) + a batch's records with > 5 sigma to spare
-    constexpr int OPW = 64 / NW;                                  // owners served by a wave
-    constexpr int G = NW;                                         // lanes that hold the state of one owner (G x 128 / G bytes move its tail)
-    constexpr int LPB = BIN / 16;                                 // lanes that copy one bin (16 bytes each)
-    constexpr int BPI = 64 / LPB;                                 // bins per copy instruction
-    constexpr int TQ = 128 / G / 16;                              // 16-byte pieces of the tail per lane
-    extern __shared__ __attribute__((aligned(16))) int dyn[];
-    constexpr int NPASS = F / 2;
-    constexpr bool xp = XP && F == 2;
-    constexpr uint32_t REC = xp ? 12u : 8u;
-    int* fill = dyn;                                             // [64] bytes in the owner's bin (tail + this batch's records)
-    char* stage = reinterpret_cast<char*>(dyn + 64);             // [64][BIN]
-    const int maxo = sink.maxo;                                  // <= 64 (host)
-    int slot, chunk;
-    if (!level_slot(bpg, list.n, sink.xcd_affine != 0, slot, chunk)) return;          // (workgroup-uniform)
-    const int lv = list.lv[slot];
-    const LevelInfo L = level_info(spec, lv);
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t M = (uint32_t)live_points(src);
-    const int first_owner = (int)(((uint64_t)L.offset * F) >> sink.shift);
-    const bool combine = !xp && L.scale < sink.combine_scale_max;
-    const uint32_t region_bytes = sink.plan.bytes[lv];
-    char* level_regions = reinterpret_cast<char*>(sink.regions) + sink.plan.off[lv];
-    const int ovf_off = list.slab_off[slot];
-    long long* ovf = sink.ovf + ovf_off;
-    const uint32_t level_base = L.offset * F;
-    const size_t region0 = (size_t)lv * maxo * bpg + chunk;
-    const size_t region_step = (size_t)bpg;
-    const uint32_t step = (uint32_t)bpg * BLK;
-    const uint32_t n_iter = (M + step - 1u) / step;
-    const float* gplanes = dfeat + (size_t)(lv * F) * m_pad;
-    float* dxplanes = dxl + (size_t)(lv * 3) * m_pad;
-    const uint32_t plane_bytes = (uint32_t)m_pad * 4u;
-    const bool emit = sink.regions != nullptr;
-    // owner bookkeeping: lanes G k .. G k + G - 1 of wave w all hold the state of owner OPW w + k
-    const int my_owner = wave * OPW + lane / G;
-    const bool own = my_owner < maxo;
-    uint32_t gpos = 0u;                                           // bytes of the owner's region already written (multiple of 128)
-    uint32_t tail = 0u;                                           // bytes of the unfinished line at the front of the bin
-    // a region too small for one worst-case batch never opens (LNR_BWD_TABLE_ATOMICS: region_bytes == 0)
-    bool closed = !own || region_bytes < (uint32_t)(BIN + 128);
-    if (threadIdx.x < 64) fill[threadIdx.x] = 0;
-    __syncthreads();
-    if (lane % G == 0 && own && closed) fill[my_owner] = ENC_BIN_CLOSED;
-    __syncthreads();
-    if (M == 0u) {
-        if (emit) for (int i = threadIdx.x; i < maxo; i += BLK) sink.counts[region0 + i * region_step] = 0;
-        return;
-    }
-    constexpr bool EARLY_DX = WANT_DX && F <= 2;
-    SampleCursor cur;
-    cur.init((uint32_t)chunk * BLK + threadIdx.x, step, src.pts ? 1u : (uint32_t)src.n_samples);
-    const uint32_t last_ray = src.pts ? 0u : (M - 1u) / cur.S;
-    const bool uni = ray_uniform(src, 64u);          // (workgroups of 256 / 512 threads: a wave's 64 samples start at a multiple of 64)
-    float g_next[F];
-    RawPoint p_next;
-    {
-        const bool in = cur.m < M;
-        const uint32_t mc = in ? cur.m : M - 1u;
-#pragma unroll
-        for (int f = 0; f < F; ++f) g_next[f] = ld32_stream<float>(gplanes, (uint32_t)f * plane_bytes + mc * 4u);
-        load_raw_point(src, mc, in ? cur.ray : last_ray, p_next, uni);
-    }
-    for (uint32_t it = 0; it < n_iter; ++it) {
-        const uint32_t m = cur.m;
-        const bool live = m < M;
-        float g[F];
-        bool any = false;
-#pragma unroll
-        for (int f = 0; f < F; ++f) { g[f] = live ? g_next[f] : 0.0f; any |= (g[f] != 0.0f); }
-        const RawPoint p_cur = p_next;
-        const uint32_t ray_cur = cur.ray;
-        cur.advance();
-        {
-            const bool in = cur.m < M;
-            const uint32_t mc = in ? cur.m : M - 1u;
-#pragma unroll
-            for (int f = 0; f < F; ++f) g_next[f] = ld32_stream<float>(gplanes, (uint32_t)f * plane_bytes + mc * 4u);
-            load_raw_point(src, mc, in ? cur.ray : last_ray, p_next, uni);
-        }
-        const bool wave_any = __ballot(any) != 0ull;
-        Cell c;
-        uint32_t e[8];
-        float w[8];
-        bool head = true;
-        RunMask run = {false, false, false, false};
-        float tv[EARLY_DX ? 8 : 1][F];
-        if (wave_any) {
-            float x[3];
-            unit_point(src, p_cur, x);
-            c = cell_of(L, x);
-            cell_entries(L, c, e);
-            if constexpr (EARLY_DX) { if (any) gather_entries<F>(table, e, tv); }
-            cell_weights(c, w);
-            if (combine) cell_runs(c, lane, head, run);
-        }
-#pragma unroll
-        for (int pass = 0; pass < (emit ? NPASS : 0); ++pass) {
-            // ---- A: every record is packed and put into its owner's bin at the offset a returning atomic hands out.  All of a
-            // thread's atomics are issued before the first offset is used: one LDS round trip per batch instead of one per record
-            // (measured: the rank atomics cost 0.11 of the x-pair levels' 0.54 ms when each was waited for in turn).
-            constexpr uint32_t NO_SLOT = 0xFFFFFFFFu;
-            if (wave_any && xp) {
-                const uint32_t xt = xpair_trailing_ones(c.b[0]);
-                const float wy[2] = {1.0f - c.frac[1], c.frac[1]}, wz[2] = {1.0f - c.frac[2], c.frac[2]};
-                float a0[4], a1[4];
-                uint32_t at[4];
-#pragma unroll
-                for (int k2 = 0; k2 < 4; ++k2) {
-                    const float wyz = wy[k2 & 1] * wz[k2 >> 1];
-                    a0[k2] = wyz * g[0]; a1[k2] = wyz * g[1];
-                    at[k2] = NO_SLOT;
-                    if (((a0[k2] != 0.0f) | (a1[k2] != 0.0f)) & (xt < 12u)) {
-                        const int o = (int)((e[2 * k2] * F) >> LNR_SLICE_SHIFT) - first_owner;
-                        at[k2] = (uint32_t)atomicAdd(&fill[o], (int)REC);
-                    }
-                }
-#pragma unroll
-                for (int k2 = 0; k2 < 4; ++k2) {
-                    if ((a0[k2] != 0.0f) | (a1[k2] != 0.0f)) {
-                        const uint32_t fi = e[2 * k2] * F;
-                        if (at[k2] <= (uint32_t)BIN - REC) {
-                            const int o = (int)(fi >> LNR_SLICE_SHIFT) - first_owner;
-                            const LnrXRec rec = lnr_pack_xpair((fi & ((1u << LNR_SLICE_SHIFT) - 1u)) >> 1, xt, a0[k2], a1[k2], c.frac[0]);
-                            uint32_t* dst = reinterpret_cast<uint32_t*>(stage + (uint32_t)o * BIN + at[k2]);
-                            dst[0] = rec.a; dst[1] = rec.b; dst[2] = rec.c;
-                        } else {
-                            // bin full or region closed: same rounding as a packed record.  Corners that straddle owner slices (xt >= 12): as
-                            // the scan partition's two single-corner records (t = 0, fx = 0, the x weight applied here), so that the two
-                            // partitions agree to the bit
-                            if (xt < 12u) xpair_overflow(ovf, fi - level_base, e[2 * k2 + 1] * F - level_base, xt, a0[k2], a1[k2], c.frac[0]);
-                            else {
-                                const uint32_t i0 = fi - level_base, i1 = e[2 * k2 + 1] * F - level_base;
-                                const float gx = 1.0f - c.frac[0];
-                                xpair_overflow(ovf, i0, i0 ^ 2u, 0u, gx * a0[k2], gx * a1[k2], 0.0f);
-                                xpair_overflow(ovf, i1, i1 ^ 2u, 0u, c.frac[0] * a0[k2], c.frac[0] * a1[k2], 0.0f);
-                            }
-                            sink.ovf_flag[lv] = sink.epoch;
-                        }
-                    }
-                }
-            } else if (wave_any) {
-                float v0[8], v1[8];
-                uint32_t at[8];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) { v0[k] = w[k] * g[2 * pass]; v1[k] = w[k] * g[2 * pass + 1]; }
-                if (combine) {
-                    const RunMul rm = run_multipliers(run);
-                    row_run_sum_n<8>(v0, rm);
-                    row_run_sum_n<8>(v1, rm);
-                }
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    at[k] = NO_SLOT;
-                    if (head & ((v0[k] != 0.0f) | (v1[k] != 0.0f))) {
-                        const int o = (int)((e[k] * F + 2 * pass) >> LNR_SLICE_SHIFT) - first_owner;
-                        at[k] = (uint32_t)atomicAdd(&fill[o], (int)REC);
-                    }
-                }
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    if (at[k] != NO_SLOT) {
-                        const uint32_t fi = e[k] * F + 2 * pass;
-                        if (at[k] <= (uint32_t)BIN - REC) {
-                            const int o = (int)(fi >> LNR_SLICE_SHIFT) - first_owner;
-                            *reinterpret_cast<uint2*>(stage + (uint32_t)o * BIN + at[k]) = lnr_pack_pair((fi & ((1u << LNR_SLICE_SHIFT) - 1u)) >> 1, v0[k], v1[k]);
-                        } else {
-                            sink.ovf_flag[lv] = sink.epoch;
-                            const float q0 = __uint_as_float(lnr_pack26(v0[k]) << 6), q1 = __uint_as_float(lnr_pack26(v1[k]) << 6);
-                            if (q0 != 0.0f) atomicAdd(reinterpret_cast<unsigned long long*>(ovf + (fi - level_base)), (unsigned long long)lnr_to_fix(q0));
-                            if (q1 != 0.0f) atomicAdd(reinterpret_cast<unsigned long long*>(ovf + (fi - level_base) + 1), (unsigned long long)lnr_to_fix(q1));
-                        }
-                    }
-                }
-            }
-            __syncthreads();
-            // ---- B: whole lines out, tail to the front
-            const uint32_t f_raw = own ? (uint32_t)fill[my_owner] : 0u;
-            uint32_t valid = 0u;
-            if (!closed) {
-                const uint32_t n_new = (f_raw - tail) / REC, n_room = ((uint32_t)BIN - tail) / REC;
-                valid = tail + (n_new < n_room ? n_new : n_room) * REC;
-            }
-            const uint32_t nlines = valid >> 7, rem = valid & 127u;
-            const char* bins = stage + (uint32_t)(wave * OPW) * BIN;
-            // tail: the G lanes of an owner move the (< 128) bytes behind its last whole line to the front of its bin
-            // (LDS operations of a wave execute in order: the line reads below come first, the tail's read next, its write last)
-            const uint32_t sub = (uint32_t)(lane % G) * (128u / G);
-            const bool mv = nlines > 0u && sub < rem;
-            char* my_bin = stage + (uint32_t)my_owner * BIN;
-            const int half = lane / LPB, piece = lane % LPB;                                            // which bin of a copy instruction, which 16 bytes of it
-#pragma unroll
-            for (int j0 = 0; j0 < OPW / BPI; j0 += 4) {
-                uint4 v[4];
-                uint32_t n16[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    // line count of the bin this lane copies from: wave-uniform per bin, selected per lane when an instruction covers two bins
-                    n16[j] = (uint32_t)__builtin_amdgcn_readlane((int)nlines, ((j0 + j) * BPI) * G) * 8u;
-                    if constexpr (BPI == 2) { const uint32_t n1 = (uint32_t)__builtin_amdgcn_readlane((int)nlines, ((j0 + j) * BPI + 1) * G) * 8u; if (half) n16[j] = n1; }
-                    if ((uint32_t)piece < n16[j]) v[j] = *reinterpret_cast<const uint4*>(bins + (j0 + j) * (BPI * BIN) + lane * 16);
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int o0 = wave * OPW + (j0 + j) * BPI;
-                    uint64_t dst = reinterpret_cast<uint64_t>(level_regions) + ((size_t)o0 * bpg + chunk) * (size_t)region_bytes +
-                                   (uint32_t)__builtin_amdgcn_readlane((int)gpos, ((j0 + j) * BPI) * G);
-                    if constexpr (BPI == 2) {
-                        const uint64_t d1 = reinterpret_cast<uint64_t>(level_regions) + ((size_t)(o0 + 1) * bpg + chunk) * (size_t)region_bytes +
-                                            (uint32_t)__builtin_amdgcn_readlane((int)gpos, ((j0 + j) * BPI + 1) * G);
-                        if (half) dst = d1;
-                    }
-                    if ((uint32_t)piece < n16[j]) store_stream_b128(dst + (uint32_t)piece * 16u, v[j]);
-                }
-            }
-            if (mv) {
-                uint4 t4[TQ];
-#pragma unroll
-                for (int q = 0; q < TQ; ++q) if (sub + 16u * q < rem) t4[q] = *reinterpret_cast<const uint4*>(my_bin + (nlines << 7) + sub + 16u * q);
-#pragma unroll
-                for (int q = 0; q < TQ; ++q) if (sub + 16u * q < rem) *reinterpret_cast<uint4*>(my_bin + sub + 16u * q) = t4[q];
-            }
-            gpos += nlines << 7;
-            tail = rem;
-            if (!closed && gpos + (uint32_t)(BIN + 128) > region_bytes) {
-                // no room for another worst-case batch: the tail - now at the front of the bin - goes out as the region's last
-                // (partial) line and the owner closes; whatever is addressed to it from here on takes the overflow path
-                char* dst = level_regions + ((size_t)my_owner * bpg + chunk) * (size_t)region_bytes + gpos;
-#pragma unroll
-                for (int q = 0; q < 32 / G; ++q) {
-                    const uint32_t off = sub + 4u * q;
-                    if (off < rem) *reinterpret_cast<uint32_t*>(dst + off) = *reinterpret_cast<const uint32_t*>(my_bin + off);
-                }
-                gpos += rem;
-                tail = 0u;
-                closed = true;
-            }
-            if (lane % G == 0 && own) fill[my_owner] = closed ? ENC_BIN_CLOSED : (int)tail;
-            __syncthreads();
-        }
-        if constexpr (WANT_DX) {
-            float dx[3] = {0.0f, 0.0f, 0.0f};
-            if (any) {
-                if constexpr (EARLY_DX) dx_from_entries<F>(L, c, g, tv, dx);
-                else { float tl[8][F]; gather_entries<F>(table, e, tl); dx_from_entries<F>(L, c, g, tl, dx); }
-            }
-            if constexpr (DXM == ENC_DX_RAYS) {
-                if (wave_any) ray_accumulate_dx(dxl, (uint32_t)__builtin_amdgcn_readfirstlane((int)ray_cur), p_cur.z, dx, lane, src.n_rays);
-            } else if (live) {
-#pragma unroll
-                for (int d = 0; d < 3; ++d) st32<float>(dxplanes, (uint32_t)d * plane_bytes + m * 4u, dx[d]);
-            }
-        }
-    }
-    if (emit && own) {
-        // the unfinished line of every open owner: the only partial-line write of a region
-        if (!closed && tail > 0u) {
-            const char* my_bin = stage + (uint32_t)my_owner * BIN;
-            char* dst = level_regions + ((size_t)my_owner * bpg + chunk) * (size_t)region_bytes + gpos;
-            const uint32_t sub = (uint32_t)(lane % G) * (128u / G);
-#pragma unroll
-            for (int q = 0; q < 32 / G; ++q) {
-                const uint32_t off = sub + 4u * q;
-                if (off < tail) *reinterpret_cast<uint32_t*>(dst + off) = *reinterpret_cast<const uint32_t*>(my_bin + off);
-            }
-        }
-        if (lane % G == 0) sink.counts[region0 + (size_t)my_owner * region_step] = (int)((gpos + (closed ? 0u : tail)) / REC);
-    }
-}
-
 // Frequency encoding has no table: backward is only the input gradient, one plane group for all features.
 // One range reduction per (sin, cos) pair as in freq_forward_h16_kernel: d/dph of the pair's features sin(ph) and sin(rn(ph + pi/2))
 // is cos(ph) and cos(ph + pi/2 + d) = -(sin(ph) + d cos(ph)); as 72 libm cosf calls a sample this kernel cost 236 us at 2.1 M samples
@@ -1238,39 +935,32 @@ int lnr_encode_forward(const LnrNetSpec* spec, const float* params, const PointS
     return LNR_OK;
 }
 
-// THE table of the encode-backward kernels: (partition, n_features, d/dx mode, x-pair records, waves of a binned workgroup) -> kernel.
-// 39 entries: the scan partition for F = 1, 2, 4, 8 and the x-pair form of F = 2, in the three d/dx modes (15); the binned partition
-// for F = 2, 4, 8 and the x-pair form, in the three modes, with 4 or 8 waves (24).  tests/test_gpu_encode_routes.py launches each.
-template <class K>
-static const void* pick_dxm(int dxm, K rays, K planes, K none) { return (const void*)(dxm == ENC_DX_RAYS ? rays : (dxm == ENC_DX_PLANES ? planes : none)); }
-template <int F, bool XP, int NW>
-static const void* binned_fn(int dxm) {
-    return pick_dxm(dxm, encode_backward_binned_kernel<F, ENC_DX_RAYS, XP, NW>, encode_backward_binned_kernel<F, ENC_DX_PLANES, XP, NW>, encode_backward_binned_kernel<F, ENC_DX_NONE, XP, NW>);
-}
+// THE table of the encode-backward kernels: (n_features, d/dx mode, x-pair records) -> kernel.
+// 15 entries: F = 1, 2, 4, 8 and the x-pair form of F = 2, in the three d/dx modes.  tests/test_gpu_encode_routes.py launches each.
 template <int F, bool XP>
-static const void* partition_fn(bool binned, int dxm, int nw) {
-    if constexpr (F >= 2) { if (binned) return nw == 8 ? binned_fn<F, XP, 8>(dxm) : binned_fn<F, XP, 4>(dxm); }          // (binned records are pair records)
-    return pick_dxm(dxm, encode_backward_kernel<F, ENC_DX_RAYS, XP>, encode_backward_kernel<F, ENC_DX_PLANES, XP>, encode_backward_kernel<F, ENC_DX_NONE, XP>);
+static const void* partition_fn(int dxm) {
+    return (const void*)(dxm == ENC_DX_RAYS ? encode_backward_kernel<F, ENC_DX_RAYS, XP>
+                         : (dxm == ENC_DX_PLANES ? encode_backward_kernel<F, ENC_DX_PLANES, XP> : encode_backward_kernel<F, ENC_DX_NONE, XP>));
 }
-static const void* encode_backward_fn(bool binned, int n_features, int dxm, bool xp, int nw) {
-    if (xp) return partition_fn<2, true>(binned, dxm, nw);
-    return n_features == 1 ? partition_fn<1, false>(binned, dxm, nw) : n_features == 2 ? partition_fn<2, false>(binned, dxm, nw)
-         : n_features == 4 ? partition_fn<4, false>(binned, dxm, nw) : partition_fn<8, false>(binned, dxm, nw);
+static const void* encode_backward_fn(int n_features, int dxm, bool xp) {
+    if (xp) return partition_fn<2, true>(dxm);
+    return n_features == 1 ? partition_fn<1, false>(dxm) : n_features == 2 ? partition_fn<2, false>(dxm)
+         : n_features == 4 ? partition_fn<4, false>(dxm) : partition_fn<8, false>(dxm);
 }
-// a launch with `lds` bytes of dynamic LDS; fail: the text of a failed launch (NULL: LNR_CHECK_LAUNCH's, for `what`)
-static int launch_with_lds(const void* fn, dim3 grid, dim3 block, size_t lds, void** args, hipStream_t st, const char* fail, const char* what) {
+// a launch with `lds` bytes of dynamic LDS; what: names the call in the text of a failed launch (as LNR_CHECK_LAUNCH does)
+static int launch_with_lds(const void* fn, dim3 grid, dim3 block, size_t lds, void** args, hipStream_t st, const char* what) {
     if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
         lnr_set_error("lnr_density_backward: hipFuncSetAttribute(%zu) failed", lds); return LNR_ERR_LAUNCH;
     }
     const hipError_t e = hipLaunchKernel(fn, grid, block, args, lds, st);
     if (e == hipSuccess) return LNR_OK;
-    if (fail != nullptr) lnr_set_error("%s", fail);
-    else { (void)hipGetLastError(); lnr_set_error("%s: launch failed: %s", what, hipGetErrorString(e)); }
+    (void)hipGetLastError();
+    lnr_set_error("%s: launch failed: %s", what, hipGetErrorString(e));
     return LNR_ERR_LAUNCH;
 }
 
 int lnr_encode_backward(const LnrNetSpec* spec, const float* params, const PointSrc* src, int64_t cap_points, const float* dfeat, int64_t m_pad,
-                        const TableGradSink& to, const InputGradOut& out, bool bins_w8, hipStream_t st) {
+                        const TableGradSink& to, const InputGradOut& out, hipStream_t st) {
     const float* table = params + spec->n_mlp_params;
     const bool hash = spec->encoding == LNR_ENC_HASHGRID;
     float* const dxl = out.dxl; float* const d_pts = out.d_pts; float* const d_rays_acc = out.d_rays; long long* const ray_acc = out.ray_acc;
@@ -1285,39 +975,31 @@ int lnr_encode_backward(const LnrNetSpec* spec, const float* params, const Point
     }
     const int n_groups = hash ? spec->n_levels : 1;
     if (hash && (to.regions != nullptr || dxm != ENC_DX_NONE)) {
-        LevelList rec_levels, xp_levels, brec_levels, bxp_levels;          // 8-byte record levels, x-pair record levels, and their binned forms: one launch each
-        rec_levels.n = xp_levels.n = brec_levels.n = bxp_levels.n = 0;
-        const bool allow_binned = to.regions != nullptr && to.maxo <= LNR_BIN_MAX_OWNERS;
+        LevelList rec_levels, xp_levels;          // 8-byte record levels, x-pair record levels: one launch each
+        rec_levels.n = xp_levels.n = 0;
         int ovf_total = 0;
         for (int l = 0; l < spec->n_levels; ++l) {
             const int nfl = (int)spec->level_size[l] * spec->n_features;
             const bool is_xp = spec->n_features == 2 && to.plan.xp[l] != 0;
-            const bool is_binned = allow_binned && to.plan.binned[l] != 0 && to.plan.bytes[l] != 0;
-            LevelList& ll = is_xp ? (is_binned ? bxp_levels : xp_levels) : (is_binned ? brec_levels : rec_levels);
+            LevelList& ll = is_xp ? xp_levels : rec_levels;
             ll.lv[ll.n] = l; ll.slab_off[ll.n] = ovf_total; ll.n++;
             ovf_total += nfl;
         }
-        if (rec_levels.n + xp_levels.n + brec_levels.n + bxp_levels.n > 0) {
+        if (rec_levels.n + xp_levels.n > 0) {
             // (the overflow accumulators are all-zero here: lnr_density_backward keeps them so between calls, lnr_density.hip)
             EncSink sink{to.grad_table, to.ovf, to.regions, to.plan, to.counts, to.maxo, to.shift, 0, to.ovf_flag, to.epoch, LNR_COMBINE_SCALE_MAX};
             LnrProfScope prof("encode_backward", st);
             const int maxo4 = (to.maxo + 3) & ~3;
             const size_t lds_scan = (size_t)(2 * maxo4 + 4 * to.maxo) * sizeof(int) + (size_t)ENC_STAGE_RECORDS * (spec->n_features >= 2 ? 16 : 8);
-            // binned partition: NW = 4 (256-thread workgroups, 512-byte bins) or 8 (512 threads, 1 KB bins)
-            const int nw = bins_w8 ? 8 : 4;
-            const size_t lds_binned = 64 * sizeof(int) + (size_t)LNR_BIN_MAX_OWNERS * (size_t)(128 * nw);
-            auto launch = [&](LevelList& list, bool xp, bool binned) -> int {          // one launch for the levels of `list`
+            auto launch = [&](LevelList& list, bool xp) -> int {          // one launch for the levels of `list`
                 if (list.n == 0) return LNR_OK;
                 sink.xcd_affine = lnr_xcd_affine(list.n, cap_points, false) ? 1 : 0;
                 void* args[] = {(void*)spec, (void*)&table, (void*)src, (void*)&dfeat, (void*)&dx_out, (void*)&m_pad, (void*)&bpg, (void*)&list, (void*)&sink};
-                return launch_with_lds(encode_backward_fn(binned, spec->n_features, dxm, xp, nw), dim3((unsigned)(list.n * bpg)), dim3(binned ? 64 * nw : ENC_BWD_BLOCK),
-                                       binned ? lds_binned : lds_scan, args, st, binned ? "lnr_density_backward: launch of the binned partition failed" : nullptr,
+                return launch_with_lds(encode_backward_fn(spec->n_features, dxm, xp), dim3((unsigned)(list.n * bpg)), dim3(ENC_BWD_BLOCK), lds_scan, args, st,
                                        "lnr_density_backward(encode backward)");
             };
-            int rc = launch(rec_levels, false, false);
-            if (!rc) rc = launch(xp_levels, true, false);                   // n_features == 2
-            if (!rc) rc = launch(brec_levels, false, true);
-            if (!rc) rc = launch(bxp_levels, true, true);
+            int rc = launch(rec_levels, false);
+            if (!rc) rc = launch(xp_levels, true);                   // n_features == 2
             if (rc) return rc;
 #ifdef LNR_PHASE_TIMING
             if (getenv("LNR_PHASE_TIMING")) {

@@ -40,8 +40,6 @@ POS_ROUNDINGS = {"fma": 0, "mul_add": 1}
 BWD_TABLE_ATOMICS = 1        # LNR_BWD_TABLE_ATOMICS
 BWD_REPORT_REGIONS = 2       # LNR_BWD_REPORT_REGIONS
 BWD_DEFER_WEIGHT_FOLD = 16   # LNR_BWD_DEFER_WEIGHT_FOLD
-BWD_BINS = 4                 # LNR_BWD_BINS
-BWD_BINS_W8 = 8              # LNR_BWD_BINS_W8
 BWD_OVERWRITE_GRAD = 32      # LNR_BWD_OVERWRITE_GRAD
 WORKSPACE_STATUS_BYTES, STATUS_CLIPPED = 256, 0            # LNR_WORKSPACE_STATUS_BYTES, LNR_STATUS_CLIPPED
 DRAW_JITTER, DRAW_PDF, DRAW_NOISE, DRAW_RAY_INDEX = 0, 1, 2, 16      # LNR_DRAW_*

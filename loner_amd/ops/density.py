@@ -3,7 +3,6 @@ Mapping loop, every iteration: fp32 device tensors (other float dtypes are conve
 workspace grows and in density_clipped_count.  A caller-owned output of the wrong dtype or shape is an assertion; RuntimeError: the
 library refused the call, or reuse_features named another forward."""
 import ctypes as C
-import os
 
 import torch
 
@@ -32,8 +31,6 @@ def profile_read():
 
 
 _workspaces = {}
-_BINS_W8 = bool(os.environ.get("LNR_BINS_W8"))
-_BINS = bool(os.environ.get("LNR_BINS"))            # A/B switch of the experiment scripts (tools/): the binned partition on hashed levels
 
 
 def _workspace(spec, device, n_points, forward_only=False):
@@ -106,7 +103,7 @@ def _event(ev):
 
 
 def density_backward(spec, params, d_sigma, grad_params, pts=None, rays=None, z=None, n_rays_dev=None,
-                     want_d_pts=False, reuse_features=False, d_rays=None, table_atomics=False, report_regions=False, bins=False, bins_w8=False, input_grad_event=None,
+                     want_d_pts=False, reuse_features=False, d_rays=None, table_atomics=False, report_regions=False, input_grad_event=None,
                      defer_weight_fold=False, overwrite_grad=False):
     """Accumulates into grad_params [n_params] (None: parameters frozen, only the input gradient is computed);
     returns d_pts ([...,3]) or None.  table_atomics: test hook (LNR_BWD_TABLE_ATOMICS).
@@ -119,7 +116,6 @@ def density_backward(spec, params, d_sigma, grad_params, pts=None, rays=None, z=
     params, d_sigma = _f32c(params), _f32c(d_sigma)
     assert grad_params is None or (grad_params.dtype == torch.float32 and grad_params.is_contiguous())
     flags = (hip.BWD_TABLE_ATOMICS if table_atomics else 0) | (hip.BWD_REPORT_REGIONS if report_regions else 0) | \
-        (hip.BWD_BINS if (bins or _BINS) else 0) | (hip.BWD_BINS_W8 if (bins_w8 or _BINS_W8) else 0) | \
         (hip.BWD_DEFER_WEIGHT_FOLD if defer_weight_fold else 0) | (hip.BWD_OVERWRITE_GRAD if overwrite_grad else 0)
     if pts is not None:                                 # the points form: rays, z and n_rays_dev stay out of the call
         pts = _f32c(pts).reshape(-1, 3)

@@ -1,7 +1,7 @@
 """The density workspace layout and route, pinned (no GPU): lnr_density_workspace, lnr_density_workspace_forward and every field of
 lnr_density_route (forward and backward) for every network of tests/test_gpu_kernels.py NETS plus the benchmark's default table
 size, at the point counts where make_layout and lnr_route change what they do.  tests/golden/density_layout.json holds the values the
-library gave before the table-gradient plumbing was folded (docs/HISTORY.md); host code that only moves must reproduce them.
+library gave when the binned partition's region headroom went (docs/HISTORY.md 14); host code that only moves must reproduce them.
 
     python tests/test_density_layout_host.py --record      rewrites the file from the library as built (a deliberate layout change)
 """

@@ -242,7 +242,7 @@ def test_gradient_accumulates_into_or_overwrites_the_buffer(ops, mode):
 
 # ------------------------------------------------------------------------------------------- d. overflow and the split reduce
 def _skewed_batch():
-    """the batch of test_binned_partition_overflow_and_region_close - every sample in three clusters of a few cells, stragglers
+    """the batch of test_record_partition_under_worst_skew_equals_global_accumulation (test_gpu_kernels.py) - every sample in three clusters of a few cells, stragglers
     elsewhere - with 512 rays instead of 256: the library gives the dense-indexed levels several reduce workgroups per owner only
     from 32 partition chunks (65 536 samples) on"""
     gen = torch.Generator().manual_seed(12)

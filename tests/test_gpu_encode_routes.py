@@ -1,8 +1,8 @@
-"""Every encode-backward kernel lnr_encode_backward can select is launched here (pytest -m gpu): the scan partition for 1, 2, 4 and 8
-features per level and the x-pair form, the binned partition (LNR_BWD_BINS) for 2, 4, 8 and the x-pair form at both workgroup sizes,
-each in the three input-gradient modes (per-ray sums, d/dx planes, none).  The nets are the smallest whose hashed levels span exactly
-64 owner slices - the only span at which a level of 8-byte records takes the binned partition (make_layout, lnr_density.hip) - and
-every route must give the same bits as the default one, as test_record_partition_equals_global_accumulation requires of the rays form.
+"""Every encode-backward kernel lnr_encode_backward can select is launched here (pytest -m gpu): the record partition for 1, 2, 4 and 8
+features per level and the x-pair form, each in the three input-gradient modes (per-ray sums, d/dx planes, none).  The hashed levels
+of f2, f4 and f8 span 64 owner slices; f2 has one level of 8-byte records and one of x-pair records.  The all-atomics route
+(LNR_BWD_TABLE_ATOMICS) must give the same bits as the default one, as test_record_partition_equals_global_accumulation requires of
+the rays form.
 """
 import functools
 
@@ -15,30 +15,27 @@ from oracle import network as NW
 
 DEV = "cuda"
 MLP = dict(activation="ReLU", n_neurons=32, n_hidden_layers=1)
-# name -> (encoding, level kinds the net is meant to have: (x-pair records, binned under LNR_BWD_BINS) per level)
+# name -> (encoding, level kinds the net is meant to have: x-pair records per level)
 NETS = {
-    "f1": (dict(otype="HashGrid", n_levels=2, n_features_per_level=1, log2_hashmap_size=13, base_resolution=8), [(False, False), (False, False)]),
-    "f2": (dict(otype="HashGrid", n_levels=2, n_features_per_level=2, log2_hashmap_size=18, base_resolution=2048), [(False, True), (True, True)]),
-    "f4": (dict(otype="HashGrid", n_levels=2, n_features_per_level=4, log2_hashmap_size=17, base_resolution=64), [(False, True), (False, True)]),
-    "f8": (dict(otype="HashGrid", n_levels=2, n_features_per_level=8, log2_hashmap_size=16, base_resolution=64), [(False, True), (False, True)]),
+    "f1": (dict(otype="HashGrid", n_levels=2, n_features_per_level=1, log2_hashmap_size=13, base_resolution=8), [False, False]),
+    "f2": (dict(otype="HashGrid", n_levels=2, n_features_per_level=2, log2_hashmap_size=18, base_resolution=2048), [False, True]),
+    "f4": (dict(otype="HashGrid", n_levels=2, n_features_per_level=4, log2_hashmap_size=17, base_resolution=64), [False, False]),
+    "f8": (dict(otype="HashGrid", n_levels=2, n_features_per_level=8, log2_hashmap_size=16, base_resolution=64), [False, False]),
 }
-ROUTES = {"default": {}, "bins": dict(bins=True), "bins_w8": dict(bins=True, bins_w8=True), "table_atomics": dict(table_atomics=True)}
+ROUTES = {"default": {}, "table_atomics": dict(table_atomics=True)}
 MODES = ("d_rays", "d_pts", "none")
 N_RAYS, N_SAMPLES = 64, 64          # one wave per ray: the per-ray input-gradient mode applies
 
-SLICE_SHIFT, XPAIR_SCALE_MIN, BIN_MAX_OWNERS, BIN_BYTES, BLOCK = 13, 3000.0, 64, 1024, 512          # lnr_density_api.h
+SLICE_SHIFT, XPAIR_SCALE_MIN = 13, 3000.0          # lnr_density_api.h
 
 
 def _level_kinds(spec):
-    """(x-pair records, binned) per level, restated from the NetSpec: lnr_level_can_use_xpairs and make_layout's binned condition"""
+    """x-pair records per level, restated from the NetSpec: lnr_level_can_use_xpairs"""
     F, kinds = spec.n_features, []
     for l in range(spec.n_levels):
         size, off, hashed = int(spec.level_size[l]), int(spec.level_offset[l]), spec.level_hashed[l] != 0
         xp = F == 2 and hashed and size & (size - 1) == 0 and spec.level_scale[l] >= XPAIR_SCALE_MIN and (off * 2) & ((1 << SLICE_SHIFT) - 1) == 0
-        lo, hi = off * F, (off + size) * F
-        span = ((hi - 1) >> SLICE_SHIFT) - (lo >> SLICE_SHIFT) + 1
-        binned = F >= 2 and hashed and span <= BIN_MAX_OWNERS and BLOCK * 8 * (6 if xp else 8) / span <= 0.5 * BIN_BYTES + 8
-        kinds.append((xp, binned))
+        kinds.append(bool(xp))
     return kinds
 
 
@@ -99,7 +96,7 @@ def test_default_route_in_every_input_gradient_mode(ops, net):
     assert torch.equal(frozen["d_rays"][1], ref["d_rays"][1])
 
 
-@pytest.mark.parametrize("net,route", [(n, r) for n in NETS for r in ROUTES if r != "default" and not (n == "f1" and r.startswith("bins"))])
+@pytest.mark.parametrize("net,route", [(n, r) for n in NETS for r in ROUTES if r != "default"])
 def test_route_equals_the_default_route_bit_for_bit(ops, net, route):
     ref, got = _reference(ops, net), _backward(ops, net, route)
     for mode in MODES:

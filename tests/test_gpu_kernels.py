@@ -1108,11 +1108,6 @@ def test_record_partition_equals_global_accumulation(ops, net):
     assert torch.equal(g_rec[table], g_acc[table])
     assert torch.equal(g_rec[:table.start], g_acc[:table.start]) and torch.equal(r_rec, r_acc)
     assert float(r_rec[live:].abs().max()) == 0.0                                  # dropped rays receive nothing
-    # the binned partition of the hashed levels (LNR_BWD_BINS, both workgroup sizes) is the same function too
-    for w8 in (False, True):
-        g_bin = torch.zeros_like(g_rec); r_bin = torch.zeros_like(r_rec)
-        ops.density_backward(spec, params, dv(d_sigma), g_bin, rays=dv(rays), z=dv(z), n_rays_dev=n_dev, d_rays=r_bin, bins=True, bins_w8=w8)
-        assert torch.equal(g_bin, g_rec) and torch.equal(r_bin, r_rec)
     # [r4] the 64-bit overflow accumulators are kept all-zero BETWEEN calls (the reduce re-zeroes what it reads; no per-call clear): a call
     # behind one that filled every level's accumulators (the all-atomics route) must see none of it
     g_acc2 = torch.zeros_like(g_rec)
@@ -1127,11 +1122,11 @@ def test_record_partition_equals_global_accumulation(ops, net):
 
 
 @pytest.mark.parametrize("net", ["default", "hash_f4_2hidden"])
-def test_binned_partition_overflow_and_region_close(ops, net):
-    """The binned partition under the worst skew: every sample of the batch sits in the same few cells, so a handful of owners
-    receive everything - their LDS bins overflow in every batch and their regions fill up and close - while the rest stay empty.
-    Whatever route a record takes (bin -> line -> region, bin tail at the kernel's end, bin-full overflow, closed-region overflow),
-    the gradient equals the all-atomics accumulation bit for bit."""
+def test_record_partition_under_worst_skew_equals_global_accumulation(ops, net):
+    """The record partition under the worst skew: every sample of the batch sits in the same few cells, so a handful of owners
+    receive everything - their regions fill up in the first batches and the rest of their records overflow - while the other
+    owners stay empty.  Whatever route a record takes (staging buffer -> region, region-full overflow), the gradient equals the
+    all-atomics accumulation bit for bit."""
     from loner_amd import hip
     enc, net_cfg = NETS[net]
     spec = hip.make_net_spec(enc, net_cfg)
@@ -1151,16 +1146,11 @@ def test_binned_partition_overflow_and_region_close(ops, net):
     for n_live in (N, 3):                                                          # also a batch with three live rays (one partial batch)
         n_dev = torch.tensor([n_live], dtype=torch.int32, device=DEV)
         ops.density_forward(spec, params, rays=dv(rays), z=dv(z), n_rays_dev=n_dev)
-        g_bin = torch.zeros(int(spec.n_params), device=DEV); g_acc = torch.zeros_like(g_bin); g_scan = torch.zeros_like(g_bin)
-        ops.density_backward(spec, params, dv(d_sigma), g_bin, rays=dv(rays), z=dv(z), n_rays_dev=n_dev, bins=True)
+        g_acc = torch.zeros(int(spec.n_params), device=DEV); g_scan = torch.zeros_like(g_acc)
         ops.density_backward(spec, params, dv(d_sigma), g_acc, rays=dv(rays), z=dv(z), n_rays_dev=n_dev, table_atomics=True)
         ops.density_backward(spec, params, dv(d_sigma), g_scan, rays=dv(rays), z=dv(z), n_rays_dev=n_dev)
-        assert float(g_bin.abs().max()) > 0
-        assert torch.equal(g_bin, g_acc), int((g_bin != g_acc).sum())
-        assert torch.equal(g_bin, g_scan)
-        g_w8 = torch.zeros_like(g_bin)
-        ops.density_backward(spec, params, dv(d_sigma), g_w8, rays=dv(rays), z=dv(z), n_rays_dev=n_dev, bins=True, bins_w8=True)
-        assert torch.equal(g_bin, g_w8)
+        assert float(g_scan.abs().max()) > 0
+        assert torch.equal(g_scan, g_acc), int((g_scan != g_acc).sum())
 
 
 # ------------------------------------------------------------------------------------------- full-size properties

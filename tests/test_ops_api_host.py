@@ -37,7 +37,7 @@ API = {
     'count_intersections': '(bvh, rays, t_min=0.0, t_max=inf, stats=None)',
     'count_opaque': '(rays, depth_gt, n_rays_dev=None, far0=None)',
     'density_backward': '(spec, params, d_sigma, grad_params, pts=None, rays=None, z=None, n_rays_dev=None, want_d_pts=False, reuse_features=False, '
-                        'd_rays=None, table_atomics=False, report_regions=False, bins=False, bins_w8=False, input_grad_event=None, '
+                        'd_rays=None, table_atomics=False, report_regions=False, input_grad_event=None, '
                         'defer_weight_fold=False, overwrite_grad=False)',
     'density_clipped_count': '(device) -> int',
     'density_fold_weight_grads': '(spec, grad_params, n_points, overwrite_grad=False)',
