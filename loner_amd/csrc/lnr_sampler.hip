@@ -270,11 +270,15 @@ sample_occ_kernel(const float* __restrict__ rays, int n_rays, const int32_t* __r
         if (dbg_inds) dbg_inds[(size_t)ray * H + j] = ind;
     }
     for (int j = S + threadIdx.x; j < P2; j += SAMPLER_BLOCK) merged[j] = __builtin_inff();
-    // sort(cat(coarse, importance)) (ray_sampling.py:90; only the values matter).  The coarse depths already ascend (a jittered depth
-    // stays inside its stratum), so when S is a power of two the full network is not needed: the importance half is sorted DESCENDING
-    // by the four waves (a network of half the size), and the last stage of the full network merges the two halves - 36 + 9 instead
-    // of 45 passes at S = 512, the 36 of them over half the pairs.  Same values out, whatever the route; any inversion among the coarse
-    // depths (none has been seen) sends the ray down the full sort.
+    // sort(cat(coarse, importance)) (ray_sampling.py:90; only the values matter).  On an ordinary span (near < far) the coarse depths
+    // already ascend (a jittered depth stays inside its stratum; neighbours can tie, never invert), so when S is a power of two the
+    // full network is not needed: the importance half is sorted DESCENDING by the four waves (a network of half the size), and the last
+    // stage of the full network merges the two halves - 36 + 9 instead of 45 passes at S = 512, the 36 of them over half the pairs.
+    // Same values out, whatever the route.  The coarse depths DO invert on a reversed span (far < near: a ray whose origin lies outside
+    // the cube and that points away has far = 0), on an empty span (near == far: near (1 - s) + far s is not constant in float32) and
+    // on a narrow span at perturb = 0 (the same rounding, no jitter on top); any inversion sends that ray down the full sort, ray by
+    // ray within one launch.  tests/test_gpu_sampler.py runs all three beside merge rays; tests/test_sampler_host.py shows that the
+    // merge alone sorts no reversed span and few of the others.
     if (__syncthreads_or(unsorted ? 1 : 0) == 0 && P2 == S && H >= 64) {
         bitonic_sort_lds(merged + H, H, true);
         bitonic_sort_lds(merged, P2, false, P2);
@@ -309,7 +313,7 @@ extern "C" int lnr_sample_rays_occ(const float* rays, int32_t n_rays, const int3
     LNR_REQUIRE(n_samples >= 8 && n_samples % 2 == 0 && n_samples <= 8192, "lnr_sample_rays_occ: n_samples must be even, in [8, 8192] (got %d)", n_samples);
     if (n_rays == 0) return LNR_OK;
     const int H = n_samples / 2, P2 = next_pow2(n_samples);
-    const size_t lds = (size_t)(4 * H + P2 + 32 + 4) * sizeof(float);
+    const size_t lds = (size_t)(4 * H + P2 + 32 + 4) * sizeof(float);     // 98 KB at n_samples = 8192: launches as it is (tested at that size)
     hipLaunchKernelGGL(sample_occ_kernel, dim3(n_rays), dim3(SAMPLER_BLOCK), lds, (hipStream_t)stream, rays, n_rays, n_rays_dev,
                        grid, V, n_samples, perturb, steps, u_jitter, u_pdf, seed, z_out, dbg_inds, dbg_probs, dbg_cdf, P2);
     LNR_CHECK_LAUNCH("lnr_sample_rays_occ");
