@@ -2,6 +2,7 @@
 
     python examples/run_sequence.py <folder> [--gt poses_tum.txt] [--gt-mesh mesh.ply [--mesh-resolution 0.1] [--tsdf-baseline]]
                                     [--out ~/LonerSLAM/outputs] [--name run] [--ray-range 1 50]
+                                    [--icp-estimation GENERALIZED] [--icp-kernel tukey 3]
 
 <folder> holds one `.npy` file per scan, [N,4] columns x, y, z, t (t: per-point time, local to the scan or global, seconds or
 nanoseconds), read in sorted name order, and `stamps.txt` with one scan time in seconds per line.  With --gt (a TUM file: ts x y z qx
@@ -43,6 +44,10 @@ def main():
     ap.add_argument("--name", default=None)
     ap.add_argument("--ray-range", type=float, nargs=2, default=(1.0, 50.0))
     ap.add_argument("--log-level", default="STANDARD", choices=("DISABLED", "STANDARD", "VERBOSE"))
+    ap.add_argument("--icp-estimation", default="POINT_TO_PLANE", choices=("POINT_TO_PLANE", "GENERALIZED"),
+                    help="the tracker's estimator (tracker.icp.estimation)")
+    ap.add_argument("--icp-kernel", nargs=2, metavar=("TYPE", "K"), default=None,
+                    help="a robust loss on the tracker's ICP: huber, cauchy or tukey and its scale (tracker.icp.robust_kernel)")
     args = ap.parse_args()
     if args.tsdf_baseline and not args.gt_mesh:
         raise SystemExit("--tsdf-baseline needs --gt-mesh")
@@ -55,6 +60,9 @@ def main():
     settings = default_settings(args.out, args.ray_range)
     settings["system"]["single_threaded"] = True
     settings["mapper"]["log_level"] = args.log_level
+    settings["tracker"]["icp"]["estimation"] = args.icp_estimation
+    if args.icp_kernel:
+        settings["tracker"]["icp"]["robust_kernel"] = {"type": args.icp_kernel[0], "k": float(args.icp_kernel[1])}
     gt_poses, gt_of_scan = None, None
     if args.gt:
         rows = read_tum(args.gt)

@@ -579,12 +579,61 @@ int lnr_icp_correspondences(const void* grid, int64_t n_targets, const double* q
  * result_dev fp64 [LNR_ICP_RESULT]: [0:16] transformation, [16] fitness, [17] inlier_rmse, [18:39] the last solved JTJ (upper
  * triangle, row by row), [39:45] its JTr, [45] its sum of d2, [46:52] its x.  info_dev int64 [8]: {status, correspondences, rounds
  * run, non-finite source points, correspondences whose target normal is non-finite, correspondences of the last solved system,
- * converged or stopped, 0}; status bit 1: a non-finite source point, 2: the grid is unusable (a non-finite target, or another
+ * converged or stopped, 0 (lnr_icp_generalized: correspondences skipped)}; status bit 1: a non-finite source point, 2: the grid is unusable (a non-finite target, or another
  * n_targets), 4: a non-finite target normal, 8: a non-finite update (the transformation keeps its last finite value). */
 size_t lnr_icp_workspace(int64_t n_source);
 int lnr_icp_point_to_plane(const void* grid, int64_t n_targets, const double* target_normals, const double* source, int64_t n_source,
                            double max_distance, const double* init, double relative_fitness, double relative_rmse, int32_t max_iteration,
                            void* workspace, size_t workspace_bytes, double* result_dev, int64_t* info_dev, void* stream);
+
+/* ---- robust kernels and generalized ICP (open3d's RobustKernel family and registration_generalized_icp; Segal et al., ------------
+ *      "Generalized-ICP", RSS 2009) ---------------------------------------------------------------------------------------------- */
+/* Robust kernels: the weight w(m) of a residual of magnitude m >= 0 with the scale k (finite and > 0 unless the kernel is L2), fp64:
+ *   LNR_ROBUST_L2      w = 1 (no weight is evaluated: the terms are summed as they are)
+ *   LNR_ROBUST_HUBER   w = k / max(m, k)
+ *   LNR_ROBUST_CAUCHY  q = m / k, w = 1 / (1 + q q)
+ *   LNR_ROBUST_TUKEY   q = m / k, u = 1 - q q, w = u u for m <= k, else 0
+ * A weighted sum adds w * term, the term formed first. */
+#define LNR_ROBUST_L2 0
+#define LNR_ROBUST_HUBER 1
+#define LNR_ROBUST_CAUCHY 2
+#define LNR_ROBUST_TUKEY 3
+
+/* lnr_icp_point_to_plane with the weight w(|r|) on every correspondence's JTJ and JTr terms (the 21 products J_a J_b and the 6
+ * products J_a r); fitness, inlier_rmse and the count are not weighted.  With LNR_ROBUST_L2 it runs lnr_icp_point_to_plane's own
+ * kernels and returns its bytes.  Everything else, the result and the info words included, is lnr_icp_point_to_plane's. */
+int lnr_icp_point_to_plane_robust(const void* grid, int64_t n_targets, const double* target_normals, const double* source,
+                                  int64_t n_source, double max_distance, const double* init, double relative_fitness,
+                                  double relative_rmse, int32_t max_iteration, int32_t kernel, double kernel_k, void* workspace,
+                                  size_t workspace_bytes, double* result_dev, int64_t* info_dev, void* stream);
+
+/* The covariance of a point on a plane with the unit normal n: C_ab = delta_ab - ((1 - epsilon) n_a) n_b for a <= b, mirrored below
+ * the diagonal; open3d's Rx diag(epsilon, 1, 1) Rx^T written without the rotation, so it does not depend on the sign of n.  A
+ * non-finite normal gives a covariance with non-finite entries.  normals [n,3] -> covariances [n,3,3]; epsilon finite and > 0. */
+int lnr_cloud_plane_covariances(const double* normals, int64_t n, double epsilon, double* covariances, void* stream);
+
+/* open3d's RegistrationGeneralizedICP (plane to plane).  Correspondences, fitness, inlier_rmse, the convergence test, the LDLT solve,
+ * the update and its composition, the fixed-order sums, the workspace, result_dev and info_dev are lnr_icp_point_to_plane's; only the
+ * system differs.  target_covariances [n_targets,3,3] in the targets' input order and source_covariances [n_source,3,3] as the
+ * caller has them for the untransformed source; of each only the upper triangle is read.  Per correspondence (s, t) of a round, with
+ * R the rotation block of the accumulated transformation (init before the first round; the source's covariances are rotated from
+ * their given values every round, so rounding does not compound), fp64 without fma:
+ *   B = R C_s, B_ab = (R_a0 S_0b + R_a1 S_1b) + R_a2 S_2b;   M_ab = T_ab + ((B_a0 R_b0 + B_a1 R_b1) + B_a2 R_b2) for a <= b
+ *   cofactors c00 = m11 m22 - m12 m12, c01 = m02 m12 - m01 m22, c02 = m01 m12 - m02 m11, c11 = m00 m22 - m02 m02,
+ *   c12 = m01 m02 - m00 m12, c22 = m00 m11 - m01 m01;  det = (m00 c00 + m01 c01) + m02 c02;  W_ab = c_ab / det
+ *   d = s - t;  (W d)_a = (W_a0 d0 + W_a1 d1) + W_a2 d2;  m = sqrt(max((d0 (Wd)_0 + d1 (Wd)_1) + d2 (Wd)_2, 0)), the Mahalanobis residual
+ *   J = [-[s]x | I] (3x6);  G = W [-[s]x], row a of G = s x (row a of W);  H = [s]x G, column b of H = s x (column b of G)
+ *   JTJ += w(m) [H G^T; G W] (its upper triangle, row by row: H_aa.. H_a2, G_0a, G_1a, G_2a for a < 3, then W's)
+ *   JTr += w(m) [s x (W d); W d]
+ * These are open3d's normal equations without the matrix square root of M^-1 (J^T sqrt(W) sqrt(W) J = J^T W J: with L2 the same
+ * least-squares problem).  Stated difference: the robust weight is taken once per correspondence on m, not once per whitened row, so
+ * it does not depend on the frame.  A correspondence whose M has a non-finite entry or whose det is not > 0 is skipped and counted:
+ * status bit 16, and info_dev[7] holds the count (0 from the point-to-plane entry points); like the other data bits it ends the
+ * call with the transformation at its last value. */
+int lnr_icp_generalized(const void* grid, int64_t n_targets, const double* target_covariances, const double* source,
+                        const double* source_covariances, int64_t n_source, double max_distance, const double* init,
+                        double relative_fitness, double relative_rmse, int32_t max_iteration, int32_t kernel, double kernel_k,
+                        void* workspace, size_t workspace_bytes, double* result_dev, int64_t* info_dev, void* stream);
 
 /* ---- mesh sampling, outlier filter, trajectory transform (analysis/compute_metrics/maps/mesh_to_pcd.py; ------------------------
  *      examples/fusion_portable/create_lidar_map.py, mask_gt_with_trajectory.py) ------------------------------------------------- */

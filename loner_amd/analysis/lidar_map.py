@@ -324,23 +324,29 @@ def alignment_skip(n):
     return int(n / 1_000_000) if n > 1_000_000 else 1
 
 
-def refine_alignment_icp(est_scan, gt_scan):
+def refine_alignment_icp(est_scan, gt_scan, kernel=None):
     """evaluate_lidar_map.py:23-53 on down-sampled clouds: the alignment subsets, the target's normals (knn 30), and 10 rounds of
-    point-to-plane ICP at 0.125 m from the identity with criteria 1e-12.  -> RegistrationResult (est_scan is not moved)."""
+    point-to-plane ICP at 0.125 m from the identity with criteria 1e-12.  -> RegistrationResult (est_scan is not moved).  kernel: an
+    analysis.registration.RobustKernel on the residuals (the clouds hold gross outliers by construction: unobserved ground truth and
+    floaters); None is the reference's plain L2 call."""
     gt_alignment = gt_scan.uniform_down_sample(alignment_skip(len(gt_scan)))
     est_alignment = est_scan.uniform_down_sample(alignment_skip(len(est_scan)))
     print("Estimating point cloud normals")
     gt_alignment.estimate_normals(30)
     print("Refining alignment")
+    if kernel is not None:
+        from .registration import registration_icp_robust
+        return registration_icp_robust(est_alignment, gt_alignment, 0.125, np.eye(4), 1e-12, 1e-12, 10, kernel)
     return registration_icp(est_alignment, gt_alignment, 0.125, np.eye(4), 1e-12, 1e-12, 10)
 
 
 # ---------------------------------------------------------------- evaluation
 def compare_point_clouds(est_scan, gt_scan, output_dir, f_score_threshold, voxel_size=0.05, write_pointclouds=False,
-                         write_gt_cloud=False, id_str=None, refine_alignment=False, alignment=None):
+                         write_gt_cloud=False, id_str=None, refine_alignment=False, alignment=None, alignment_kernel=None):
     """Accuracy, completion, Chamfer distance, precision, recall and F-score of est_scan against gt_scan after down-sampling both
     (evaluate_lidar_map.py:16-98).  refine_alignment: first move the down-sampled estimate by point-to-plane ICP
-    (refine_alignment_icp; evaluate_lidar_map.py:23-53); alignment (a dict, optional) receives the ICP result.  Writes
+    (refine_alignment_icp; evaluate_lidar_map.py:23-53); alignment (a dict, optional) receives the ICP result; alignment_kernel (an
+    analysis.registration.RobustKernel, optional) is the refinement's loss.  Writes
     {output_dir}/metrics/statistics{_id}.yaml and, when asked, lidar_renders/rendered{_id}.pcd and gt{_id}.pcd; returns the
     statistics.  Quirks kept: precision = TP / len(accuracy), recall = TP / (TP + FN) with TP counted on the estimate and FN on the
     ground truth, and 1e-8 in the F-score's denominator."""
@@ -351,7 +357,7 @@ def compare_point_clouds(est_scan, gt_scan, output_dir, f_score_threshold, voxel
     if len(est_scan) == 0 or len(gt_scan) == 0:
         raise ValueError(f"compare_point_clouds: {len(est_scan)} estimated and {len(gt_scan)} ground-truth points after down-sampling")
     if refine_alignment:
-        reg = refine_alignment_icp(est_scan, gt_scan)
+        reg = refine_alignment_icp(est_scan, gt_scan, alignment_kernel)
         est_scan.transform(reg.transformation)
         if alignment is not None:
             alignment.update(reg.as_dict())

@@ -21,6 +21,7 @@ LOSS_RAYS_PER_BLOCK = 4      # LNR_LOSS_RAYS_PER_BLOCK
 FRONT_HEADER = 4             # LNR_FRONT_HEADER
 KNN_MAX = 32                 # LNR_KNN_MAX
 ICP_RESULT = 64              # LNR_ICP_RESULT
+ROBUST_KERNELS = {"l2": 0, "huber": 1, "cauchy": 2, "tukey": 3}      # LNR_ROBUST_*
 MOCOMP_CONSTS = 30           # LNR_MOCOMP_CONSTS
 SKY_MAX_RAYS = 65160         # LNR_SKY_MAX_RAYS
 SCAN_MAX_FOV_SEGMENTS = 8    # LNR_SCAN_MAX_FOV_SEGMENTS
@@ -139,6 +140,11 @@ _SIGNATURES = {
     "lnr_icp_workspace": (C.c_size_t, [C.c_int64]),
     "lnr_icp_point_to_plane": (C.c_int, [P, C.c_int64, P, P, C.c_int64, C.c_double, C.POINTER(C.c_double), C.c_double, C.c_double,
                                          C.c_int32, P, C.c_size_t, P, P, P]),
+    "lnr_icp_point_to_plane_robust": (C.c_int, [P, C.c_int64, P, P, C.c_int64, C.c_double, C.POINTER(C.c_double), C.c_double, C.c_double,
+                                                C.c_int32, C.c_int32, C.c_double, P, C.c_size_t, P, P, P]),
+    "lnr_cloud_plane_covariances": (C.c_int, [P, C.c_int64, C.c_double, P, P]),
+    "lnr_icp_generalized": (C.c_int, [P, C.c_int64, P, P, P, C.c_int64, C.c_double, C.POINTER(C.c_double), C.c_double, C.c_double,
+                                      C.c_int32, C.c_int32, C.c_double, P, C.c_size_t, P, P, P]),
     "lnr_mesh_sample_workspace": (C.c_size_t, [C.c_int64]),
     "lnr_mesh_sample_points": (C.c_int, [P, C.c_int64, P, C.c_int64, C.c_int64, C.c_uint64, P, C.c_size_t, P, P, P, P]),
     "lnr_cloud_tools_workspace": (C.c_size_t, [C.c_int64]),

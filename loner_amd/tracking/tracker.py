@@ -1,5 +1,6 @@
 """Tracker: frame-to-frame LiDAR odometry by point-to-plane ICP (src/tracking/tracker.py:31-297), on HIP and without open3d, kornia
-or pytorch3d.
+or pytorch3d.  Two optional settings beyond the reference's choose another estimator: icp.estimation ("POINT_TO_PLANE", the default,
+or "GENERALIZED": analysis.registration's plane-to-plane ICP) and icp.robust_kernel ({type, k}; none by default).
 
 update() takes what the rgb and lidar signals hold, lets FrameSynthesis form frames, tracks each and emits it.  track_frame builds the
 frame's cloud (Frame.build_point_cloud -> ops.frame_cloud), registers it against the previous frame's cloud through the icp.schedule
@@ -7,7 +8,8 @@ frame's cloud (Frame.build_point_cloud -> ops.frame_cloud), registers it against
 (LidarScan.motion_compensate -> ops.motion_compensate).  compute_sky_rays fills frame.lidar_points.sky_rays (ops.sky_rays).
 Differences from the reference, by intent:
   * a cloud's normals are estimated once, when it becomes the ICP target (knn 30, open3d's default search); the reference also
-    estimates the source's, which point-to-plane ICP never reads;
+    estimates the source's, which point-to-plane ICP never reads; with GENERALIZED a cloud gets its plane covariances once, when it
+    is built (knn 20 and epsilon 1e-3, open3d's defaults), and keeps them when it becomes the target;
   * a stopped tracker ignores further update() calls;
   * run(), the multi-process orchestration and the synchronisation wait on the mapper are not here: update() is driven by the caller;
   * the debug PCD dumps (write_frame_point_clouds, write_icp_point_clouds) raise NotImplementedError when set;
@@ -27,6 +29,25 @@ from .frame_synthesis import FrameSynthesis
 
 NORMALS_KNN = 30            # open3d's estimate_normals() default: KDTreeSearchParamKNN(30)
 DOWNSAMPLE_TYPES = (None, "VOXEL", "UNIFORM")
+ESTIMATIONS = ("POINT_TO_PLANE", "GENERALIZED")
+GICP_KNN = 20               # open3d's registration_generalized_icp: KDTreeSearchParamKNN(20) for the clouds' covariances
+GICP_EPSILON = 1e-3         # TransformationEstimationForGeneralizedICP's default
+
+
+def _optional(block, key, default):
+    """block[key] of a settings block (a dict, or the reference's attrdict), `default` when the key is absent"""
+    return block.get(key, default) if hasattr(block, "get") else getattr(block, key, default)
+
+
+def robust_kernel_from_settings(entry):
+    """icp.robust_kernel -> analysis.registration.RobustKernel, or None for no entry: {type: L2 | HUBER | CAUCHY | TUKEY, k: scale}"""
+    from ..analysis.registration import RobustKernel
+    if entry is None:
+        return None
+    kind, k = _optional(entry, "type", None), _optional(entry, "k", 1.0)
+    if kind is None:
+        raise ValueError(f"Tracker: icp.robust_kernel needs a type, got {dict(entry)!r}")
+    return RobustKernel(str(kind).lower(), k)
 
 
 def _is_stop(value):
@@ -60,6 +81,10 @@ class Tracker:
                 raise NotImplementedError(f"Tracker: debug.{flag} (PCD dumps) is not supported")
         if self._settings.icp.downsample.type not in DOWNSAMPLE_TYPES:
             raise ValueError(f"Unrecognized downsample type {self._settings.icp.downsample.type}")
+        self._estimation = _optional(self._settings.icp, "estimation", "POINT_TO_PLANE")
+        if self._estimation not in ESTIMATIONS:
+            raise ValueError(f"Unrecognized icp.estimation {self._estimation!r} (one of {ESTIMATIONS})")
+        self._robust_kernel = robust_kernel_from_settings(_optional(self._settings.icp, "robust_kernel", None))
 
     def update(self) -> None:
         """One turn of the tracker: take at most one value from each input signal, then track and emit every frame that is ready.
@@ -120,17 +145,28 @@ class Tracker:
             raise ValueError(f"Unrecognized downsample type {kind}")
         wanted = icp.downsample.target_uniform_point_count if kind == "UNIFORM" else None
         cloud = frame.build_point_cloud(scan_duration=icp.scan_duration, target_points=wanted)
-        return cloud.voxel_down_sample(icp.downsample.voxel_downsample_size) if kind == "VOXEL" else cloud
+        cloud = cloud.voxel_down_sample(icp.downsample.voxel_downsample_size) if kind == "VOXEL" else cloud
+        if self._estimation == "GENERALIZED":
+            from ..analysis.registration import cloud_covariances
+            cloud.covariances = cloud_covariances(cloud, GICP_EPSILON, GICP_KNN)
+        return cloud
 
     def _register(self, cloud) -> np.ndarray:
         """The rigid motion (fp64 4x4) that lays `cloud` onto the reference cloud: icp.schedule from the identity, coarse to fine, every
         stage starting where the one before ended.  The stages' results stay in last_registrations."""
         from ..analysis.lidar_map import registration_icp
+        from ..analysis.registration import registration_generalized_icp, registration_icp_robust
         motion = np.eye(4)
         self.last_registrations = []
         for stage in self._settings.icp.schedule:
-            result = registration_icp(cloud, self._reference_point_cloud, stage.threshold, motion, stage.relative_fitness,
-                                      stage.relative_rmse, stage.max_iterations)
+            args = (cloud, self._reference_point_cloud, stage.threshold, motion, stage.relative_fitness, stage.relative_rmse,
+                    stage.max_iterations)
+            if self._estimation == "GENERALIZED":
+                result = registration_generalized_icp(*args, kernel=self._robust_kernel, epsilon=GICP_EPSILON, knn=GICP_KNN)
+            elif self._robust_kernel is not None:
+                result = registration_icp_robust(*args, kernel=self._robust_kernel)
+            else:
+                result = registration_icp(*args)
             self.last_registrations.append(result)
             motion = result.transformation.copy()
         if not np.isfinite(motion).all():
@@ -139,8 +175,9 @@ class Tracker:
 
     def _become_reference(self, cloud, pose_matrix, stamp) -> None:
         """The next frame is registered against this one: its cloud as built (never the compensated scan), with the normals
-        point-to-plane ICP needs of a target, its pose (kept on the host) and its middle time."""
-        self._reference_point_cloud = cloud.estimate_normals(NORMALS_KNN)
+        point-to-plane ICP needs of a target (generalized ICP reads the covariances the cloud was built with), its pose (kept on the
+        host) and its middle time."""
+        self._reference_point_cloud = cloud if self._estimation == "GENERALIZED" else cloud.estimate_normals(NORMALS_KNN)
         self._reference_pose = Pose(pose_matrix, fixed=True)
         self._reference_time = stamp
 
