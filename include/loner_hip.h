@@ -635,6 +635,99 @@ int lnr_icp_generalized(const void* grid, int64_t n_targets, const double* targe
                         double relative_fitness, double relative_rmse, int32_t max_iteration, int32_t kernel, double kernel_k,
                         void* workspace, size_t workspace_bytes, double* result_dev, int64_t* info_dev, void* stream);
 
+/* ---- global registration (open3d's compute_fpfh_feature, registration_ransac_based_on_feature_matching and ----------------------
+ *      registration_ransac_based_on_correspondence; Rusu et al., "Fast Point Feature Histograms (FPFH) for 3D Registration", ICRA 2009)
+ * A starting pose for the ICP entry points above, from two clouds alone.  Everything is fp64 without fma and rounds operation by
+ * operation; dot(a, b) = (a0 b0 + a1 b1) + a2 b2, cross(a, b) = (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0), |a| = sqrt(dot(a, a)),
+ * d2 as lnr_nn_distance's.  Two runs give the same bytes: no float atomics, no hand-over between workgroups inside a launch. */
+#define LNR_ORIENT_LOCATION 0
+#define LNR_ORIENT_DIRECTION 1
+#define LNR_FPFH_DIM 33
+#define LNR_FEATURE_DIM_MAX 64
+#define LNR_RANSAC_CHUNK 2048
+#define LNR_STREAM_RANSAC 0x524E534300000000ull   /* "RNSC" in the top word of the Philox counter's high half */
+
+/* open3d's OrientNormalsTowardsCameraLocation / OrientNormalsToAlignWithDirection, in place on normals [n,3].  reference host [3],
+ * finite.  LNR_ORIENT_LOCATION: with v_a = reference_a - p_i,a per axis, n_i is negated (each component) when dot(v, n_i) < 0;
+ * LNR_ORIENT_DIRECTION (points may be null): when dot(n_i, reference) < 0.  A zero or NaN dot product leaves the normal (open3d
+ * replaces a zero normal by the direction; this entry does not).  A normal with a non-finite component is left as it is and counted.
+ * counters_dev int64 [4], written by the call: {non-finite normals, normals flipped, 0, 0}. */
+int lnr_cloud_orient_normals(const double* points, int64_t n_points, double* normals, int32_t mode, const double* reference,
+                             int64_t* counters_dev, void* stream);
+
+/* The 20 literals of the FPFH angle bins: out[2 (b - 1)] = cos(theta_b), out[2 (b - 1) + 1] = sin(theta_b) with
+ * theta_b = -pi + 2 pi b / 11 for b = 1..10.  Host only. */
+int lnr_fpfh_bin_edges(double* out);
+
+/* open3d's ComputeFPFHFeature with KDTreeSearchParamHybrid(radius, max_nn) over the points a grid was built from (lnr_nn_grid_build),
+ * normals [n,3] in their input order; max_nn in [2, LNR_KNN_MAX] (open3d's default of 100 is out of range by intent: the neighbour
+ * list stays in registers), radius finite and > 0.  features fp64 [n, LNR_FPFH_DIM], row i = point i.
+ * Neighbours of i: of the min(max_nn, n) smallest (d2, input index) pairs of lnr_cloud_normals' search (the same shell walk, the same
+ * exact pass after 5 shells) those with d2 < radius * radius (strict, the product rounded once), less the entry whose index is i;
+ * m is their count, their order the list's.  (With more than max_nn exact duplicates before i the list does not hold i and m can
+ * reach max_nn.)
+ * Pair feature of (p1, n1) = point i and (p2, n2) = a neighbour: d = p2 - p1 per axis, f3 = |d|; a1 = dot(n1, d) / f3,
+ * a2 = dot(n2, d) / f3; if |a1| < |a2| the two normals are swapped, d is negated and f2 = -a2, else f2 = a1; v = cross(d, n1), each
+ * component divided by |v|; w = cross(n1, v); f1 = dot(v, n2); y = dot(w, n2), x = dot(n1, n2).  If f3 = 0 or |v| = 0, or either
+ * normal has a non-finite component, the pair counts as f1 = f2 = 0 and x = y = 0.
+ * Bins, 11 per feature: f1 and f2 go to floor(11 * ((f + 1) * 0.5)) clamped to [0, 10] (NaN: 0).  The angle atan2(y, x) is binned
+ * without libm, with (c_b, s_b) of lnr_fpfh_bin_edges: x = y = 0 gives 5; y < 0 gives the count of b in 1..5 with
+ * y * c_b - x * s_b >= 0; otherwise 5 + the count of b in 6..10 with y * c_b - x * s_b >= 0.  (This is floor(11 (atan2(y, x) + pi) /
+ * (2 pi)) clamped to 10 wherever the angle is not within rounding of an edge.)
+ * SPFH of i, open3d's row order: rows 0..10 the angle, 11..21 f1, 22..32 f2; each bin is (double) count * (100.0 / (double) m), all
+ * zero when m = 0.  Stated difference: open3d adds 100 / m once per neighbour.
+ * FPFH of i: acc_j and sum_b start at 0.0; over the neighbours k in list order with d2_k != 0 and then j = 0..32,
+ * val = spfh_k,j / d2_k, acc_j = acc_j + val, sum_{j / 11} = sum_{j / 11} + val; feature_j = acc_j * (100.0 / sum_{j / 11}) + spfh_i,j,
+ * and acc_j + spfh_i,j where the sum is 0.  An exact duplicate counts in m and is skipped in the weighting.
+ * A point whose own normal is not finite is counted; its pairs, and every pair that reads such a normal, are the zero pair above, so
+ * every feature stays finite.  workspace: lnr_cloud_fpfh_workspace(n) bytes (about 660 n; 0 = n out of range).
+ * counters_dev int64 [4], written by the call: {points that took the exact pass, 1 if the grid is unusable (a non-finite point, or
+ * another n: features is not written), shells visited, points whose own normal is not finite}. */
+size_t lnr_cloud_fpfh_workspace(int64_t n_points);
+int lnr_cloud_fpfh(const void* grid, int64_t n_points, const double* normals, double radius, int32_t max_nn, double* features,
+                   void* workspace, size_t workspace_bytes, int64_t* counters_dev, void* stream);
+
+/* The nearest target of every query in feature space, brute force and exact (the KDTreeFlann over features of
+ * registration_ransac_based_on_feature_matching).  targets [n_targets, dim] and queries [n_queries, dim], dim in
+ * [1, LNR_FEATURE_DIM_MAX].  d2 = the sum over j = 0..dim-1, left to right from 0.0, of (q_j - t_j) * (q_j - t_j); the answer is the
+ * target with the smallest (d2, index), the lower index winning a tie; a NaN d2 never wins.  index int32 [n_queries] (-1 for none)
+ * and sq_distance [n_queries] (+inf for none).  The targets are split into slices over the second grid dimension and a second launch
+ * takes the minimum of the slices' pairs; the order is total, so the result does not depend on the split.  split: 0 for the
+ * library's rule (about 512 workgroups), else the number of slices wanted, at most 512 (both are capped by the 64-row tiles there
+ * are).  workspace: lnr_feature_nearest_workspace(n_queries) bytes (0 = out of range). */
+size_t lnr_feature_nearest_workspace(int64_t n_queries);
+int lnr_feature_nearest(const double* targets, int64_t n_targets, const double* queries, int64_t n_queries, int32_t dim, int32_t split,
+                        int32_t* index, double* sq_distance, void* workspace, size_t workspace_bytes, void* stream);
+
+/* open3d's RegistrationRANSACBasedOnCorrespondence with a fixed number of hypotheses.  source [n_source,3], target [n_target,3],
+ * corr int32 [m,2] (source index, target index), n_hypotheses H in [1, 2^22], max_distance d finite and > 0, edge_similarity e in
+ * [0, 1] (0 switches the edge checker off).  Stated differences from open3d: H is a fixed count, there is no confidence-based early
+ * stop, so the work and the answer depend on the arguments only; a hypothesis' pose comes from the two triangle frames, not from a
+ * Kabsch fit of the sample; there is no final refit on the inliers.
+ * Hypothesis h = 0..H-1: (x0, x1, x2, _) = philox4x32_10 with counter low 64 bits h, high 64 bits LNR_STREAM_RANSAC, key seed;
+ * i_k = ((uint64) x_k * m) >> 32; sample k is correspondence i_k, (s_k, t_k) its source and target point.  In this order: two equal
+ * indices reject the hypothesis (repeated index); with e != 0, for (k, j) = (0,1), (1,2), (2,0), ls = sqrt(d2(s_k, s_j)) and
+ * lt = sqrt(d2(t_k, t_j)) (differences k minus j), rejected unless ls >= e * lt and lt >= e * ls (edge checker); the frame of
+ * (a, b, c) = the three points in draw order is e1 = (b - a) / |b - a| per component, nrm = cross(e1, c - a), e3 = nrm / |nrm|,
+ * e2 = cross(e3, e1), and a non-finite entry in the source's or the target's frame rejects the hypothesis (frame).  Otherwise
+ * R_ab = (et1_a es1_b + et2_a es2_b) + et3_a es3_b, the centroids are ((a + b) + c) / 3.0 per axis, and
+ * t_a = ct_a - ((R_a0 cs_0 + R_a1 cs_1) + R_a2 cs_2).
+ * Score: every correspondence i = 0..m-1 in order, p = R s_i + t with lnr_cloud_append_transformed's rounding, d2 = d2(p, t_i)
+ * (differences p minus t), an inlier when d2 < d * d.  The inlier d2 are summed left to right from 0.0 within each chunk of
+ * LNR_RANSAC_CHUNK correspondences and the chunk sums are added in chunk order; counts are integers.
+ * Best: the largest count, then the smallest sum, then the smallest h.
+ * result_dev fp64 [18]: [0:16] the 4x4 transformation (row-major), [16] fitness = count / m, [17] inlier_rmse = sqrt(sum / count),
+ * both 0 for a count of 0.  info_dev int64 [8]: {status, best h (-1 for none), its count, surviving hypotheses, rejected: repeated
+ * index, rejected: edge checker, rejected: frame, m}.  status bit 1: m < 3 (no hypothesis is formed: every counter is 0), 2: no
+ * hypothesis survived, 4: a correspondence index out of range (such a pair is never an inlier and spoils every frame it is in);
+ * with bit 1 or 2 the transformation is the identity and the count 0.
+ * workspace: lnr_ransac_workspace(m, H) bytes (48 m + 9 H + 12 H ceil(m / LNR_RANSAC_CHUNK), about; 0 = out of range). */
+size_t lnr_ransac_workspace(int64_t n_correspondences, int64_t n_hypotheses);
+int lnr_ransac_correspondence(const double* source, int64_t n_source, const double* target, int64_t n_target, const int32_t* corr,
+                              int64_t n_correspondences, int64_t n_hypotheses, uint64_t seed, double max_distance,
+                              double edge_similarity, void* workspace, size_t workspace_bytes, double* result_dev, int64_t* info_dev,
+                              void* stream);
+
 /* ---- mesh sampling, outlier filter, trajectory transform (analysis/compute_metrics/maps/mesh_to_pcd.py; ------------------------
  *      examples/fusion_portable/create_lidar_map.py, mask_gt_with_trajectory.py) ------------------------------------------------- */
 /* open3d's TriangleMesh::SamplePointsUniformly (mesh_to_pcd.py:22) with a defined order and counter-based draws.  vertices fp64

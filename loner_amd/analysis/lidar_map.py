@@ -69,6 +69,34 @@ class PointCloud:
             self.covariances = torch.zeros(0, 3, 3, dtype=torch.float64, device=self.points.device)
         return self
 
+    def _orient(self, what, **how):
+        if self.normals is None:
+            raise ValueError(f"{what}: the cloud has no normals (call estimate_normals())")
+        from .registration import orient_normals
+        orient_normals(self.normals, self.points, **how)
+        return self
+
+    def orient_normals_towards_location(self, location=(0.0, 0.0, 0.0)):
+        """open3d's orient_normals_towards_camera_location, in place (include/loner_hip.h: lnr_cloud_orient_normals): a normal is
+        flipped when it points away from `location`; non-finite normals are left as they are."""
+        return self._orient("orient_normals_towards_location", location=location)
+
+    def orient_normals_to_align_with_direction(self, direction=(0.0, 0.0, 1.0)):
+        """open3d's orient_normals_to_align_with_direction, in place: a normal is flipped when its dot product with `direction` is
+        negative."""
+        return self._orient("orient_normals_to_align_with_direction", direction=direction)
+
+    def compute_fpfh_feature(self, radius, max_nn=32, cell_edge=None):
+        """open3d's compute_fpfh_feature(cloud, KDTreeSearchParamHybrid(radius, max_nn)) (include/loner_hip.h: lnr_cloud_fpfh) ->
+        features [n,33] fp64 on the device, row i = point i (open3d's Feature.data transposed).  max_nn <= 32.  The cloud needs
+        normals, consistently oriented: FPFH depends on their sign."""
+        if self.normals is None:
+            raise ValueError("compute_fpfh_feature: the cloud has no normals (call estimate_normals() and orient them)")
+        if len(self) == 0:
+            return torch.zeros(0, 33, dtype=torch.float64, device=self.points.device)
+        from .registration import fpfh
+        return fpfh(ops.NNGrid(self.points, cell_edge), self.normals, radius, max_nn)
+
     def uniform_down_sample(self, every_k_points):
         """A new cloud of the points whose index i satisfies i % every_k_points == 0, in order (with their normals and covariances)."""
         k = int(every_k_points)
@@ -342,11 +370,15 @@ def refine_alignment_icp(est_scan, gt_scan, kernel=None):
 
 # ---------------------------------------------------------------- evaluation
 def compare_point_clouds(est_scan, gt_scan, output_dir, f_score_threshold, voxel_size=0.05, write_pointclouds=False,
-                         write_gt_cloud=False, id_str=None, refine_alignment=False, alignment=None, alignment_kernel=None):
+                         write_gt_cloud=False, id_str=None, refine_alignment=False, alignment=None, alignment_kernel=None,
+                         global_alignment=False):
     """Accuracy, completion, Chamfer distance, precision, recall and F-score of est_scan against gt_scan after down-sampling both
     (evaluate_lidar_map.py:16-98).  refine_alignment: first move the down-sampled estimate by point-to-plane ICP
     (refine_alignment_icp; evaluate_lidar_map.py:23-53); alignment (a dict, optional) receives the ICP result; alignment_kernel (an
-    analysis.registration.RobustKernel, optional) is the refinement's loss.  Writes
+    analysis.registration.RobustKernel, optional) is the refinement's loss.  global_alignment: before that, move the down-sampled
+    estimate onto the ground truth by analysis.registration.global_registration (for maps that are metres or a half turn apart, where
+    ICP from the identity finds nothing): True for its defaults at 10 voxel_size, or a dict of its keyword arguments (voxel_size,
+    orient, hypotheses, seed); alignment["global"] receives its result.  Writes
     {output_dir}/metrics/statistics{_id}.yaml and, when asked, lidar_renders/rendered{_id}.pcd and gt{_id}.pcd; returns the
     statistics.  Quirks kept: precision = TP / len(accuracy), recall = TP / (TP + FN) with TP counted on the estimate and FN on the
     ground truth, and 1e-8 in the F-score's denominator."""
@@ -356,6 +388,15 @@ def compare_point_clouds(est_scan, gt_scan, output_dir, f_score_threshold, voxel
     gt_scan = gt_scan.voxel_down_sample(voxel_size)
     if len(est_scan) == 0 or len(gt_scan) == 0:
         raise ValueError(f"compare_point_clouds: {len(est_scan)} estimated and {len(gt_scan)} ground-truth points after down-sampling")
+    if global_alignment:
+        from .registration import global_registration
+        print("Aligning the clouds globally")
+        how = dict(global_alignment) if isinstance(global_alignment, dict) else {}
+        how.setdefault("voxel_size", 10.0 * voxel_size)
+        rough = global_registration(est_scan, gt_scan, kernel=alignment_kernel, **how)
+        est_scan.transform(rough.transformation)
+        if alignment is not None:
+            alignment["global"] = rough.as_dict()
     if refine_alignment:
         reg = refine_alignment_icp(est_scan, gt_scan, alignment_kernel)
         est_scan.transform(reg.transformation)
@@ -400,13 +441,14 @@ def compare_point_clouds(est_scan, gt_scan, output_dir, f_score_threshold, voxel
 
 
 def evaluate_lidar_map(experiment_directory, gt_map, gt_trajectory=None, estimated_map=None, f_score_threshold=0.1, voxel_size=0.05,
-                       initial_transform=None, est_traj=None, alignment=None):
+                       initial_transform=None, est_traj=None, alignment=None, global_alignment=False):
     """The entry point of evaluate_lidar_map.py (:101-148) with the refinement on: reads the estimated map (default
     {experiment_directory}/lidar_renders/render_full.pcd, else {experiment_directory}/{estimated_map}) and gt_map, rough-aligns the
     ground truth by the inverse of initial_transform (16 numbers, row-major) or of the first pose of the TUM trajectory gt_trajectory,
     and the estimate by the inverse of est_traj's first pose when given, then scores them (compare_point_clouds, refine_alignment=True).
     The reference's rounding is kept: both start poses are fp32 (torch.tensor of the list; build_poses_from_df's .float()), inverted in
-    fp32 and widened.  Returns the statistics."""
+    fp32 and widened.  global_alignment: compare_point_clouds', for maps without a trajectory to rough-align them by.  Returns the
+    statistics."""
     from ..common.pose_utils import build_poses_from_df, read_tum
     est_map_path = (f"{experiment_directory}/lidar_renders/render_full.pcd" if estimated_map is None
                     else f"{experiment_directory}/{estimated_map}")
@@ -426,4 +468,4 @@ def evaluate_lidar_map(experiment_directory, gt_map, gt_trajectory=None, estimat
         est_map.transform(start_est_pose.inverse().cpu().numpy())
     gt_map.transform(start_pose.inverse().cpu().numpy())
     return compare_point_clouds(est_map, gt_map, experiment_directory, f_score_threshold, voxel_size, refine_alignment=True,
-                                alignment=alignment)
+                                alignment=alignment, global_alignment=global_alignment)

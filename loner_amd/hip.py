@@ -22,6 +22,12 @@ FRONT_HEADER = 4             # LNR_FRONT_HEADER
 KNN_MAX = 32                 # LNR_KNN_MAX
 ICP_RESULT = 64              # LNR_ICP_RESULT
 ROBUST_KERNELS = {"l2": 0, "huber": 1, "cauchy": 2, "tukey": 3}      # LNR_ROBUST_*
+ORIENT_LOCATION, ORIENT_DIRECTION = 0, 1     # LNR_ORIENT_*
+FPFH_DIM = 33                # LNR_FPFH_DIM
+FEATURE_DIM_MAX = 64         # LNR_FEATURE_DIM_MAX
+RANSAC_CHUNK = 2048          # LNR_RANSAC_CHUNK
+RANSAC_MAX_HYPOTHESES = 1 << 22
+STREAM_RANSAC = 0x524E534300000000           # LNR_STREAM_RANSAC
 MOCOMP_CONSTS = 30           # LNR_MOCOMP_CONSTS
 SKY_MAX_RAYS = 65160         # LNR_SKY_MAX_RAYS
 SCAN_MAX_FOV_SEGMENTS = 8    # LNR_SCAN_MAX_FOV_SEGMENTS
@@ -145,6 +151,15 @@ _SIGNATURES = {
     "lnr_cloud_plane_covariances": (C.c_int, [P, C.c_int64, C.c_double, P, P]),
     "lnr_icp_generalized": (C.c_int, [P, C.c_int64, P, P, P, C.c_int64, C.c_double, C.POINTER(C.c_double), C.c_double, C.c_double,
                                       C.c_int32, C.c_int32, C.c_double, P, C.c_size_t, P, P, P]),
+    "lnr_cloud_orient_normals": (C.c_int, [P, C.c_int64, P, C.c_int32, C.POINTER(C.c_double), P, P]),
+    "lnr_fpfh_bin_edges": (C.c_int, [P]),
+    "lnr_cloud_fpfh_workspace": (C.c_size_t, [C.c_int64]),
+    "lnr_cloud_fpfh": (C.c_int, [P, C.c_int64, P, C.c_double, C.c_int32, P, P, C.c_size_t, P, P]),
+    "lnr_feature_nearest_workspace": (C.c_size_t, [C.c_int64]),
+    "lnr_feature_nearest": (C.c_int, [P, C.c_int64, P, C.c_int64, C.c_int32, C.c_int32, P, P, P, C.c_size_t, P]),
+    "lnr_ransac_workspace": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "lnr_ransac_correspondence": (C.c_int, [P, C.c_int64, P, C.c_int64, P, C.c_int64, C.c_int64, C.c_uint64, C.c_double, C.c_double, P,
+                                            C.c_size_t, P, P, P]),
     "lnr_mesh_sample_workspace": (C.c_size_t, [C.c_int64]),
     "lnr_mesh_sample_points": (C.c_int, [P, C.c_int64, P, C.c_int64, C.c_int64, C.c_uint64, P, C.c_size_t, P, P, P, P]),
     "lnr_cloud_tools_workspace": (C.c_size_t, [C.c_int64]),
