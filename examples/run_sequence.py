@@ -1,6 +1,6 @@
 """Run LiDAR SLAM on a folder of scans.
 
-    python examples/run_sequence.py <folder> [--gt poses_tum.txt] [--gt-mesh mesh.ply [--mesh-resolution 0.1] [--tsdf-baseline]]
+    python examples/run_sequence.py <folder> [--gt poses_tum.txt] [--gt-mesh mesh.ply [--mesh-resolution 0.1] [--tsdf-baseline [--tsdf-sparse]]]
                                     [--out ~/LonerSLAM/outputs] [--name run] [--ray-range 1 50]
                                     [--icp-estimation GENERALIZED] [--icp-kernel tukey 3]
 
@@ -13,7 +13,9 @@ by 1 m, written to <log>/meshes/, and scored against that mesh with the exact po
 (mesh_eval.evaluate_mesh_to_mesh).  With --tsdf-baseline (needs --gt-mesh) the scan files are then read again and fused into a TSDF
 volume (analysis/tsdf.py) along estimated_trajectory.txt and, with --gt, along the ground truth, every ray from the pose at its own
 time; both volumes are meshed at --mesh-resolution over the same box, written beside the neural mesh and scored the same way: the
-ground-truth one shows what the scans support at that resolution, the estimated one what the tracking costs.  The log directory holds the checkpoints, the four trajectory files and the configuration, as the
+ground-truth one shows what the scans support at that resolution, the estimated one what the tracking costs.  With --tsdf-sparse
+(only with --tsdf-baseline) the volumes are SparseTSDFVolumes over the same box: the same meshes and scores from the blocks the rays
+wrote to instead of the whole lattice.  The log directory holds the checkpoints, the four trajectory files and the configuration, as the
 analysis tools of this package expect them."""
 import argparse
 import glob
@@ -40,6 +42,7 @@ def main():
     ap.add_argument("--gt-mesh")
     ap.add_argument("--mesh-resolution", type=float, default=0.1)
     ap.add_argument("--tsdf-baseline", action="store_true")
+    ap.add_argument("--tsdf-sparse", action="store_true", help="with --tsdf-baseline: fuse into a block-sparse volume")
     ap.add_argument("--out", default="~/LonerSLAM/outputs")
     ap.add_argument("--name", default=None)
     ap.add_argument("--ray-range", type=float, nargs=2, default=(1.0, 50.0))
@@ -94,9 +97,9 @@ def main():
         device = loner._mapper._optimizer._device
         scans = reread_scans(files, stamps, fov, device)
         tsdf_baseline("estimated trajectory", "estimated", scans, os.path.join(log, "trajectory", "estimated_trajectory.txt"), args.gt_mesh,
-                      args.mesh_resolution, log, device)
+                      args.mesh_resolution, log, device, args.tsdf_sparse)
         if args.gt:
-            tsdf_baseline("ground-truth trajectory", "gt", scans, args.gt, args.gt_mesh, args.mesh_resolution, log, device)
+            tsdf_baseline("ground-truth trajectory", "gt", scans, args.gt, args.gt_mesh, args.mesh_resolution, log, device, args.tsdf_sparse)
 
 
 def score_against_mesh(loner, gt_mesh_path, resolution, ray_range, log):
@@ -133,18 +136,20 @@ def reread_scans(files, stamps, fov, device):
     return scans
 
 
-def tsdf_baseline(what, tag, scans, trajectory, gt_mesh_path, resolution, log, device):
+def tsdf_baseline(what, tag, scans, trajectory, gt_mesh_path, resolution, log, device, sparse=False):
     """Fuse the scans along a trajectory (a TUM file) into a TSDF volume over the neural mesh's box, mesh it at the same resolution,
-    write it beside the neural mesh and print the same evaluate_mesh_to_mesh line"""
+    write it beside the neural mesh and print the same evaluate_mesh_to_mesh line; sparse: a SparseTSDFVolume over the same box"""
     from loner_amd.analysis.mesh_eval import evaluate_mesh_to_mesh
     from loner_amd.analysis.mesher import TriangleMesh
     from loner_amd.analysis.tsdf import fuse_scans
     gt_mesh = TriangleMesh.read_ply(gt_mesh_path)
     bound = (gt_mesh.vertices.min(axis=0) - 1.0, gt_mesh.vertices.max(axis=0) + 1.0)
     stats = {}
-    volume = fuse_scans(scans, trajectory, bound, resolution, device=device, stats=stats)
+    volume = fuse_scans(scans, trajectory, bound, resolution, device=device, stats=stats, sparse=sparse)
     print(f"TSDF on the {what}: {stats['scans'] - stats['skipped_scans']} of {stats['scans']} scans fused (a scan whose sweep leaves "
-          f"the trajectory's time span is left out), {stats.get('node_updates', 0)} node updates")
+          f"the trajectory's time span is left out), {stats.get('node_updates', 0)} node updates" +
+          (f", {volume.n_blocks} blocks of 8 x 8 x 8 nodes ({volume.memory_bytes() / 2 ** 20:.1f} MiB in blocks, "
+           f"{volume.allocated_bytes() / 2 ** 20:.1f} MiB allocated)" if sparse else ""))
     mesh = volume.extract_mesh()
     if mesh is None:
         print(f"TSDF on the {what} against the ground-truth mesh: the volume has no surface to score")

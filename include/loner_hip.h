@@ -1042,6 +1042,83 @@ int lnr_tsdf_integrate(const double* rays, const double* ranges, int64_t n_rays,
 int lnr_tsdf_field(const int64_t* sum, const uint32_t* count, int32_t nx, int32_t ny, int32_t nz, uint32_t min_count, float* field,
                    uint8_t* valid, void* stream);
 
+/* ---- sparse TSDF (open3d's ScalableTSDFVolume / VoxelBlockGrid for range rays) ------------------------------------------------ */
+/* A sparse volume IS the dense volume of lnr_tsdf_integrate over a lattice of nx ny nz nodes, of which only the blocks a ray wrote to
+ * are stored: each axis has 2 <= n <= 2^21 nodes and there is no limit on the product.  Origin, voxel_size, trunc, front and the grid
+ * frame, the slab clip against [0, n_a], the walk with its tie rule, s and q, and the invalid and miss classes are those of "TSDF
+ * fusion" above, word for word and with the same operation-by-operation fp64 arithmetic.  So for every lattice a dense volume can
+ * hold, every node of the sparse volume has the dense volume's sum and count, bit for bit.
+ *
+ * Blocks.  A block is 8 x 8 x 8 nodes; the block of node (i, j, k) is (i >> 3, j >> 3, k >> 3) and its key bx << 36 | by << 18 | bz:
+ * 18 bits per axis, at most 54.  A block exists if and only if some ray wrote one of its nodes (s >= -trunc at a visited voxel); a
+ * block that was only visited does not exist.  Nodes of a block with an index >= n_a on some axis are never written and never valid.
+ *
+ * Directory.  keys uint64 [B], ascending and unique, with a parallel slot uint32 [B]: block slot owns sum int64 [512] and count uint32
+ * [512] in the caller's pool arrays [capacity][8][8][8], z fastest, zeroed by the caller.  An existing block keeps its slot for life.
+ * The blocks a call creates take the slots B_old, B_old + 1, ... in ascending key order.  A lookup is a binary search over keys.
+ * Hence the pool is a function of the sequence of the calls' ray sets, and the volume in directory order (ascending key) is a function
+ * of the set of all rays, whatever their order, their split into calls, or the run.
+ *
+ * One integration is four calls on one stream, with rays, ranges, the lattice and the parameters as lnr_tsdf_integrate takes them, the
+ * same in each.  The host reads a count after the first and after the second, because the pool is the caller's and grows there:
+ *   lnr_tsdf_sparse_touch      walks the rays without writing.  A ray has a candidate at every written voxel whose block is not the
+ *                              block of the voxel it wrote before and is not in the directory (keys [n_blocks]).  ray_offsets uint32
+ *                              [n_rays + 1] gets the exclusive scan of the rays' candidate counts, counts_dev int64 [2] = {candidates, 0}.
+ *   lnr_tsdf_sparse_insert     (n_candidates >= 1: the count read back) walks the rays that have a candidate again, sorts the candidate
+ *                              keys (stable LSD radix, as many 8-bit passes as the lattice's highest key needs) and keeps the distinct
+ *                              ones in the workspace; counts_dev[1] = their number, B_new.
+ *   lnr_tsdf_sparse_merge      (n_new >= 1: B_new read back; the workspace of the insert, untouched, and the same n_candidates) sorts
+ *                              the pairs (keys, slot) [n_blocks] and (new key r, n_blocks + r) into keys_out, slot_out [n_blocks + n_new],
+ *                              which may be keys and slot themselves.
+ *   lnr_tsdf_sparse_integrate  (keys, slot [n_blocks]: the directory after the merge, n_new of its blocks new; capacity >= n_blocks
+ *                              blocks in sum and count) runs the walk and per written voxel resolves block to slot - a ray searches
+ *                              only when the block changes - and issues the two atomics of the dense call.  A written voxel whose
+ *                              block the search does not find, or finds with a slot >= capacity, writes nothing and is counted.
+ *                              info_dev int64 [8], written by the call: {status (0), rays that updated at least one node, invalid rays,
+ *                              rays that miss the box, node updates, new blocks, blocks, lost updates}; lost updates is 0 whenever the
+ *                              four calls saw the same rays.
+ * With no candidate, insert and merge are skipped.  lnr_tsdf_sparse_workspace: the bytes that serve a touch of n_rays rays and an
+ * insert and merge that sort n_sort = n_blocks + n_candidates pairs (either may be 0); 0 for a count out of range (n_rays < 2^32 - 256,
+ * n_sort <= 2^31 - 4096).
+ *
+ * lnr_tsdf_sparse_field writes field fp32 and valid uint8 [n_blocks][8][8][8] in directory order, gathered through slot, with
+ * lnr_tsdf_field's expression and min_count rule (1 <= n_blocks < 2^22). */
+size_t lnr_tsdf_sparse_workspace(int64_t n_rays, int64_t n_sort);
+int lnr_tsdf_sparse_touch(const double* rays, const double* ranges, int64_t n_rays, int32_t nx, int32_t ny, int32_t nz,
+                          const double* origin /*host [3]*/, double voxel_size, double trunc, double front, const uint64_t* keys,
+                          int64_t n_blocks, uint32_t* ray_offsets, void* workspace, size_t workspace_bytes, int64_t* counts_dev,
+                          void* stream);
+int lnr_tsdf_sparse_insert(const double* rays, const double* ranges, int64_t n_rays, int32_t nx, int32_t ny, int32_t nz,
+                           const double* origin /*host [3]*/, double voxel_size, double trunc, double front, const uint64_t* keys,
+                           int64_t n_blocks, const uint32_t* ray_offsets, int64_t n_candidates, void* workspace, size_t workspace_bytes,
+                           int64_t* counts_dev, void* stream);
+int lnr_tsdf_sparse_merge(const uint64_t* keys, const uint32_t* slot, int64_t n_blocks, int64_t n_new, int64_t n_candidates, int32_t nx,
+                          int32_t ny, int32_t nz, void* workspace, size_t workspace_bytes, uint64_t* keys_out, uint32_t* slot_out,
+                          void* stream);
+int lnr_tsdf_sparse_integrate(const double* rays, const double* ranges, int64_t n_rays, int32_t nx, int32_t ny, int32_t nz,
+                              const double* origin /*host [3]*/, double voxel_size, double trunc, double front, const uint64_t* keys,
+                              const uint32_t* slot, int64_t n_blocks, int64_t n_new, int64_t capacity, int64_t* sum, uint32_t* count,
+                              int64_t* info_dev, void* stream);
+int lnr_tsdf_sparse_field(const int64_t* sum, const uint32_t* count, const uint32_t* slot, int64_t n_blocks, int64_t capacity,
+                          uint32_t min_count, float* field, uint8_t* valid, void* stream);
+
+/* Marching cubes over the blocks of a directory (keys uint64 [n_blocks], ascending, unique and inside the lattice; 1 <= n_blocks <
+ * 2^22), with field fp32 and valid uint8 [n_blocks][8][8][8] in directory order: the two-call protocol of lnr_mc_count / lnr_mc_emit
+ * (totals_dev uint64 [2] = {vertices, triangles} read back by the caller, the same workspace in both calls, V < 2^30).  The definition
+ * is that of lnr_mc_*_masked on the full lattice of nx ny nz nodes with every node of a missing block not valid: a vertex sits on every
+ * lattice edge whose ends are both valid and differ, owned by the lower node; a cell is named by its lower node, which may lie in any
+ * block, with its other corners in up to seven neighbouring blocks, and emits its case's triangles only when all eight corners are
+ * valid; nodes with index n_a - 1 name no cell, and a valid byte of a node with an index >= n_a is not read.  Coordinates use global
+ * indices in the dense formula, ((float) index + t) * spacing + origin with each operation rounded in fp32.  Order: blocks in
+ * directory order, then nodes in block-local order (z fastest), then axis; triangles follow cell order, then the case table's order.
+ * The mesh therefore equals the dense masked mesh as a set: the same triangles with the same nine floats each, in another order. */
+size_t lnr_mc_sparse_workspace(int64_t n_blocks);
+int lnr_mc_sparse_count(const uint64_t* keys, int64_t n_blocks, const float* field, const uint8_t* valid, int32_t nx, int32_t ny, int32_t nz,
+                        float level, void* workspace, size_t workspace_bytes, uint64_t* totals_dev, void* stream);
+int lnr_mc_sparse_emit(const uint64_t* keys, int64_t n_blocks, const float* field, const uint8_t* valid, int32_t nx, int32_t ny, int32_t nz,
+                       float level, const float* spacing /*host [3]*/, const float* origin /*host [3]*/, void* workspace,
+                       size_t workspace_bytes, int64_t n_verts, int64_t n_tris, float* verts, int32_t* tris, void* stream);
+
 /* ---- tracking(src/common/frame.py:104-145; src/common/sensors.py:176-232; src/tracking/tracker.py:257-297) ----------------- */
 #define LNR_MOCOMP_CONSTS 30      /* fp64 entries of lnr_motion_compensate's consts */
 #define LNR_SKY_MAX_RAYS 65160    /* 181 x 360: the row stride lnr_sky_rays' output needs */

@@ -186,6 +186,19 @@ _SIGNATURES = {
     "lnr_tsdf_integrate": (C.c_int, [P, P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_double, C.c_double,
                                      C.c_double, P, P, P, P]),
     "lnr_tsdf_field": (C.c_int, [P, P, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, P, P, P]),
+    "lnr_tsdf_sparse_workspace": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "lnr_tsdf_sparse_touch": (C.c_int, [P, P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_double, C.c_double,
+                                        C.c_double, P, C.c_int64, P, P, C.c_size_t, P, P]),
+    "lnr_tsdf_sparse_insert": (C.c_int, [P, P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_double, C.c_double,
+                                         C.c_double, P, C.c_int64, P, C.c_int64, P, C.c_size_t, P, P]),
+    "lnr_tsdf_sparse_merge": (C.c_int, [P, P, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, P, C.c_size_t, P, P, P]),
+    "lnr_tsdf_sparse_integrate": (C.c_int, [P, P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_double, C.c_double,
+                                            C.c_double, P, P, C.c_int64, C.c_int64, C.c_int64, P, P, P, P]),
+    "lnr_tsdf_sparse_field": (C.c_int, [P, P, P, C.c_int64, C.c_int64, C.c_uint32, P, P, P]),
+    "lnr_mc_sparse_workspace": (C.c_size_t, [C.c_int64]),
+    "lnr_mc_sparse_count": (C.c_int, [P, C.c_int64, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_float, P, C.c_size_t, P, P]),
+    "lnr_mc_sparse_emit": (C.c_int, [P, C.c_int64, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.POINTER(C.c_float),
+                                     C.POINTER(C.c_float), P, C.c_size_t, C.c_int64, C.c_int64, P, P, P]),
     "lnr_frame_cloud": (C.c_int, [P, P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, P, P]),
     "lnr_motion_compensate": (C.c_int, [P, P, P, C.c_int32, C.c_int64, C.c_double, C.c_double, C.POINTER(C.c_double), P]),
     "lnr_sky_rays_workspace": (C.c_size_t, []),
