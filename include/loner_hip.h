@@ -728,6 +728,66 @@ int lnr_ransac_correspondence(const double* source, int64_t n_source, const doub
                               double edge_similarity, void* workspace, size_t workspace_bytes, double* result_dev, int64_t* info_dev,
                               void* stream);
 
+/* ---- segmentation (open3d's PointCloud::RemoveRadiusOutliers, ClusterDBSCAN and SegmentPlane; Ester et al., "A Density-Based -----
+ *      Algorithm for Discovering Clusters", KDD 1996; Fischler and Bolles, "Random Sample Consensus", CACM 1981) ----------------------
+ * Taking a cloud apart.  Everything is fp64 without fma and rounds operation by operation; dot, cross and |a| are the global
+ * registration block's, d2(p, q) = (dx dx + dy dy) + dz dz with d = p - q per axis (lnr_nn_distance's; it is symmetric bit for bit).
+ * Integer atomics only, no hand-over or waiting between workgroups inside a launch, every loop bounded by the call's arguments: two
+ * runs give the same bytes. */
+#define LNR_STREAM_PLANE 0x504C414E00000000ull    /* "PLAN" in the top word of the Philox counter's high half */
+
+/* For every point i of the cloud a grid was built from (lnr_nn_grid_build), counts[i] (uint32, input order) = the number of points j,
+ * i included, with d2(p_i, p_j) < radius * radius (strict, the product rounded once: lnr_icp_correspondences' rule).  radius finite
+ * and > 0.  The walk covers at most ceil(radius / edge) + 1 shells of cells, as lnr_icp_correspondences' does (the one past
+ * ceil(radius / edge) covers the rounding of the two cell assignments), and ends sooner once the shells' lower bound reaches
+ * radius^2; the counts do not depend on the grid's edge.  PointCloud.remove_radius_outlier keeps point i when counts[i] > nb_points
+ * (open3d's rule, whose count includes i).  counters_dev int64 [4], written by the call: {0, 1 if the grid is unusable (a non-finite
+ * point, or another n: counts is not written), shells walked, 0}. */
+int lnr_cloud_radius_count(const void* grid, int64_t n_points, double radius, uint32_t* counts, int64_t* counters_dev, void* stream);
+
+/* open3d's ClusterDBSCAN over the points a grid was built from; eps finite and > 0, min_points >= 1.  With count_i as
+ * lnr_cloud_radius_count's at radius eps: point i is a core when count_i >= min_points; two cores are adjacent when
+ * d2 < eps * eps; a cluster is a connected component of cores; clusters are numbered 0, 1, ... by ascending smallest core index; a
+ * core gets its cluster's number, a non-core with at least one core within d2 < eps * eps (a border point) the smallest number among
+ * those cores' clusters, every other point (noise) -1.  These are the labels of open3d's sequential algorithm (indices in ascending
+ * order, a breadth-first walk from every unvisited core, a noise point re-labelled by the first cluster that reaches it); they
+ * depend on the order of the input only through the numbering.  labels int32 [n] in input order.
+ * info_dev int64 [8], written by the call: {status, clusters, cores, border points, noise points, 0, 0, 0}; status bit 1: the grid
+ * holds a non-finite point, 2: the grid is unusable (that, or built for another n); with a bit set every label is -1 and the counts
+ * are 0.  workspace: lnr_cloud_dbscan_workspace(n) bytes (about 17 n; 0 = n out of range). */
+size_t lnr_cloud_dbscan_workspace(int64_t n_points);
+int lnr_cloud_dbscan(const void* grid, int64_t n_points, double eps, int32_t min_points, int32_t* labels, void* workspace,
+                     size_t workspace_bytes, int64_t* info_dev, void* stream);
+
+/* open3d's SegmentPlane with ransac_n = 3 and a fixed number of hypotheses.  points [n,3], distance_threshold t finite and > 0,
+ * n_hypotheses H in [1, 2^22].  Stated differences from open3d: the sample size is always 3; H is a fixed count, there is no
+ * probability-based stop; the draws are counter-based, so the result depends on the arguments only.
+ * Hypothesis h = 0..H-1: (x0, x1, x2, _) = philox4x32_10 with counter low 64 bits h, high 64 bits LNR_STREAM_PLANE, key seed;
+ * i_k = ((uint64) x_k * n) >> 32.  Two equal indices reject the hypothesis (repeated).  With a, b, c the three points in draw order:
+ * nrm = cross(b - a, c - a) (differences per axis), L = |nrm|, nv = nrm / L per component, d = -dot(nv, a); L == 0, or a non-finite
+ * L, nv component or d, rejects it (degenerate).
+ * Score: for every point i = 0..n-1 in order e = dot(nv, p_i) + d, an inlier when |e| < t (strict; a NaN is never an inlier); e * e
+ * of the inliers is summed left to right from 0.0 within each chunk of LNR_RANSAC_CHUNK points and the chunk sums are added in chunk
+ * order (lnr_ransac_correspondence's rule); counts are integers.
+ * Best: the largest count, then the smallest sum, then the smallest h.  inlier uint8 [n]: the best hypothesis's mask (open3d's
+ * returned inliers precede its refit too).
+ * Refit (refine != 0 and at least 3 inliers; otherwise the returned model is the hypothesis's): with q_i = p_i - a per axis, a the
+ * best hypothesis's first sample point, the 9 cumulants (qx, qy, qz, qx qx, qx qy, qx qz, qy qy, qy qz, qz qz) are summed over the
+ * points in lnr_cloud_outlier_threshold's order (thread j of block b adds its terms i = 256 b + j, + 256 B, ... in turn from 0.0,
+ * B = min(ceil(n / 256), 2048); a block sums its threads by the xor butterfly of each wave and the four waves left to right; one
+ * workgroup folds the B partials the same way), a point that is no inlier adding 0.0; each sum is divided by (double) count and the
+ * covariance formed as lnr_cloud_normals forms it (C_xx = m_xx - m_x m_x, ...); the normal is FastEigen3x3's unit eigenvector of the
+ * smallest eigenvalue with lnr_cloud_normals' degenerate-case rules, negated per component when its dot product with nv is negative;
+ * the centroid is a + (m_x, m_y, m_z) per axis and d = -dot(normal, centroid).
+ * plane_dev fp64 [8]: [0:4] the returned model (a, b, c, d), [4:8] the best hypothesis's own model.  info_dev int64 [8]: {status,
+ * best h (-1 for none), its count, surviving hypotheses, rejected: repeated, rejected: degenerate, non-finite points, n}; status bit
+ * 1: n < 3 (no hypothesis is formed), 2: no hypothesis survived; with either the plane is zeros and the mask empty.
+ * workspace: lnr_plane_workspace(n, H) bytes (H + 12 H ceil(n / LNR_RANSAC_CHUNK) + 256 Ki, about; 0 = out of range). */
+size_t lnr_plane_workspace(int64_t n_points, int64_t n_hypotheses);
+int lnr_cloud_segment_plane(const double* points, int64_t n_points, double distance_threshold, int64_t n_hypotheses, uint64_t seed,
+                            int32_t refine, double* plane_dev, uint8_t* inlier, void* workspace, size_t workspace_bytes,
+                            int64_t* info_dev, void* stream);
+
 /* ---- mesh sampling, outlier filter, trajectory transform (analysis/compute_metrics/maps/mesh_to_pcd.py; ------------------------
  *      examples/fusion_portable/create_lidar_map.py, mask_gt_with_trajectory.py) ------------------------------------------------- */
 /* open3d's TriangleMesh::SamplePointsUniformly (mesh_to_pcd.py:22) with a defined order and counter-based draws.  vertices fp64

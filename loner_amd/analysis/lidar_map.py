@@ -125,6 +125,72 @@ class PointCloud:
         out.covariances = None if self.covariances is None else self.covariances[index].contiguous()
         return out, index
 
+    def select_by_index(self, index):
+        """A new cloud of the points at `index` (int64 on the device), with their normals and covariances."""
+        out = PointCloud(self.points[index])
+        out.normals = None if self.normals is None else self.normals[index].contiguous()
+        out.covariances = None if self.covariances is None else self.covariances[index].contiguous()
+        return out
+
+    def remove_radius_outlier(self, nb_points, radius):
+        """open3d's remove_radius_outlier -> (a new cloud of the kept points in input order, with their normals and covariances;
+        their indices, int64 on the device).  A point is kept when more than nb_points points lie within `radius` of it (d2 <
+        radius^2, strict), itself counted as open3d counts it (include/loner_hip.h: lnr_cloud_radius_count).  The search grid's cell
+        edge is the radius; the result does not depend on it."""
+        from ..ops._common import _positive
+        from .segmentation import radius_count
+        r = _positive(radius, "remove_radius_outlier", "radius")
+        if int(nb_points) != nb_points or nb_points < 0:
+            raise ValueError(f"remove_radius_outlier: nb_points must be an integer >= 0, got {nb_points!r}")
+        if len(self) == 0:
+            return PointCloud(self.points.clone()), torch.zeros(0, dtype=torch.int64, device=self.points.device)
+        index = (radius_count(ops.NNGrid(self.points, r), r) > int(nb_points)).nonzero().squeeze(1)
+        return self.select_by_index(index), index
+
+    def cluster_dbscan(self, eps, min_points, info=None):
+        """open3d's cluster_dbscan -> labels int32 [n] on the device, -1 for noise (include/loner_hip.h: lnr_cloud_dbscan): clusters
+        are the connected components of the core points (at least min_points points within eps, itself counted), numbered by their
+        smallest core index; a border point takes the smallest label among the cores within eps.  These are open3d's labels, and
+        two runs give the same bytes.  info (a dict, optional) receives {clusters, cores, border, noise} (one device -> host read).
+        The search grid's cell edge is eps."""
+        from .segmentation import dbscan, dbscan_args
+        e, k = dbscan_args("cluster_dbscan", eps, min_points)
+        if len(self) == 0:
+            if info is not None:
+                info.update(clusters=0, cores=0, border=0, noise=0)
+            return torch.zeros(0, dtype=torch.int32, device=self.points.device)
+        labels, words = dbscan(ops.NNGrid(self.points, e), e, k)
+        if info is not None:
+            w = [int(x) for x in words.cpu()]
+            info.update(clusters=w[1], cores=w[2], border=w[3], noise=w[4])
+        return labels
+
+    def remove_small_clusters(self, eps, min_points, min_cluster_points):
+        """The floaters of a cloud, as meshes have remove_small_components -> (a new cloud, the kept indices int64 on the device):
+        the points whose DBSCAN cluster (cluster_dbscan(eps, min_points)) has at least min_cluster_points members; noise goes.  The
+        cluster sizes are a histogram on the device."""
+        if int(min_cluster_points) != min_cluster_points or min_cluster_points < 0:
+            raise ValueError(f"remove_small_clusters: min_cluster_points must be an integer >= 0, got {min_cluster_points!r}")
+        labels = self.cluster_dbscan(eps, min_points).to(torch.int64)
+        if len(self) == 0:
+            return PointCloud(self.points.clone()), labels
+        sizes = torch.bincount(labels + 1)                       # slot 0: noise
+        sizes[0] = -1
+        index = (sizes[labels + 1] >= int(min_cluster_points)).nonzero().squeeze(1)
+        return self.select_by_index(index), index
+
+    def segment_plane(self, distance_threshold, num_iterations=1000, seed=0, refine=True, info=None):
+        """open3d's segment_plane with ransac_n = 3 (include/loner_hip.h: lnr_cloud_segment_plane) -> (plane_model numpy fp64 [4]
+        (a, b, c, d), the inliers' indices int64 on the device, ascending).  num_iterations is the fixed number of hypotheses (no
+        probability-based stop) and the draws are counter-based: the result depends on the arguments only.  The inliers are the best
+        hypothesis's, as open3d's are; with refine the model is refitted to them.  Fewer than 3 points, or no usable hypothesis:
+        a zero model and no inliers.  info (a dict, optional) receives analysis.segmentation.plane_ransac's dictionary."""
+        from .segmentation import plane_ransac
+        out = plane_ransac(self.points, distance_threshold, num_iterations, seed, refine)
+        if info is not None:
+            info.update(out)
+        return out["plane"], out["inlier"].nonzero().squeeze(1)
+
     def __len__(self):
         return int(self.points.shape[0])
 
@@ -371,18 +437,28 @@ def refine_alignment_icp(est_scan, gt_scan, kernel=None):
 # ---------------------------------------------------------------- evaluation
 def compare_point_clouds(est_scan, gt_scan, output_dir, f_score_threshold, voxel_size=0.05, write_pointclouds=False,
                          write_gt_cloud=False, id_str=None, refine_alignment=False, alignment=None, alignment_kernel=None,
-                         global_alignment=False):
+                         global_alignment=False, min_cluster_points=0, cluster_eps=None, cluster_min_points=4):
     """Accuracy, completion, Chamfer distance, precision, recall and F-score of est_scan against gt_scan after down-sampling both
     (evaluate_lidar_map.py:16-98).  refine_alignment: first move the down-sampled estimate by point-to-plane ICP
     (refine_alignment_icp; evaluate_lidar_map.py:23-53); alignment (a dict, optional) receives the ICP result; alignment_kernel (an
     analysis.registration.RobustKernel, optional) is the refinement's loss.  global_alignment: before that, move the down-sampled
     estimate onto the ground truth by analysis.registration.global_registration (for maps that are metres or a half turn apart, where
     ICP from the identity finds nothing): True for its defaults at 10 voxel_size, or a dict of its keyword arguments (voxel_size,
-    orient, hypotheses, seed); alignment["global"] receives its result.  Writes
+    orient, hypotheses, seed); alignment["global"] receives its result.  min_cluster_points > 0: before anything else the floaters
+    of the *estimated* cloud go (PointCloud.remove_small_clusters(cluster_eps or 2 * voxel_size, cluster_min_points,
+    min_cluster_points) on the cloud as given), and the statistics gain "removed_floaters", the number of points removed; with 0
+    nothing changes.  Writes
     {output_dir}/metrics/statistics{_id}.yaml and, when asked, lidar_renders/rendered{_id}.pcd and gt{_id}.pcd; returns the
     statistics.  Quirks kept: precision = TP / len(accuracy), recall = TP / (TP + FN) with TP counted on the estimate and FN on the
     ground truth, and 1e-8 in the F-score's denominator."""
     import yaml
+    removed = None
+    if min_cluster_points > 0:
+        eps = 2.0 * voxel_size if cluster_eps is None else cluster_eps
+        print(f"Removing clusters of fewer than {min_cluster_points} points (eps {eps})")
+        kept, _ = est_scan.remove_small_clusters(eps, cluster_min_points, min_cluster_points)
+        removed = len(est_scan) - len(kept)
+        est_scan = kept
     print("Downsampling clouds to voxel size", voxel_size)
     est_scan = est_scan.voxel_down_sample(voxel_size)
     gt_scan = gt_scan.voxel_down_sample(voxel_size)
@@ -425,6 +501,8 @@ def compare_point_clouds(est_scan, gt_scan, output_dir, f_score_threshold, voxel
         "f-score": f_score,
         "num_points": len(accuracy)
     }
+    if removed is not None:
+        stats["removed_floaters"] = removed
 
     metrics_dir = f"{output_dir}/metrics"
     os.makedirs(metrics_dir, exist_ok=True)
@@ -441,14 +519,15 @@ def compare_point_clouds(est_scan, gt_scan, output_dir, f_score_threshold, voxel
 
 
 def evaluate_lidar_map(experiment_directory, gt_map, gt_trajectory=None, estimated_map=None, f_score_threshold=0.1, voxel_size=0.05,
-                       initial_transform=None, est_traj=None, alignment=None, global_alignment=False):
+                       initial_transform=None, est_traj=None, alignment=None, global_alignment=False, min_cluster_points=0,
+                       cluster_eps=None):
     """The entry point of evaluate_lidar_map.py (:101-148) with the refinement on: reads the estimated map (default
     {experiment_directory}/lidar_renders/render_full.pcd, else {experiment_directory}/{estimated_map}) and gt_map, rough-aligns the
     ground truth by the inverse of initial_transform (16 numbers, row-major) or of the first pose of the TUM trajectory gt_trajectory,
     and the estimate by the inverse of est_traj's first pose when given, then scores them (compare_point_clouds, refine_alignment=True).
     The reference's rounding is kept: both start poses are fp32 (torch.tensor of the list; build_poses_from_df's .float()), inverted in
-    fp32 and widened.  global_alignment: compare_point_clouds', for maps without a trajectory to rough-align them by.  Returns the
-    statistics."""
+    fp32 and widened.  global_alignment: compare_point_clouds', for maps without a trajectory to rough-align them by; min_cluster_points and
+    cluster_eps: compare_point_clouds' floater removal (off at 0).  Returns the statistics."""
     from ..common.pose_utils import build_poses_from_df, read_tum
     est_map_path = (f"{experiment_directory}/lidar_renders/render_full.pcd" if estimated_map is None
                     else f"{experiment_directory}/{estimated_map}")
@@ -468,4 +547,5 @@ def evaluate_lidar_map(experiment_directory, gt_map, gt_trajectory=None, estimat
         est_map.transform(start_est_pose.inverse().cpu().numpy())
     gt_map.transform(start_pose.inverse().cpu().numpy())
     return compare_point_clouds(est_map, gt_map, experiment_directory, f_score_threshold, voxel_size, refine_alignment=True,
-                                alignment=alignment, global_alignment=global_alignment)
+                                alignment=alignment, global_alignment=global_alignment, min_cluster_points=min_cluster_points,
+                                cluster_eps=cluster_eps)

@@ -17,6 +17,7 @@
 //   select     keep flags per triangle and vertex, their exclusive scans, and the emit through the vertex scan
 //   normals    keys (vertex << 2 | corner) with the triangle as payload, sorted; the thread at the head of a vertex's run walks it
 #include "lnr_mesh_head.h"
+#include "lnr_union_find.h"
 
 namespace {
 
@@ -42,34 +43,6 @@ __global__ __launch_bounds__(CL_BLOCK) void cc_keys(const int32_t* __restrict__ 
         idx[3 * (size_t)t + k] = t;
     }
     if (!ok) atomicOr(&h->status, (uint32_t)MT_ST_BAD_INDEX);
-}
-
-// parents are read past the per-CU cache: a lane must see the hooks of other CUs, or it would retry on a stale root for ever
-__device__ inline uint32_t uf_load(uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// the root above x.  A parent is smaller than its child (uf_unite), so the walk ends whatever other lanes do meanwhile; on the way each
-// node is pointed at its grandparent (atomicMin: an ancestor, and never above a closer one written since)
-__device__ inline uint32_t uf_find(uint32_t* parent, uint32_t x) {
-    for (;;) {
-        const uint32_t p = uf_load(parent + x);
-        if (p == x) return x;
-        const uint32_t g = uf_load(parent + p);
-        if (g != p) atomicMin(parent + x, g);
-        x = p;
-    }
-}
-
-// max(a, b) falls with every failed swap, so the loop ends; it never waits for another lane
-__device__ inline void uf_unite(uint32_t* parent, uint32_t a, uint32_t b) {
-    for (;;) {
-        a = uf_find(parent, a);
-        b = uf_find(parent, b);
-        if (a == b) return;
-        if (a < b) { const uint32_t s = a; a = b; b = s; }
-        const uint32_t old = atomicCAS(parent + a, a, b);
-        if (old == a) return;
-        a = old;                                                        // a was hooked meanwhile, under old < a
-    }
 }
 
 __global__ __launch_bounds__(CL_BLOCK) void cc_link(SortedPairs sp, uint32_t* __restrict__ parent, const MeshSortHead* __restrict__ h) {

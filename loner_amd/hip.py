@@ -28,6 +28,7 @@ FEATURE_DIM_MAX = 64         # LNR_FEATURE_DIM_MAX
 RANSAC_CHUNK = 2048          # LNR_RANSAC_CHUNK
 RANSAC_MAX_HYPOTHESES = 1 << 22
 STREAM_RANSAC = 0x524E534300000000           # LNR_STREAM_RANSAC
+STREAM_PLANE = 0x504C414E00000000            # LNR_STREAM_PLANE
 MOCOMP_CONSTS = 30           # LNR_MOCOMP_CONSTS
 SKY_MAX_RAYS = 65160         # LNR_SKY_MAX_RAYS
 SCAN_MAX_FOV_SEGMENTS = 8    # LNR_SCAN_MAX_FOV_SEGMENTS
@@ -160,6 +161,11 @@ _SIGNATURES = {
     "lnr_ransac_workspace": (C.c_size_t, [C.c_int64, C.c_int64]),
     "lnr_ransac_correspondence": (C.c_int, [P, C.c_int64, P, C.c_int64, P, C.c_int64, C.c_int64, C.c_uint64, C.c_double, C.c_double, P,
                                             C.c_size_t, P, P, P]),
+    "lnr_cloud_radius_count": (C.c_int, [P, C.c_int64, C.c_double, P, P, P]),
+    "lnr_cloud_dbscan_workspace": (C.c_size_t, [C.c_int64]),
+    "lnr_cloud_dbscan": (C.c_int, [P, C.c_int64, C.c_double, C.c_int32, P, P, C.c_size_t, P, P]),
+    "lnr_plane_workspace": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "lnr_cloud_segment_plane": (C.c_int, [P, C.c_int64, C.c_double, C.c_int64, C.c_uint64, C.c_int32, P, P, P, C.c_size_t, P, P]),
     "lnr_mesh_sample_workspace": (C.c_size_t, [C.c_int64]),
     "lnr_mesh_sample_points": (C.c_int, [P, C.c_int64, P, C.c_int64, C.c_int64, C.c_uint64, P, C.c_size_t, P, P, P, P]),
     "lnr_cloud_tools_workspace": (C.c_size_t, [C.c_int64]),
