@@ -33,6 +33,7 @@ extern "C" {
 
 #define LNR_RAY_STRIDE 13
 #define LNR_LOSS_RAYS_PER_BLOCK 4
+#define LNR_LOSS_MAX_SAMPLES 1024   /* lnr_los_loss_fused refuses more samples per ray (LNR_ERR_UNSUPPORTED) */
 #define LNR_MAX_LEVELS 32
 
 typedef enum LnrStatus {
@@ -1291,7 +1292,10 @@ int lnr_render_ftb_composite(const float* sigma_c /*[cap,256]*/, const float* z,
  * block_partials (nullable) [ceil(n_rays / LNR_LOSS_RAYS_PER_BLOCK) * 8] scratch: with it the terms are summed
  * without atomics (deterministic, and ~0.25 ms faster at 4096 rays than 20 k same-address atomics);
  * ray_stats (nullable) [n,8]: {depth, opacity, variance, mean_m, std_m, js, eps, opaque}.
- * weights_out (nullable) [n,S]. */
+ * weights_out (nullable) [n,S].
+ * n_samples: 2 .. LNR_LOSS_MAX_SAMPLES.  More is refused with LNR_ERR_UNSUPPORTED before anything is launched, also for n_rays = 0:
+ * the 32-samples-per-lane instantiation (1024 < S <= 2048) ended in a memory fault on its first launch and is not built (DESIGN.md
+ * 3.5); lnr_render_forward / lnr_render_backward keep their 2048. */
 int lnr_count_opaque(const float* rays, const float* depth_gt, int32_t n_rays, const int32_t* n_rays_dev,
                      const float* far0_dev, int32_t* counts_dev /*[2], overwritten*/, void* stream);
 int lnr_los_loss_fused(const float* sigma, const float* z, const float* rays, const float* depth_gt,

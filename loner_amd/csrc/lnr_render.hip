@@ -528,6 +528,21 @@ extern "C" int lnr_count_opaque(const float* rays, const float* depth_gt, int32_
     return LNR_OK;
 }
 
+// The fused loss stops at 16 samples per lane: los_loss_fused_kernel<32> is not instantiated, and the entry refuses
+// n_samples > LNR_LOSS_MAX_SAMPLES before it gets here.
+static_assert(LNR_LOSS_MAX_SAMPLES == 64 * 16, "the fused loss's dispatch ends at C = 16");
+#define DISPATCH_LOSS_C(S, CALL)                               \
+    switch (chunk_for(S)) {                                    \
+        case 1: { constexpr int C = 1; CALL; } break;          \
+        case 2: { constexpr int C = 2; CALL; } break;          \
+        case 4: { constexpr int C = 4; CALL; } break;          \
+        case 8: { constexpr int C = 8; CALL; } break;          \
+        case 16: { constexpr int C = 16; CALL; } break;        \
+        default:                                               \
+            lnr_set_error("lnr_los_loss_fused: n_samples=%d not supported (max %d)", S, LNR_LOSS_MAX_SAMPLES); \
+            return LNR_ERR_UNSUPPORTED;                        \
+    }
+
 extern "C" int lnr_los_loss_fused(const float* sigma, const float* z, const float* rays, const float* depth_gt, int32_t n_rays,
                                   const int32_t* n_rays_dev, int32_t n_samples, const float* noise, float noise_std, uint64_t seed,
                                   float scale, const LnrLossConfig* cfg, const int32_t* counts_dev, const float* far0_dev, float* loss_out,
@@ -537,12 +552,16 @@ extern "C" int lnr_los_loss_fused(const float* sigma, const float* z, const floa
     LNR_REQUIRE(poison_dev == nullptr || block_partials != nullptr, "lnr_los_loss_fused: the failure guard needs block_partials (the deterministic reduction)");
     LNR_REQUIRE(cfg->selection >= 0 && cfg->selection <= 3, "lnr_los_loss_fused: unknown loss selection %d", cfg->selection);
     LNR_REQUIRE(n_rays >= 0 && n_samples >= 2, "lnr_los_loss_fused: bad sizes");
+    if (n_samples > LNR_LOSS_MAX_SAMPLES) {
+        lnr_set_error("lnr_los_loss_fused: n_samples=%d not supported (max %d)", n_samples, LNR_LOSS_MAX_SAMPLES);
+        return LNR_ERR_UNSUPPORTED;
+    }
     if (n_rays == 0) return LNR_OK;
     const dim3 grid(lnr_div_up(n_rays, RAYS_PER_BLOCK)), block(RENDER_BLOCK);
     hipStream_t st = (hipStream_t)stream;
-    DISPATCH_C(n_samples, hipLaunchKernelGGL(los_loss_fused_kernel<C>, grid, block, 0, st, sigma, z, rays, depth_gt, n_rays, n_rays_dev,
-                                             n_samples, noise, noise_std, seed, scale, *cfg, counts_dev, loss_out, d_sigma, d_rays,
-                                             ray_stats, weights_out, block_partials, far0_dev));
+    DISPATCH_LOSS_C(n_samples, hipLaunchKernelGGL(los_loss_fused_kernel<C>, grid, block, 0, st, sigma, z, rays, depth_gt, n_rays, n_rays_dev,
+                                                  n_samples, noise, noise_std, seed, scale, *cfg, counts_dev, loss_out, d_sigma, d_rays,
+                                                  ray_stats, weights_out, block_partials, far0_dev));
     LNR_CHECK_LAUNCH("lnr_los_loss_fused");
     if (block_partials) {
         hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(256), 0, st, block_partials, (int)grid.x, loss_out, poison_dev, poison_tag);

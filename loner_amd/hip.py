@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("LNR_LIB_PATH") or os.path.join(_HERE, "_lib", "liblon
 MAX_LEVELS = 32
 RAY_STRIDE = 13
 LOSS_RAYS_PER_BLOCK = 4      # LNR_LOSS_RAYS_PER_BLOCK
+LOSS_MAX_SAMPLES = 1024      # LNR_LOSS_MAX_SAMPLES: lnr_los_loss_fused refuses more samples per ray
 FRONT_HEADER = 4             # LNR_FRONT_HEADER
 KNN_MAX = 32                 # LNR_KNN_MAX
 ICP_RESULT = 64              # LNR_ICP_RESULT

@@ -21,10 +21,40 @@ float32 run need not show:
     factor.  It multiplies the weights' magnitude and the terms of `term_magnitudes`; a ray that is dense at all 2048 samples (ray 12
     of every case) is thus allowed 3e-4 of its largest weight, one with 20 samples in its surface 2e-6.
   - G of render_backward contains the variance's path through depth, itself a cancelling sum: `render_G_magnitude`.
-The per-ray statistics of the fused loss (mean, sd, js, eps) have no yardstick here: js is a function of g - mean, a difference of two
-50 m-sized numbers, and a bound for it has to come from that conditioning, not from the largest js of the case.
+The per-ray scalars depth, opacity and variance are sums over a ray's weights and are held per ray to `forward_magnitudes`, not to
+the largest entry of the case: measured on an MI355X at S = 2047, ray 3 (opacity 0.15: a thin surface of many small alphas) was off
+by 26 ulp of the case's largest variance and 7 ulp of its largest opacity, where the float32 run of one CPU was off by 1.3 and 0.3 and
+that of another by twice as much - 1.9 times the bound 4 x noise + 4 ulp of the largest entry with the first CPU's noise, 0.99 with
+the second's - and 0.012 of 4 ulp of the ray's own magnitude.  The far column of render_backward is gD_tot (1 - opacity) and inherits
+the same terms (`kernel_G_render`; 1.1 times its earlier bound at S = 2047 with the first CPU's noise).
+The per-ray statistics of the fused loss (mean, sd, js, eps: ray_stats columns 3..6) are held per ray to magnitudes that come from
+their conditioning (`statistics_magnitudes`), not from the largest entry of the case: js is a function of g - mean, a difference of
+two 50 m-sized numbers, and moves by |d js / d mean| times whatever the mean moves by.
+  - mean = sum s_i w_i / wden, wden = opacity + 1e-10: sum |s_i| w_i f_i / wden, f = the `growth` of the weights above.
+  - var = sum q_i^2 w_i / wden + 1e-10, q = s - mean: the sum of its terms, sum q_i^2 w_i f_i / wden + 1e-10, plus what the mean's
+    own error moves it by, |2 sum q_i w_i / wden| mag(mean) (the derivative with respect to the centre; nearly 0 about the true mean,
+    not about another centre).  sd = sqrt(var) follows through d sd / d var = 1 / (2 sd).
+  - js = gaussian_js(g, min_eps / 3, mean, sd): |d js / d mean| mag(mean) + |d js / d sd| mag(sd) from float64 autograd of the oracle's
+    gaussian_js, plus the sum of the absolute values of the terms of its two KL expressions (log, quotient, 0.5; each halved).
+  - eps = min_eps (1 + js_alpha score) under the JS selections: min_eps js_alpha mag(js).  Under the LOS selections eps is the
+    configured float32 number, bit for bit.
+Four terms that a float32 evaluation cannot avoid go beyond that list.  With the list alone the oracle's own float32 run errs by up to
+1000 times 4 ulp of sd's magnitude (S = 64, ray 19) and 63 times js's; with them it stays below 0.32 of 4 ulp of every magnitude, and
+a float32 run whose exponential leans by 2^-23 of its value at every sample below 0.63 (tests/test_render_host.py):
+  - alpha_i = 1 - e_i has no relative accuracy of its own: it carries the ABSOLUTE error of e_i, up to an ulp of e_i, however small
+    alpha_i is.  In a sum over the ray w_i enters with w_i f_i + e_i T_i / 2 where its density is positive (`weight_terms`), in mean and
+    var alike; on a ray of 1024 samples with alpha = 0.005 each that is 100 times the weights themselves.  At the other end, where
+    e_k is small, alpha_k = fl(1 - e_k) is rounded by a quarter of an ulp of 1 (or by all of e_k, if that is less), which the factor
+    tt_k = 1 - alpha_k + 1e-10 inherits as an absolute error: every weight behind a sample that absorbs nearly everything carries
+    min(e_k, ulp / 4) / tt_k relative, summed over such k in a_i (behind one factor tt = 5.7e-4, S = 2, ray 11: 1e-5 of the weight
+    that decides that ray's sd).
+  - s_i = z_i scale is rounded to float32 before mean is subtracted: q_i carries half an ulp of s_i, independently per sample, and var
+    moves by sum 2 |q_i| |s_i| w_i / wden.  (The list's |2 sum q_i w_i / wden| has the absolute value outside the sum: it covers a
+    common shift of every q_i, not this.)
+  - where var is its 1e-10 floor (one sample holds all the weight) the square of the mean's own error shows: 4 ulp mag(mean)^2.
+  - g = depth_gt scale is rounded to float32 as well, and js depends on g - mean: |d js / d mean| |g|.
 
-The fused loss must not be launched at S > 1024 for now (open defect)."""
+The fused loss refuses S > 1024 (LNR_LOSS_MAX_SAMPLES; DESIGN.md 3.5: refused, cause unknown): its cases are LOSS_SAMPLE_COUNTS."""
 import functools
 
 import torch
@@ -50,6 +80,8 @@ FIXED_EPS = f32(3.0 * 0.95 ** 3)             # the LOS selections' margin at ite
 DEPTH_LAMBDA = f32(0.005)
 TIER_EDGES = {1: (2, 63, 64), 2: (65, 128), 4: (129, 256), 8: (257, 512), 16: (513, 1000, 1024), 32: (1025, 2047, 2048)}
 SAMPLE_COUNTS = tuple(S for edges in TIER_EDGES.values() for S in edges)
+LOSS_MAX_SAMPLES = 1024                      # LNR_LOSS_MAX_SAMPLES: the fused loss refuses more
+LOSS_SAMPLE_COUNTS = tuple(S for S in SAMPLE_COUNTS if S <= LOSS_MAX_SAMPLES)
 
 
 def chunk_for(S):
@@ -218,8 +250,11 @@ def kernel_G_render(p, cot, slip=None):
     G = gO[:, None] + gD_tot[:, None] * (p["z"] - p["far"][:, None]) + gV[:, None] * q * q
     if cot.get("weights") is not None:
         G = G + cot["weights"].to(G.dtype)
-    gD_mag = gD.abs() + gV.abs() * 2.0 * (p["w"] * q.abs()).sum(1)
-    far_mag = gD_mag * (1.0 - p["opacity"]).abs()
+    # the far column gD_tot (1 - opacity): the terms of gD_tot with the weights at the size of what they are formed from and the depth
+    # inside q at its own magnitude, times |1 - opacity|; plus gD_tot times what the opacity itself can be off by (forward_magnitudes)
+    fm = forward_magnitudes(p)
+    gD_mag = gD.abs() + gV.abs() * 2.0 * ((weight_terms(p) * q.abs()).sum(1) + p["opacity"].abs() * fm["depth"])
+    far_mag = gD_mag * (1.0 - p["opacity"]).abs() + gD_tot.abs() * fm["opacity"]
     return G, gD_tot, far_mag
 
 
@@ -317,6 +352,88 @@ def total_G(dens, z, rays, scalar_of):
     return torch.autograd.grad(scalar_of(dict(weights=w, opacity=opacity, depth=depth, variance=variance)), w)[0]
 
 
+# ---------------------------------------------------------------- per-ray statistics of the fused loss (ray_stats columns 3..6)
+STAT_NAMES = ("mean", "sd", "js", "eps")
+STAT_SLIPS = ("f", "g", "h")
+
+
+def ray_statistics(p, depth_gt, selection, slip=None):
+    """mean, sd, js, eps [n,4] as los_loss_ray forms them from the parts, in the dtype of the parts.  Slips a kernel could make:
+    "f": the variance is taken about depth * scale (the rendered depth, which the kernel holds as well) instead of the mean;
+    "g": the variance's sum is not divided by wden;  "h": a js below min_js is not set to 0 before it selects the margin."""
+    cfg = loss_config(selection)
+    dtype = p["w"].dtype
+    s, g = p["z"] * SCALE, depth_gt.to(dtype) * SCALE
+    wden = p["opacity"] + 1e-10
+    mean = (s * p["w"]).sum(1) / wden
+    centre = p["depth"] * SCALE if slip == "f" else mean
+    v = ((s - centre[:, None]) ** 2 * p["w"]).sum(1)
+    sd = torch.sqrt((v if slip == "g" else v / wden) + 1e-10)
+    js = OL.gaussian_js(g, cfg.min_eps / 3.0, mean, sd)
+    if selection.endswith("JS"):
+        score = js.clone()
+        if slip != "h":
+            score[score < cfg.min_js] = 0
+        score[score > cfg.max_js] = cfg.max_js
+        eps = cfg.min_eps * (1 + cfg.js_alpha * score)
+    else:
+        eps = torch.full_like(js, FIXED_EPS)
+    return torch.stack([mean, sd, js, eps], dim=1)
+
+
+def weight_terms(p):
+    """per sample the size of what w_i = (1 - e_i) T_i is formed from, for sums over a ray: w_i (f_i + a_i) + e_i T_i / 2 (module
+    docstring; with the half the bound's 4 ulp allow e_i an error of 2^-22 e_i, which is 2 to 4 of its own ulps)"""
+    zero = torch.zeros_like(p["w"])
+    lost = torch.where(p["pos"], torch.clamp(p["e"] * 2.0 ** 21, max=1.0 / 16.0) / p["tt"], zero)      # min(e_k, ulp / 4) / tt_k over the bound's 4 ulp
+    absorbed = torch.cumsum(lost, dim=1) - lost
+    return p["w"] * (p["growth"] + absorbed) + torch.where(p["pos"], 0.5 * p["e"] * p["T"], zero)
+
+
+def forward_magnitudes(p):
+    """per ray the size of what opacity = sum w_i, depth = sum w_i z_i + (1 - opacity) far and variance = sum w_i (depth - z_i)^2 are
+    formed from -> dict of [n] (float64 parts): the weights enter as `weight_terms`; the depth inherits the opacity's through far, the
+    variance the depth's through d variance / d depth = 2 sum w_i q_i"""
+    assert p["w"].dtype == F64
+    wt = weight_terms(p)
+    opacity = wt.sum(1)
+    depth = (wt * p["z"].abs()).sum(1) + (1.0 - p["opacity"]).abs() * p["far"].abs() + opacity * p["far"].abs()
+    q = p["depth"][:, None] - p["z"]
+    variance = (wt * q * q).sum(1) + (2.0 * (p["w"] * q).sum(1)).abs() * depth
+    return dict(opacity=opacity, depth=depth, variance=variance)
+
+
+def statistics_magnitudes(p, depth_gt, selection):
+    """per ray the size of what mean, sd, js and eps are formed from (module docstring), from float64 parts -> [n,4]"""
+    assert p["w"].dtype == F64
+    cfg = loss_config(selection)
+    s, g = p["z"] * SCALE, depth_gt.double() * SCALE
+    w, wt = p["w"], weight_terms(p)
+    wden = p["opacity"] + 1e-10
+    mean = (s * w).sum(1) / wden
+    mean_mag = (s.abs() * wt).sum(1) / wden
+    q = s - mean[:, None]
+    var = (q * q * w).sum(1) / wden + 1e-10
+    var_mag = (q * q * wt).sum(1) / wden + 1e-10 + (2.0 * q.abs() * s.abs() * w).sum(1) / wden \
+        + (2.0 * (q * w).sum(1) / wden).abs() * mean_mag + 4.0 * F32_EPS * mean_mag ** 2
+    sd = torch.sqrt(var)
+    sd_mag = var_mag / (2.0 * sd)
+    m, d = mean.clone().requires_grad_(True), sd.clone().requires_grad_(True)
+    s1 = torch.full_like(g, cfg.min_eps / 3.0)
+    d_mean, d_sd = torch.autograd.grad(OL.gaussian_js(g, s1, m, d).sum(), (m, d))
+    mm, sm = 0.5 * (g + mean), 0.5 * torch.sqrt(s1 ** 2 + sd ** 2)
+    kl_terms = lambda m1, a, b: torch.log(b / a).abs() + (a * a + (m1 - mm) ** 2) / (2 * (b * b)) + 0.5
+    js_mag = d_mean.abs() * (mean_mag + g.abs()) + d_sd.abs() * sd_mag + 0.5 * kl_terms(g, s1, sm) + 0.5 * kl_terms(mean, sd, sm)
+    eps_mag = cfg.min_eps * cfg.js_alpha * js_mag if selection.endswith("JS") else torch.zeros_like(js_mag)
+    return torch.stack([mean_mag, sd_mag, js_mag, eps_mag], dim=1)
+
+
+def oracle_statistics(r, n):
+    """mean, sd, js, eps [n,4] of a loss_run"""
+    aux = r["aux"]
+    return torch.stack([aux["mean"], aux["std"], aux["js"], eps_of(aux, n, aux["js"].dtype)], dim=1)
+
+
 # ---------------------------------------------------------------- decisions
 def ulp32(x):
     return F32_EPS * x.abs()
@@ -355,8 +472,9 @@ def forward_reference(S):
     """the forward on the noisy density in float32 and float64, and the weights' magnitude per ray"""
     c = case(S)
     f64 = forward(_dd(c["dens"]), _dd(c["z"]), _dd(c["rays"]))
-    growth = ray_parts(_dd(c["dens"]), _dd(c["z"]), _dd(c["rays"]))["growth"]
-    return dict(f32=forward(c["dens"], c["z"], c["rays"]), f64=f64, weights_mag=(f64["weights"] * growth).max(1).values)
+    p = ray_parts(_dd(c["dens"]), _dd(c["z"]), _dd(c["rays"]))
+    return dict(f32=forward(c["dens"], c["z"], c["rays"]), f64=f64, weights_mag=(f64["weights"] * p["growth"]).max(1).values,
+                mag=forward_magnitudes(p))
 
 
 COTANGENT_SETS = ("all", "depth", "variance")
@@ -399,8 +517,9 @@ def loss_reference(S, selection):
     eps64 = eps_of(r64["aux"], n_rays, F64)
     pieces = loss_pieces(p, _dd(dgt), selection, float(far0), counts, eps64)
     ok = decided(z, dgt, far0, r64["aux"], r64["out"]["weights"], r64["aux"]["target"], selection)
+    stats = dict(f32=oracle_statistics(r32, n_rays), f64=ray_statistics(p, _dd(dgt), selection), mag=statistics_magnitudes(p, _dd(dgt), selection))
     return dict(r32=r32, r64=r64, counts=counts, opaque=opaque, far0=far0, M=M, D=D, far_mag=pieces["far_mag"], G=G, parts=p,
-                pieces=pieces, decided=ok, eps64=eps64)
+                pieces=pieces, decided=ok, eps64=eps64, stats=stats)
 
 
 def loss_terms(S, selection, keep, dtype):
@@ -452,6 +571,15 @@ def check_rows(led, name, x, x32, x64, mag=None, where=""):
     ok = True
     for i in range(x64.shape[0]):
         ok &= led.figures(name, float(err[i]), float(noise[i]), float(mag[i]), f"{where} ray {i}")
+    return ok
+
+
+def check_statistics(led, x, ref, keep, where="", prefix=""):
+    """mean, sd, js, eps (x [kept rays, 4]: ray_stats columns 3..6, or a slipped restatement's) per ray on the rays `keep`"""
+    st = ref["stats"]
+    ok = True
+    for k, name in enumerate(STAT_NAMES):
+        ok &= check_rows(led, prefix + name, x[:, k], st["f32"][keep, k], st["f64"][keep, k], st["mag"][keep, k], where)
     return ok
 
 

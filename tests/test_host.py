@@ -106,6 +106,29 @@ def test_bad_configs_fail_loudly(lib_path):
         hip.make_net_spec(dict(otype="HashGrid"), dict(n_neurons=64, output_activation="Sigmoid"))
 
 
+def test_fused_loss_refuses_more_than_1024_samples_before_anything_else(lib_path):
+    """n_rays = 0 reaches no launch on any build, so this runs on any machine: S = 1025 must be refused in the argument checks (before
+    the empty-batch return) with the limit in the message, S = 1024 is an empty batch like any other"""
+    from loner_amd import hip
+    lib = hip.load()
+    assert hip.LOSS_MAX_SAMPLES == 1024
+    header = open(os.path.join(ROOT, "include", "loner_hip.h")).read()
+    assert re.search(r"#define\s+LNR_LOSS_MAX_SAMPLES\s+1024\b", header)
+    cfg = hip.LossConfig(selection=0, min_js=1.0, max_js=10.0, js_alpha=1.0, los_lambda=1000.0, depth_lambda=0.005, min_eps=0.5, fixed_eps=3.0)
+    bufs = [(ctypes.c_float * 16)() for _ in range(7)]               # host memory: never dereferenced with n_rays = 0
+    sigma, z, rays, depth_gt, loss_out, d_sigma, d_rays = (ctypes.cast(b, ctypes.c_void_p) for b in bufs)
+    counts = ctypes.cast((ctypes.c_int32 * 2)(), ctypes.c_void_p)
+
+    def call(n_samples):
+        return lib.lnr_los_loss_fused(sigma, z, rays, depth_gt, 0, None, n_samples, None, 0.0, 0, 1.0, ctypes.byref(cfg), counts, None,
+                                      loss_out, d_sigma, d_rays, None, None, None, None, 0, None)
+    assert call(1025) == -2                                           # LNR_ERR_UNSUPPORTED
+    message = lib.lnr_last_error().decode()
+    assert "lnr_los_loss_fused" in message and "1025" in message and "1024" in message
+    assert call(2048) == -2 and call(4096) == -2
+    assert call(1024) == 0 and call(2) == 0                           # LNR_OK
+
+
 def test_no_cpu_fallback_and_product_never_imports_the_oracle(lib_path):
     from loner_amd import hip, ops
     spec = hip.make_net_spec(dict(otype="Frequency", n_frequencies=4), dict(n_neurons=16, n_hidden_layers=1))
