@@ -2,7 +2,7 @@
 
     python examples/run_sequence.py <folder> [--gt poses_tum.txt] [--gt-mesh mesh.ply [--mesh-resolution 0.1] [--tsdf-baseline [--tsdf-sparse]]]
                                     [--out ~/LonerSLAM/outputs] [--name run] [--ray-range 1 50]
-                                    [--icp-estimation GENERALIZED] [--icp-kernel tukey 3]
+                                    [--icp-estimation GENERALIZED] [--icp-kernel tukey 3] [--pose-graph]
 
 <folder> holds one `.npy` file per scan, [N,4] columns x, y, z, t (t: per-point time, local to the scan or global, seconds or
 nanoseconds), read in sorted name order, and `stamps.txt` with one scan time in seconds per line.  With --gt (a TUM file: ts x y z qx
@@ -16,7 +16,10 @@ time; both volumes are meshed at --mesh-resolution over the same box, written be
 ground-truth one shows what the scans support at that resolution, the estimated one what the tracking costs.  With --tsdf-sparse
 (only with --tsdf-baseline) the volumes are SparseTSDFVolumes over the same box: the same meshes and scores from the blocks the rays
 wrote to instead of the whole lattice.  The log directory holds the checkpoints, the four trajectory files and the configuration, as the
-analysis tools of this package expect them."""
+analysis tools of this package expect them.  With --pose-graph the scans are read again after the run, registered pairwise along
+estimated_trajectory.txt (consecutive scans, and scans whose estimated positions lie within --loop-radius and at least --loop-gap
+frames apart: no place recognition) and the pose graph is optimised (analysis/pose_graph.py); the result goes to
+trajectory/pose_graph_trajectory.txt beside the four files, and with --gt its APE is printed after the run's."""
 import argparse
 import glob
 import os
@@ -51,6 +54,10 @@ def main():
                     help="the tracker's estimator (tracker.icp.estimation)")
     ap.add_argument("--icp-kernel", nargs=2, metavar=("TYPE", "K"), default=None,
                     help="a robust loss on the tracker's ICP: huber, cauchy or tukey and its scale (tracker.icp.robust_kernel)")
+    ap.add_argument("--pose-graph", action="store_true", help="refine estimated_trajectory.txt by multiway registration")
+    ap.add_argument("--loop-radius", type=float, default=3.0, help="with --pose-graph: loop candidates lie within this distance (m)")
+    ap.add_argument("--loop-gap", type=int, default=4, help="with --pose-graph: and at least this many frames apart")
+    ap.add_argument("--pose-graph-distance", type=float, default=0.5, help="with --pose-graph: the correspondence distance (m)")
     args = ap.parse_args()
     if args.tsdf_baseline and not args.gt_mesh:
         raise SystemExit("--tsdf-baseline needs --gt-mesh")
@@ -91,6 +98,8 @@ def main():
     if args.gt:
         score = ape(os.path.join(log, "trajectory", "estimated_trajectory.txt"), args.gt)
         print("APE (aligned, m): " + ", ".join(f"{k} {score[k]:.4f}" for k in ("rmse", "mean", "median", "std", "min", "max")))
+    if args.pose_graph:
+        pose_graph_refine(files, stamps, fov, loner._mapper._optimizer._device, log, args)
     if args.gt_mesh:
         score_against_mesh(loner, args.gt_mesh, args.mesh_resolution, args.ray_range, log)
     if args.tsdf_baseline:
@@ -134,6 +143,27 @@ def reread_scans(files, stamps, fov, device):
         scan, _ = build_scan_from_points(points[:, :3].astype(np.float32), points[:, 3], float(stamp), fov=fov)
         scans.append(scan.to(device))
     return scans
+
+
+def pose_graph_refine(files, stamps, fov, device, log, args):
+    """Multiway registration of the scans along estimated_trajectory.txt -> trajectory/pose_graph_trajectory.txt"""
+    from loner_amd.analysis.pose_graph import refine_trajectory
+    est = os.path.join(log, "trajectory", "estimated_trajectory.txt")
+    out = os.path.join(log, "trajectory", "pose_graph_trajectory.txt")
+    rows = read_tum(est)
+    scan_idx, row_idx = associate(stamps, rows[:, 0], t_max_diff=1e-3)
+    scans = reread_scans([files[k] for k in scan_idx], stamps[scan_idx], fov, device)
+    info = {}
+    refine_trajectory(scans, rows[row_idx], out, args.pose_graph_distance, args.loop_radius, args.loop_gap, args.icp_estimation,
+                      voxel_size=0.1, info=info)
+    edges = info["edges"]
+    print(f"pose graph: {len(scans)} nodes, {sum(e['added'] for e in edges)} of {len(edges)} edges added "
+          f"({sum(e['added'] and e['uncertain'] for e in edges)} loop candidates), {len(info['pruned'])} pruned; "
+          f"{info['first']['trials']} + {info['second']['trials']} trials, stops {info['first']['stop_reason']} / {info['second']['stop_reason']}")
+    print(f"pose graph trajectory: {out}")
+    if args.gt:
+        score = ape(out, args.gt)
+        print("APE after the pose graph (aligned, m): " + ", ".join(f"{k} {score[k]:.4f}" for k in ("rmse", "mean", "median", "std", "min", "max")))
 
 
 def tsdf_baseline(what, tag, scans, trajectory, gt_mesh_path, resolution, log, device, sparse=False):

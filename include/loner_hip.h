@@ -1333,6 +1333,91 @@ int lnr_occ_grid_apply(float* grid, int64_t* grad_acc, int64_t count, float lr, 
  * the split itself must give back its input). */
 int lnr_selftest_mfma(float* out /*[3]*/, void* stream);
 
+/* ---- pose graph: multiway registration (open3d's GetInformationMatrixFromPointClouds, PoseGraph and GlobalOptimization with ------
+ *      Levenberg-Marquardt; Choi et al., "Robust Reconstruction of Indoor Scenes", CVPR 2015) ---------------------------------------
+ * Everything is fp64 without fma and rounds operation by operation.  Two runs give the same bytes: no float atomics, nothing handed
+ * between workgroups inside a launch, ordinary launches only. */
+
+/* The information matrix of a registered pair.  Each source point is moved by transformation (host [16], row-major, bottom row
+ * 0 0 0 1; lnr_cloud_append_transformed's rounding), then paired by lnr_icp_correspondences' rule (strict d2 < r r, ties by the lower
+ * index).  For every pair with the target q: G = [-[q]x | I] (3x6, rotation columns first: rows (0, q2, -q1, 1, 0, 0),
+ * (-q2, 0, q0, 0, 1, 0), (q1, -q0, 0, 0, 0, 1)) and the 21 upper-triangle terms (G0a G0b + G1a G1b) + G2a G2b are summed in the fixed
+ * order of the ICP systems.  workspace: lnr_icp_workspace(n_source) bytes.  result_dev fp64 [36]: the symmetric 6x6, row-major; all
+ * zeros without a correspondence, which is no error.  info_dev int64 [4]: {status, correspondences, non-finite source points, 0};
+ * status bits as lnr_icp_point_to_plane's: 1 a non-finite source point (it takes no correspondence), 2 the grid is unusable.  No host
+ * read. */
+int lnr_icp_information(const void* grid, int64_t n_targets, const double* source, int64_t n_source, const double* transformation,
+                        double max_distance, void* workspace, size_t workspace_bytes, double* result_dev, int64_t* info_dev,
+                        void* stream);
+
+/* The graph.  Node i has the pose T_i [16] (node frame to world, rigid).  Edge k = (s, t, X, L, uncertain): X [16] takes source-frame
+ * points to the target frame (ideally T_t^-1 T_s = X), L [36] is its information matrix, read as given and expected symmetric.
+ *   E = X^-1 T_t^-1 T_s (rigid inverses [R^T | -R^T t]; products ((a0 b0 + a1 b1) + a2 b2) + a3)
+ *   e = [(E21 - E12) / 2, (E02 - E20) / 2, (E10 - E01) / 2, E03, E13, E23]                   (0-based entries)
+ * A step moves a pose by T_i <- M(d_i) T_i with M lnr_icp_point_to_plane's update rule ([Rz(d2) Ry(d1) Rx(d0) | d3..d5], composed
+ * as there).  With A = X^-1 T_t^-1 and B = T_s, E(d_s, d_t) = A M(d_t)^-1 M(d_s) B, so at 0 dE/d d_s,c = A G_c B and
+ * dE/d d_t,c = -A G_c B (G_c the generator of component c): J_t = -J_s exactly.  J = J_s is, with e_c the unit vector and b_j column
+ * j of B's rotation,
+ *   c < 3:  N_c[r][j] = A_R[r] . (e_c x b_j);  J[0..2][c] = ((N_c)21 - (N_c)12, (N_c)02 - (N_c)20, (N_c)10 - (N_c)01) / 2;
+ *           J[3 + r][c] = A_R[r] . (e_c x B_t)
+ *   c >= 3: J[0..2][c] = 0;  J[3 + r][c] = A_R[r][c - 3]
+ * One block per edge carries the linearisation: W = J^T (L J) and g = J^T (L e); J_s^T L J_s = J_t^T L J_t = W, J_s^T L J_t = -W,
+ * and the edge adds -w g to b_s and +w g to b_t.  q = e^T (L e).  Weight w: 1 for a certain edge, the line-process value l for an
+ * uncertain one.  Objective F = sum w q + mu sum over uncertain edges of (sqrt(l) - 1)^2.
+ *
+ * Status bits of every info word 0 below: 1 an edge names a node out of range, 2 a self edge (both refused by lnr_pose_graph_build:
+ * the graph then takes part in nothing), 4 a non-finite pose, 8 a non-finite measurement or information matrix, 16 a breakdown of
+ * the conjugate gradients (p.Ap not > 0, or a non-finite sum). */
+#define LNR_PG_MAX_NODES (1 << 24)
+#define LNR_PG_MAX_EDGES (1 << 26)
+size_t lnr_pose_graph_bytes(int64_t n_nodes, int64_t n_edges);        /* the graph buffer; 0 outside the limits (n_nodes >= 1) */
+size_t lnr_pose_graph_workspace(int64_t n_nodes, int64_t n_edges);    /* the workspace of every call below */
+
+/* The CSR adjacency: node -> its incident slots, slot = 2 k + role (role 0: the node is edge k's source, 1: its target), from the
+ * keys (node, slot) by the shared radix sort, so every later gather walks a node's edges in edge order.  source, target int32 [m].
+ * info_dev int64 [4]: {status, edges with an id out of range, self edges, 0}.  No host read. */
+int lnr_pose_graph_build(const int32_t* source, const int32_t* target, int64_t n_nodes, int64_t n_edges, void* graph,
+                         size_t graph_bytes, void* workspace, size_t workspace_bytes, int64_t* info_dev, void* stream);
+
+/* Per edge e [m,6], q [m], W [m,36], g [m,6]; per node, through the adjacency and in its order, H_diag [n,36] = sum w W and
+ * b [n,6] = -sum w J_i^T L e.  reference_node (-1 for none): its block is the identity and its b zero; in the solve its row and
+ * column hold nothing else.  uncertain int32 [m], line fp64 [m] (read for uncertain edges).  info_dev int64 [4]: {status, 0, 0, 0}. */
+int lnr_pose_graph_linearize(const void* graph, int64_t n_nodes, int64_t n_edges, const int32_t* source, const int32_t* target,
+                             const double* poses, const double* measurements, const double* information, const int32_t* uncertain,
+                             const double* line, int32_t reference_node, double* e, double* q, double* W, double* g, double* H_diag,
+                             double* b, void* workspace, size_t workspace_bytes, int64_t* info_dev, void* stream);
+
+/* (H + lambda I) delta = b by conjugate gradients with the block-Jacobi preconditioner: each diagonal block H_ii + lambda I through
+ * lnr_icp_point_to_plane's pivoted LDLT, the product with H as a per-node gather over the adjacency (off-diagonal blocks -w W and
+ * -w W^T), dot products as per-block sums folded by one workgroup.  It stops on |r| <= rtol |b| or after max_cg iterations, decided
+ * on the device: every iteration is enqueued and later ones return at once.  Not a direct solve: delta carries an error of the order
+ * of cond(H + lambda I) rtol |delta|.  delta [n,6].  info_dev int64 [4]: {status, iterations, 1 if the tolerance was met (0: the
+ * max_cg stop), 0}.  No host read. */
+int lnr_pose_graph_solve(const void* graph, int64_t n_nodes, int64_t n_edges, const int32_t* source, const int32_t* target,
+                         const double* W, const int32_t* uncertain, const double* line, const double* H_diag, const double* b,
+                         double lambda, int32_t reference_node, double rtol, int32_t max_cg, void* workspace, size_t workspace_bytes,
+                         double* delta, int64_t* info_dev, void* stream);
+
+/* open3d's GlobalOptimizationLevenbergMarquardt with the line process.  poses [n,16] are updated in place; line [m] is set to 1 and
+ * receives the final line-process values.  mu = preference_loop_closure * max_correspondence_distance^2 * the mean of L[5][5] over
+ * the uncertain edges.  lambda0 = 1e-5 * the largest diagonal entry of H, nu = 2.  One trial: delta from lnr_pose_graph_solve's
+ * iteration at the current lambda; it stops (reason 2) when |delta| <= min_relative_increment (|x| + min_relative_increment), |x| the
+ * norm of all node positions; F_new at the trial poses with the current line values; rho = (F - F_new) / (delta . (lambda delta +
+ * b)).  rho > 0 accepts: lambda *= max(1/3, 1 - (2 rho - 1)^3), nu = 2, every uncertain edge's l = (mu / (mu + q))^2 at the new
+ * poses, and the system and F are formed again; then reason 3 when |b|_inf < min_right_term, 4 when F < min_residual, 1 after
+ * max_iteration accepted steps.  Otherwise lambda *= nu, nu *= 2, and reason 5 after max_iteration_lm rejections in a row.  Reason 6:
+ * a status bit.  The host reads one word per trial.  history_dev int32 [history_capacity] (nullable with capacity 0): per trial 1
+ * accepted, 0 rejected, -1 the relative-increment stop.  result_dev fp64 [4]: {F, |b|_inf, lambda, mu}.  info_dev int64 [8]:
+ * {status, trials, conjugate-gradient iterations of all trials, accepted, rejected, stop reason, 1 if stopped by a criterion (0: the
+ * trials ran out), trials whose solve ended on max_cg and not on rtol (their steps are inexact)}.  With mu = 0 (every uncertain
+ * edge's L[5][5] is 0) the line values stay 1. */
+int lnr_pose_graph_optimize(const void* graph, int64_t n_nodes, int64_t n_edges, const int32_t* source, const int32_t* target,
+                            double* poses, const double* measurements, const double* information, const int32_t* uncertain,
+                            double* line, int32_t reference_node, double max_correspondence_distance, double preference_loop_closure,
+                            int32_t max_iteration, int32_t max_iteration_lm, double min_relative_increment, double min_right_term,
+                            double min_residual, double rtol, int32_t max_cg, void* workspace, size_t workspace_bytes,
+                            int32_t* history_dev, int32_t history_capacity, double* result_dev, int64_t* info_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

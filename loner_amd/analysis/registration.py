@@ -17,6 +17,10 @@ Global registration, for two clouds without a starting pose (include/loner_hip.h
                                     hypotheses and triangle-frame poses -> RegistrationResult
   global_registration               down-sample, normals, orientation, FPFH, RANSAC, two rounds of point-to-plane ICP
 
+The information matrix of a registered pair, for the pose graph (analysis/pose_graph.py; include/loner_hip.h, "pose graph"):
+
+  icp_information, get_information_matrix_from_point_clouds     open3d's GetInformationMatrixFromPointClouds -> 6x6 fp64
+
 Limits of the global path, by intent: FPFH takes at most 32 neighbours (max_nn <= 32) and the feature search at most 64 dimensions
 (dim <= 64); the search is brute force and exact; the number of hypotheses is fixed (no confidence-based early stop), so the answer
 depends on the arguments and the seed only; a hypothesis' pose comes from the two triangle frames, not from a Kabsch fit; FPFH depends
@@ -394,3 +398,41 @@ def global_registration(source, target, voxel_size, orient=None, refine=True, ke
             else:
                 result = registration_icp_robust(clouds[0], clouds[1], r, result.transformation, kernel=kernel)
     return result
+
+
+# ---------------------------------------------------------------- information matrix of a registered pair
+_INFORMATION_STATUS = {1: "non-finite source points", 2: "the target grid is unusable (non-finite targets)"}
+
+
+def icp_information(grid, source, max_distance, transformation, stats=None):
+    """include/loner_hip.h: lnr_icp_information.  grid: an ops.NNGrid over the targets; source [m,3] as it is before
+    `transformation` (4x4, finite, affine).  -> the 6x6 fp64 information matrix on the device: sum of G^T G, G = [-[q]x | I], over
+    the correspondences within max_distance; zeros without one.  stats (a dict, optional) receives {"status", "n_correspondences",
+    "nonfinite_source"} (one device -> host read, only then; nothing is raised here)."""
+    src = _f64_points(source, "icp_information")
+    r = _positive(max_distance, "icp_information", "max_correspondence_distance")
+    T = ops.affine_f64(transformation, "icp_information: transformation must be a finite 4x4 affine matrix", finite=True)
+    dev = src.device
+    lib = load()
+    ws, need = _scratch(lib.lnr_icp_workspace(src.shape[0]), dev)
+    result = torch.empty(36, device=dev, dtype=torch.float64)
+    info = torch.empty(4, device=dev, dtype=torch.int64)
+    t16 = (C.c_double * 16)(*[float(x) for x in T.reshape(-1)])
+    check(lib.lnr_icp_information(_ptr(grid.buf), grid.n, _ptr(src), src.shape[0], t16, r, _ptr(ws), need, _ptr(result), _ptr(info),
+                                  _stream()), "lnr_icp_information")
+    if stats is not None:
+        c = info.cpu()
+        stats.update(status=int(c[0]), n_correspondences=int(c[1]), nonfinite_source=int(c[2]))
+    return result.reshape(6, 6)
+
+
+def get_information_matrix_from_point_clouds(source, target, max_correspondence_distance, transformation):
+    """open3d's get_information_matrix_from_point_clouds on the device -> numpy fp64 6x6 (rotation columns first, as the ICP's x).
+    The search grid's cell edge is the correspondence distance.  RuntimeError on a status bit; no correspondence gives zeros."""
+    r = _positive(max_correspondence_distance, "get_information_matrix_from_point_clouds", "max_correspondence_distance")
+    T = ops.affine_f64(transformation, "get_information_matrix_from_point_clouds: transformation must be a finite 4x4 affine matrix",
+                       finite=True)
+    stats = {}
+    out = icp_information(ops.NNGrid(target.points, r), source.points.to(target.points.device), r, T, stats)
+    _raise_status("get_information_matrix_from_point_clouds", stats["status"], _INFORMATION_STATUS)
+    return out.cpu().numpy()

@@ -27,7 +27,7 @@ ARCH = "gfx950"
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wno-unused-value"] + \
          os.environ.get("LNR_EXTRA_HIPCC_FLAGS", "").split()        # development switches, e.g. -DLNR_PHASE_TIMING (tools/README.md)
 # files whose float arithmetic must round exactly like the reference's torch CPU ops
-EXACT = {"lnr_sampler.hip", "lnr_rays.hip", "lnr_cloud.hip", "lnr_icp.hip", "lnr_cloud_tools.hip", "lnr_track.hip", "lnr_image.hip", "lnr_scan.hip", "lnr_mesh_tools.hip", "lnr_mesh_filters.hip", "lnr_raycast.hip", "lnr_tsdf.hip", "lnr_tsdf_sparse.hip", "lnr_global_reg.hip", "lnr_cloud_segment.hip"}
+EXACT = {"lnr_sampler.hip", "lnr_rays.hip", "lnr_cloud.hip", "lnr_icp.hip", "lnr_cloud_tools.hip", "lnr_track.hip", "lnr_image.hip", "lnr_scan.hip", "lnr_mesh_tools.hip", "lnr_mesh_filters.hip", "lnr_raycast.hip", "lnr_tsdf.hip", "lnr_tsdf_sparse.hip", "lnr_global_reg.hip", "lnr_cloud_segment.hip", "lnr_pose_graph.hip"}
 # per-source flags.  lnr_render.hip: its 32-samples-per-lane instantiations (2048-sample rays, the inference path) exceed the default
 # threshold for "#pragma unroll"; with a loop left rolled the per-lane arrays become scratch memory (820 bytes per lane: the compositing of
 # a rendered scan ran at 230 GB/s)
@@ -43,7 +43,7 @@ SOURCES = [("lnr_density_ht.hip", f"lnr_density_ht{ht}.o", [f"-DLNR_HT={ht}"]) f
           [("lnr_density_f16_bwd.hip", f"lnr_density_f16_bwd{part}_fq{fq}.o", [f"-DLNR_BWD_PART={part}", f"-DLNR_BWD_FQ={fq}"]) for part in (2, 1, 0) for fq in (0, 1)] + \
           [("lnr_density_f16_fwd.hip", f"lnr_density_f16_fwd{part}_fq{fq}.o", [f"-DLNR_FWD_PART={part}", f"-DLNR_FWD_FQ={fq}"]) for part in (1, 0) for fq in (0, 1)] + \
           [(s, s.replace(".hip", ".o"), EXTRA.get(s, [])) for s in
-           ("lnr_core.hip", "lnr_density.hip", "lnr_table_reduce.hip", "lnr_density_f16.hip", "lnr_density_bf3.hip", "lnr_density_wide.hip", "lnr_encode.hip", "lnr_sampler.hip", "lnr_render.hip", "lnr_render_peak.hip", "lnr_mesh.hip", "lnr_cloud.hip", "lnr_icp.hip", "lnr_global_reg.hip", "lnr_cloud_segment.hip", "lnr_cloud_tools.hip", "lnr_mesh_tools.hip", "lnr_mesh_filters.hip", "lnr_raycast.hip", "lnr_tsdf.hip", "lnr_tsdf_sparse.hip", "lnr_track.hip", "lnr_scan.hip", "lnr_rays.hip", "lnr_image.hip", "lnr_optim.hip", "lnr_pose.hip", "lnr_comm.hip")]
+           ("lnr_core.hip", "lnr_density.hip", "lnr_table_reduce.hip", "lnr_density_f16.hip", "lnr_density_bf3.hip", "lnr_density_wide.hip", "lnr_encode.hip", "lnr_sampler.hip", "lnr_render.hip", "lnr_render_peak.hip", "lnr_mesh.hip", "lnr_cloud.hip", "lnr_icp.hip", "lnr_pose_graph.hip", "lnr_global_reg.hip", "lnr_cloud_segment.hip", "lnr_cloud_tools.hip", "lnr_mesh_tools.hip", "lnr_mesh_filters.hip", "lnr_raycast.hip", "lnr_tsdf.hip", "lnr_tsdf_sparse.hip", "lnr_track.hip", "lnr_scan.hip", "lnr_rays.hip", "lnr_image.hip", "lnr_optim.hip", "lnr_pose.hip", "lnr_comm.hip")]
 
 
 def _hipcc():

@@ -23,6 +23,7 @@
 //              icp_corr<true>
 #include "lnr_cloud_knn.h"
 #include "lnr_eigen3.h"
+#include "lnr_solve6.h"
 
 namespace {
 
@@ -352,102 +353,6 @@ __global__ __launch_bounds__(CL_BLOCK) void icp_fold(const double* __restrict__ 
     st->n_corr = (unsigned long long)cnt;
 }
 
-// Eigen's LDLT (symmetric pivoting on the largest remaining |diagonal|, first index on ties; left-looking columns) and its solve with the
-// pseudo-inverse of D (|D_i| <= DBL_MIN gives a zero component), for A x = b.  A is overwritten.  Every loop is unrolled and every
-// runtime index (the pivot) becomes a compare against a static one, so that A stays in registers.
-__device__ inline void swap_if(bool c, double& a, double& b) {
-    const double t = a;
-    a = c ? b : a;
-    b = c ? t : b;
-}
-
-__device__ inline void ldlt_solve6(double A[6][6], const double b_in[6], double x[6]) {
-    int perm[6] = {0, 1, 2, 3, 4, 5};
-    bool stop = false;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        if (stop) continue;
-        int p = k;
-        double big = fabs(A[k][k]);
-#pragma unroll
-        for (int i = k + 1; i < 6; ++i)
-            if (fabs(A[i][i]) > big) { big = fabs(A[i][i]); p = i; }
-        perm[k] = p;
-#pragma unroll
-        for (int q = k + 1; q < 6; ++q) {                   // the symmetric swap of rows and columns k and p
-            const bool c = q == p;
-#pragma unroll
-            for (int j = 0; j < 6; ++j) swap_if(c, A[k][j], A[q][j]);
-#pragma unroll
-            for (int j = 0; j < 6; ++j) swap_if(c, A[j][k], A[j][q]);
-        }
-        if (k > 0) {
-            double temp[6];
-#pragma unroll
-            for (int j = 0; j < k; ++j) temp[j] = A[j][j] * A[k][j];
-            double s = 0.0;
-#pragma unroll
-            for (int j = 0; j < k; ++j) s = s + A[k][j] * temp[j];
-            A[k][k] = A[k][k] - s;
-#pragma unroll
-            for (int i = k + 1; i < 6; ++i) {
-                double t = 0.0;
-#pragma unroll
-                for (int j = 0; j < k; ++j) t = t + A[i][j] * temp[j];
-                A[i][k] = A[i][k] - t;
-            }
-        }
-        const double akk = A[k][k];
-        if (k == 0 && !(fabs(akk) > 0.0)) {                 // an all-zero diagonal: nothing is factored
-            perm[0] = 0;
-            stop = true;
-            continue;
-        }
-        if (fabs(akk) > 0.0) {
-#pragma unroll
-            for (int i = k + 1; i < 6; ++i) A[i][k] = A[i][k] / akk;
-        }
-    }
-    double y[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) y[i] = b_in[i];
-#pragma unroll
-    for (int k = 0; k < 6; ++k)
-#pragma unroll
-        for (int q = k + 1; q < 6; ++q) swap_if(perm[k] == q, y[k], y[q]);
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {                           // L (unit lower)
-        double s = 0.0;
-#pragma unroll
-        for (int j = 0; j < i; ++j) s = s + A[i][j] * y[j];
-        y[i] = y[i] - s;
-    }
-#pragma unroll
-    for (int i = 0; i < 6; ++i) y[i] = fabs(A[i][i]) > DBL_MIN ? y[i] / A[i][i] : 0.0;
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {                          // L^T
-        double s = 0.0;
-#pragma unroll
-        for (int j = i + 1; j < 6; ++j) s = s + A[j][i] * y[j];
-        y[i] = y[i] - s;
-    }
-#pragma unroll
-    for (int k = 5; k >= 0; --k)
-#pragma unroll
-        for (int q = k + 1; q < 6; ++q) swap_if(perm[k] == q, y[k], y[q]);
-#pragma unroll
-    for (int i = 0; i < 6; ++i) x[i] = y[i];
-}
-
-// TransformVector6dToMatrix4d: R = Rz(x2) Ry(x1) Rx(x0), t = x[3:6]
-__device__ inline void step_matrix(const double x[6], double U[16]) {
-    const double ca = cos(x[0]), sa = sin(x[0]), cb = cos(x[1]), sb = sin(x[1]), cc = cos(x[2]), sc = sin(x[2]);
-    U[0] = cc * cb; U[1] = (cc * sb) * sa - sc * ca; U[2] = (cc * sb) * ca + sc * sa; U[3] = x[3];
-    U[4] = sc * cb; U[5] = (sc * sb) * sa + cc * ca; U[6] = (sc * sb) * ca - cc * sa; U[7] = x[4];
-    U[8] = -sb;     U[9] = cb * sa;                  U[10] = cb * ca;                 U[11] = x[5];
-    U[12] = 0.0; U[13] = 0.0; U[14] = 0.0; U[15] = 1.0;
-}
-
 // one thread: the step from the last fold's system, update @ transformation, and whether the round runs
 __global__ void icp_solve(IcpState* st) {
     st->active = 0;
@@ -529,6 +434,69 @@ __global__ void icp_end(const IcpState* st, double* result, int64_t* info) {
     info[5] = (int64_t)st->sys[28];
     info[6] = st->done;
     info[7] = (int64_t)st->bad_covariances;
+}
+
+// ------------------------------------------------------------------------------------------------ information matrix
+// GetInformationMatrixFromPointClouds: the source moved by T (transform_point's rounding), icp_corr's search, and per correspondence
+// with the target q the 21 upper-triangle terms of G^T G, G = [-[q]x | I], each ((G0a G0b + G1a G1b) + G2a G2b); term 21 counts the
+// correspondences, term 22 the non-finite source points.  Per thread in source order, then per block, as icp_corr's sums.
+#define INFO_TERMS 23
+__global__ __launch_bounds__(CL_BLOCK) void icp_info_corr(GridView g, const double* __restrict__ src, uint32_t n_src, Affine T, double r,
+                                                          double* __restrict__ part) {
+    __shared__ double lds[CL_BLOCK / 64];
+    const CloudParams* p = g.p;
+    const double r2 = r * r;
+    const double dmax = (double)(p->dims[0] > p->dims[1] ? (p->dims[0] > p->dims[2] ? p->dims[0] : p->dims[2])
+                                                         : (p->dims[1] > p->dims[2] ? p->dims[1] : p->dims[2]));
+    const int64_t max_shell = (int64_t)fmin(ceil(r / p->edge) + 1.0, dmax);
+    const bool any = p->n > 0;
+    double acc[INFO_TERMS];
+#pragma unroll
+    for (int v = 0; v < INFO_TERMS; ++v) acc[v] = 0.0;
+    for (uint32_t i = blockIdx.x * CL_BLOCK + threadIdx.x; i < n_src; i += gridDim.x * CL_BLOCK) {
+        double s3[3];
+        transform_point(src + 3 * (size_t)i, T.t, s3, 0);
+        double best;
+        uint32_t id, pos;
+        const bool ok = finite3(s3[0], s3[1], s3[2]);
+        if (!ok) acc[22] = acc[22] + 1.0;
+        if (!(ok && any && nearest_within(g, s3[0], s3[1], s3[2], r2, max_shell, best, id, pos))) continue;
+        const double* q = g.pts + 3 * (size_t)pos;
+        const double G[3][6] = {{0.0, q[2], -q[1], 1.0, 0.0, 0.0}, {-q[2], 0.0, q[0], 0.0, 1.0, 0.0}, {q[1], -q[0], 0.0, 0.0, 0.0, 1.0}};
+        int v = 0;
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int b = a; b < 6; ++b, ++v) acc[v] = acc[v] + ((G[0][a] * G[0][b] + G[1][a] * G[1][b]) + G[2][a] * G[2][b]);
+        acc[21] = acc[21] + 1.0;
+    }
+#pragma unroll
+    for (int v = 0; v < INFO_TERMS; ++v) {
+        const double t = block_sum(acc[v], lds);
+        if (threadIdx.x == 0) part[(size_t)ICP_PART_STRIDE * blockIdx.x + v] = t;
+    }
+}
+
+// one workgroup: icp_fold's order over the partials, the symmetric 6x6 and the info words
+__global__ __launch_bounds__(CL_BLOCK) void icp_info_fold(const double* __restrict__ part, uint32_t n_part, const CloudParams* p,
+                                                          uint32_t n_targets, double* __restrict__ result, int64_t* __restrict__ info) {
+    __shared__ double lds[CL_BLOCK / 64];
+    __shared__ double tot[INFO_TERMS];
+    for (int v = 0; v < INFO_TERMS; ++v) {
+        double a = 0.0;
+        for (uint32_t b = threadIdx.x; b < n_part; b += CL_BLOCK) a = a + part[(size_t)ICP_PART_STRIDE * b + v];
+        const double t = block_sum(a, lds);
+        if (threadIdx.x == 0) tot[v] = t;
+    }
+    if (threadIdx.x != 0) return;
+    int v = 0;
+    for (int a = 0; a < 6; ++a)
+        for (int b = a; b < 6; ++b, ++v) result[6 * a + b] = result[6 * b + a] = tot[v];
+    const bool bad_grid = (p->status & CL_ST_NONFINITE) || p->n != n_targets;
+    info[0] = (tot[22] > 0.0 ? (int64_t)ICP_ST_NONFINITE_SOURCE : 0) | (bad_grid ? (int64_t)ICP_ST_NONFINITE_TARGET : 0);
+    info[1] = (int64_t)tot[21];
+    info[2] = (int64_t)tot[22];
+    info[3] = 0;
 }
 
 // ------------------------------------------------------------------------------------------------ host
@@ -730,5 +698,29 @@ extern "C" int lnr_cloud_plane_covariances(const double* normals, int64_t n, dou
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(plane_covariances, dim3(blocks_for(n)), dim3(CL_BLOCK), 0, st, normals, (uint32_t)n, epsilon, covariances);
     LNR_CHECK_LAUNCH("lnr_cloud_plane_covariances");
+    return LNR_OK;
+}
+
+extern "C" int lnr_icp_information(const void* grid, int64_t n_targets, const double* source, int64_t n_source, const double* transformation,
+                                   double max_distance, void* workspace, size_t workspace_bytes, double* result_dev, int64_t* info_dev,
+                                   void* stream) {
+    CL_REQUIRE_COUNTS("lnr_icp_information", n_targets, "targets", n_source, "source points");
+    LNR_REQUIRE(isfinite(max_distance) && max_distance > 0.0, "lnr_icp_information: max_distance must be finite and > 0, got %g", max_distance);
+    LNR_REQUIRE(grid && transformation && workspace && result_dev && info_dev && (n_source == 0 || source), "lnr_icp_information: null argument");
+    const IcpLayout l = icp_layout(n_source);
+    LNR_REQUIRE(workspace_bytes >= l.total, "lnr_icp_information: workspace of %zu bytes, %zu needed", workspace_bytes, l.total);
+    Affine T;
+    const int bad = affine_from_host(transformation, &T);
+    LNR_REQUIRE(bad < 0, "lnr_icp_information: non-finite transformation entry %d", bad);
+    LNR_REQUIRE(transformation[12] == 0.0 && transformation[13] == 0.0 && transformation[14] == 0.0 && transformation[15] == 1.0,
+                "lnr_icp_information: transformation's bottom row must be [0, 0, 0, 1]");
+    hipStream_t st = (hipStream_t)stream;
+    LnrProfScope prof("icp_information", st);
+    double* part = (double*)((char*)workspace + l.part);
+    const GridView g = grid_view(grid, n_targets);
+    const uint32_t nb = icp_blocks(n_source);
+    hipLaunchKernelGGL(icp_info_corr, dim3(nb), dim3(CL_BLOCK), 0, st, g, source, (uint32_t)n_source, T, max_distance, part);
+    hipLaunchKernelGGL(icp_info_fold, dim3(1), dim3(CL_BLOCK), 0, st, (const double*)part, nb, g.p, (uint32_t)n_targets, result_dev, info_dev);
+    LNR_CHECK_LAUNCH("lnr_icp_information");
     return LNR_OK;
 }

@@ -30,6 +30,8 @@ RANSAC_CHUNK = 2048          # LNR_RANSAC_CHUNK
 RANSAC_MAX_HYPOTHESES = 1 << 22
 STREAM_RANSAC = 0x524E534300000000           # LNR_STREAM_RANSAC
 STREAM_PLANE = 0x504C414E00000000            # LNR_STREAM_PLANE
+PG_MAX_NODES = 1 << 24       # LNR_PG_MAX_NODES
+PG_MAX_EDGES = 1 << 26       # LNR_PG_MAX_EDGES
 MOCOMP_CONSTS = 30           # LNR_MOCOMP_CONSTS
 SKY_MAX_RAYS = 65160         # LNR_SKY_MAX_RAYS
 SCAN_MAX_FOV_SEGMENTS = 8    # LNR_SCAN_MAX_FOV_SEGMENTS
@@ -167,6 +169,16 @@ _SIGNATURES = {
     "lnr_cloud_dbscan": (C.c_int, [P, C.c_int64, C.c_double, C.c_int32, P, P, C.c_size_t, P, P]),
     "lnr_plane_workspace": (C.c_size_t, [C.c_int64, C.c_int64]),
     "lnr_cloud_segment_plane": (C.c_int, [P, C.c_int64, C.c_double, C.c_int64, C.c_uint64, C.c_int32, P, P, P, C.c_size_t, P, P]),
+    "lnr_icp_information": (C.c_int, [P, C.c_int64, P, C.c_int64, C.POINTER(C.c_double), C.c_double, P, C.c_size_t, P, P, P]),
+    "lnr_pose_graph_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "lnr_pose_graph_workspace": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "lnr_pose_graph_build": (C.c_int, [P, P, C.c_int64, C.c_int64, P, C.c_size_t, P, C.c_size_t, P, P]),
+    "lnr_pose_graph_linearize": (C.c_int, [P, C.c_int64, C.c_int64, P, P, P, P, P, P, P, C.c_int32, P, P, P, P, P, P, P, C.c_size_t, P, P]),
+    "lnr_pose_graph_solve": (C.c_int, [P, C.c_int64, C.c_int64, P, P, P, P, P, P, P, C.c_double, C.c_int32, C.c_double, C.c_int32, P,
+                                       C.c_size_t, P, P, P]),
+    "lnr_pose_graph_optimize": (C.c_int, [P, C.c_int64, C.c_int64, P, P, P, P, P, P, P, C.c_int32, C.c_double, C.c_double, C.c_int32,
+                                          C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, P, C.c_size_t, P,
+                                          C.c_int32, P, P, P]),
     "lnr_mesh_sample_workspace": (C.c_size_t, [C.c_int64]),
     "lnr_mesh_sample_points": (C.c_int, [P, C.c_int64, P, C.c_int64, C.c_int64, C.c_uint64, P, C.c_size_t, P, P, P, P]),
     "lnr_cloud_tools_workspace": (C.c_size_t, [C.c_int64]),
